@@ -9,10 +9,12 @@ frames already resident in HBM.  `value` is that figure.  Beside it, never as `v
 single entry point itm_process_frame and through itm_process_frame_ahead (which needs the NEXT frame's pose before
 this frame is done: fine for an offline sequence, impossible for a closed tracking loop).
 
-Short runs: with --steps < 100 the timed region (exactly --steps frames between two barriers) is repeated until at
-least 0.25 s have been measured; `value` / `ms_per_step` are those of the MEDIAN repetition, `repetitions` says how
-many there were.  The roofline kernel is never timed inside the timed region: one extra, untimed repetition brackets
-EVERY launch of it (and of the integration and the visible-list launch) with HIP events, at least 64 samples.
+The timed region is exactly --steps frames between two barriers; `ms_per_step` is its time divided by --steps.  Only with
+--min-measured-s > 0 (off by default) is a region of --steps < 100 frames repeated until that much has been measured;
+`value` / `ms_per_step` are then those of the MEDIAN repetition, `repetitions` says how many there were.  --dump-outputs DIR
+writes what the last timed frame computed (ICP maps, counters, a seeded sample of the voxel pool) as .npy files.
+The roofline kernel is never timed inside the timed region: one extra, untimed repetition brackets EVERY launch of it
+(and of the integration and the visible-list launch) with HIP events, at least 64 samples.
 
 Workloads (--config, names in config.workload):
   2 (default, the headline): BASELINE configs[1] -- synthetic 640x480 depth (sphere + wall, SURVEY 8d bench
@@ -87,7 +89,10 @@ def parse():
     ap.add_argument("--frame-call", choices=["four", "process_frame", "ahead"], default="four",
                     help="how the timed region issues a frame: the reference's four engine calls (default, the headline), itm_process_frame, or "
                          "itm_process_frame_ahead (a marked line: the next frame's pose is handed over before this frame is done)")
-    ap.add_argument("--min-measured-s", type=float, default=0.25, help="runs with --steps < 100 repeat the timed region until this much has been measured")
+    ap.add_argument("--min-measured-s", type=float, default=0.0,
+                    help="runs with --steps < 100 repeat the timed region until this much has been measured (0 = off: exactly --steps timed frames)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what its last frame computed (rank 0, stream 0) as DIR/<name>.npy (float32/float64, < 64 MB)")
     ap.add_argument("--raw-serial", action="store_true", help="raw-depth legs: the upload on the frame's own stream instead of the library's stager (A/B)")
     ap.add_argument("--raw-depth", action="store_true",
                     help="SURVEY 8d second figure as the run's value: each step uploads the 16-bit raw frame from pinned host memory "
@@ -551,8 +556,9 @@ def worker(args) -> int:
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         return float(tt.item()), mine
 
-    # Short runs are repeated: 20 frames are 1.7 ms, less than the jitter of one host wake-up.  The number of repetitions follows from
-    # the first one (the same on every rank: it is computed from the all-reduced time), the MEDIAN repetition is the one reported.
+    # With --min-measured-s, short runs are repeated: 20 frames are 1.7 ms, less than the jitter of one host wake-up.  The number of
+    # repetitions follows from the first one (the same on every rank: it is computed from the all-reduced time), the MEDIAN repetition
+    # is the one reported.  Off by default: the timed region is then exactly --steps frames.
     reps = [timed_region(args.warmup)]
     if args.steps < 100 and args.min_measured_s > 0:
         want = int(min(2000, max(0, -(-args.min_measured_s // max(reps[0][0], 1e-6)) - 1)))
@@ -561,6 +567,8 @@ def worker(args) -> int:
     order = sorted(range(len(reps)), key=lambda r: reps[r][0])
     med = order[len(order) // 2]
     elapsed, elapsed_local = reps[med]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, streams[0], capi)      # before any later leg resets or refills the scene
     fps_minmax = None
     if world > 1:
         tn = torch.tensor([elapsed_local], dtype=torch.float64, device=ctl_device)
@@ -832,6 +840,37 @@ def worker(args) -> int:
             print(f"bench.py: PARITY CHECK FAILED: {failed}", file=sys.stderr)
             return 4
     return 0
+
+
+DUMP_VOXEL_SAMPLE = 1 << 19     # voxels of the fixed, seeded sample of the voxel pool written by --dump-outputs
+DUMP_SEED = 20240601
+
+
+def dump_outputs(directory, s, capi):
+    """--dump-outputs: what the last timed frame of stream `s` left for its caller -- the ICP maps of itm_create_icp_maps (points,
+    normals), the scene's counters and a fixed, seeded sample of its voxel pool (sdf, depth weight, colour) -- as float32 / float64
+    .npy files.  The inputs are synthetic and seeded, so two builds run with the same arguments can be compared file by file."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    if s.hip_stream is not None:
+        s.torch.cuda.synchronize()
+    c = s.scene.counters(s.rs)
+    vox = s.scene.download(capi.BUF_VOXEL_BLOCKS)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(len(vox), size=min(DUMP_VOXEL_SAMPLE, len(vox)), replace=False))
+    sample = vox[idx]
+    out = {"icp_points": s.points.cpu().numpy().astype(np.float32),
+           "icp_normals": s.normals.cpu().numpy().astype(np.float32),
+           "counters": np.array([c["lastFreeBlockId"], c["lastFreeExcessListId"], c["noVisibleEntries"]], dtype=np.float64),
+           "voxel_sample_index": idx.astype(np.float64),
+           "voxel_sample_sdf": sample["sdf"].astype(np.float32),
+           "voxel_sample_w_depth": sample["w_depth"].astype(np.float32)}
+    if "clr" in sample.dtype.names:
+        out["voxel_sample_clr"] = sample["clr"].astype(np.float32)
+        out["voxel_sample_w_color"] = sample["w_color"].astype(np.float32)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= 64 << 20, f"--dump-outputs: {total} bytes"
+    for name, a in out.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 # -------------------------------------------------------------------------------------------------------------

@@ -20,12 +20,19 @@ def oracle():
 
 
 @pytest.fixture(scope="session")
-def reference():
+def reference_records():
     import itm_testlib
-    be = itm_testlib.reference_backend()
-    if be is None:
-        pytest.skip("reference build (oracle/_ref) not available on this machine")
-    return be
+    records = itm_testlib.ReferenceRecords()
+    yield records
+    records.save()
+
+
+@pytest.fixture
+def ref(request, reference_records):
+    """The reference where its build exists, else its record (tests/golden/reference_records.json): see itm_testlib.ReferenceCheck."""
+    import itm_testlib
+    test_id = f"{request.node.module.__name__}::{request.node.name}"
+    return itm_testlib.ReferenceCheck(reference_records, test_id, itm_testlib.reference_backend())
 
 
 @pytest.fixture(scope="session")

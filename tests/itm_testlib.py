@@ -5,6 +5,7 @@ Only test code may load anything from oracle/ (see oracle/itm_oracle.cpp header)
 """
 from __future__ import annotations
 
+import json
 import os
 import subprocess
 import sys
@@ -70,6 +71,81 @@ def reference_pool40000_backend() -> Optional[Backend]:
             subprocess.run(["make", "-C", ORACLE_DIR, "ref40000"], check=True, capture_output=True)
         _cache["ref40000"] = Backend(REF_POOL40000_LIB, "itmr_") if os.path.exists(REF_POOL40000_LIB) else None
     return _cache["ref40000"]
+
+
+# Oracle outputs certified against the reference: digests of what the oracle computed in a test that compared it, bit for bit, with
+# the reference's own engines.  Where the reference build is absent those tests still run and the oracle must reproduce the record.
+REFERENCE_RECORDS = os.path.join(GOLDEN_DIR, "reference_records.json")
+RECORD_REFERENCE = os.environ.get("ITM_RECORD_REFERENCE") == "1"      # rewrite the records (needs the reference build)
+
+
+def digest_tree(obj, path="", out=None) -> dict:
+    """{path: digest} of every array / scalar in a (nested) test result: dataclasses, dicts, lists, tuples, numpy arrays (structured
+    ones field by field, so padding bytes never count), numbers, strings and bytes."""
+    import dataclasses
+    import hashlib
+    out = {} if out is None else out
+    if dataclasses.is_dataclass(obj) and not isinstance(obj, type):
+        for f in dataclasses.fields(obj):
+            digest_tree(getattr(obj, f.name), f"{path}.{f.name}", out)
+    elif isinstance(obj, dict):
+        for k in sorted(obj, key=str):
+            digest_tree(obj[k], f"{path}.{k}", out)
+    elif isinstance(obj, (list, tuple)):
+        for i, v in enumerate(obj):
+            digest_tree(v, f"{path}[{i}]", out)
+    elif isinstance(obj, np.ndarray) and obj.dtype.names:
+        for name in obj.dtype.names:
+            digest_tree(obj[name], f"{path}.{name}", out)
+    elif isinstance(obj, np.ndarray):
+        a = np.ascontiguousarray(obj)
+        out[path] = f"{a.dtype.str}{list(a.shape)}:" + hashlib.sha256(a.tobytes()).hexdigest()
+    elif isinstance(obj, bytes):
+        out[path] = "bytes:" + hashlib.sha256(obj).hexdigest()
+    elif obj is None or isinstance(obj, (bool, int, float, str, np.generic)):
+        out[path] = repr(obj.item() if isinstance(obj, np.generic) else obj)
+    else:
+        raise TypeError(f"digest_tree: {path}: {type(obj).__name__}")
+    return out
+
+
+class ReferenceRecords:
+    """tests/golden/reference_records.json: {"<test module>::<test name>::<what>": digest_tree of the certified oracle output}."""
+
+    def __init__(self, path=REFERENCE_RECORDS):
+        self.path, self.changed = path, False
+        self.data = {}
+        if os.path.exists(path):
+            with open(path) as f:
+                self.data = json.load(f)
+
+    def save(self):
+        if self.changed:
+            with open(self.path, "w") as f:
+                json.dump(self.data, f, indent=0, sort_keys=True)
+                f.write("\n")
+
+
+class ReferenceCheck:
+    """One test's view of the reference: `backend` is the reference's CPU engines where their build exists (None elsewhere);
+    check(what, value) pins `value` -- an output of the oracle that the test has just compared with the reference wherever it could --
+    to its record.  With the reference present and ITM_RECORD_REFERENCE=1 the record is (re)written instead."""
+
+    def __init__(self, records: ReferenceRecords, test_id: str, backend: Optional[Backend]):
+        self.records, self.test_id, self.backend = records, test_id, backend
+
+    def check(self, what: str, value):
+        key = f"{self.test_id}::{what}"
+        got = digest_tree(value)
+        if RECORD_REFERENCE:
+            assert self.backend is not None, "ITM_RECORD_REFERENCE=1 needs the reference build (oracle/_ref)"
+            self.records.data[key] = got
+            self.records.changed = True
+            return
+        want = self.records.data.get(key)
+        assert want is not None, f"{key}: no record in {os.path.basename(self.records.path)} (ITM_RECORD_REFERENCE=1 where the reference build exists)"
+        diff = sorted(k for k in set(want) | set(got) if want.get(k) != got.get(k))
+        assert not diff, f"{key}: differs from the output certified against the reference in {len(diff)} place(s): {diff[:8]}"
 
 
 def hip_backend() -> Backend:

@@ -92,3 +92,25 @@ def test_rank_cpu_sets_are_disjoint_and_cover():
         assert all(sets) and all(s <= avail for s in sets)
         assert sum(len(s) for s in sets) == len(set().union(*sets))               # pairwise disjoint
     assert bench.rank_cpu_set(0, 1) is None
+
+
+def test_bench_times_exactly_steps_and_dumps_the_last_frame(tmp_path):
+    """--steps is the number of timed frames (one repetition by default) and --dump-outputs writes what the last of them left for the
+    caller as float32 / float64 .npy files, identical from run to run with the same arguments."""
+    import numpy as np
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        res = _run(["--steps", "3", "--warmup", "1", "--dump-outputs", str(d)])
+        assert res.returncode == 0, res.stderr[-2000:]
+        out = json.loads(res.stdout.strip().splitlines()[-1])
+        assert out["steps"] == 3 and out["repetitions"]["count"] == 1 and out["ms_per_step"] > 0
+        assert abs(out["ms_per_step"] * 3 / 1e3 - out["repetitions"]["measured_s"]) < 1e-3
+        dumps.append({f.stem: np.load(f) for f in sorted(d.glob("*.npy"))})
+    a, b = dumps
+    assert {"icp_points", "icp_normals", "counters", "voxel_sample_sdf", "voxel_sample_w_depth"} <= set(a)
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    assert a["icp_points"].shape == (480, 640, 4) and np.isfinite(a["icp_points"]).any()
+    assert a["counters"][2] > 1000                       # visible blocks of the last frame
+    assert set(a) == set(b) and all(np.array_equal(a[k], b[k], equal_nan=True) for k in a)

@@ -81,21 +81,39 @@ def test_calib_variants(hip_host, tmp_path):
         hip_host.read_rgbd_calib(p)
 
 
-def test_against_reference_both_directions(hip_host, reference, tmp_path):
+def test_against_reference_both_directions(hip_host, ref, tmp_path):
+    reference = ref.backend
     depth, rgba = images()
+    written = {}
     for writer, reader in ((hip_host, reference), (reference, hip_host)):
+        if writer is None or reader is None:
+            continue
         p, q = str(tmp_path / "d.pgm"), str(tmp_path / "c.ppm")
         writer.write_image(p, depth); writer.write_image(q, rgba)
         assert np.array_equal(reader.read_depth_image(p), depth)
         assert np.array_equal(reader.read_rgb_image(q), rgba)
+    # the files the product writes, as the reference's readers accepted them (recorded where the reference is absent)
+    p, q = str(tmp_path / "d.pgm"), str(tmp_path / "c.ppm")
+    hip_host.write_image(p, depth); hip_host.write_image(q, rgba)
+    written["depth_pgm"], written["rgb_ppm"] = open(p, "rb").read(), open(q, "rb").read()
     a, b = str(tmp_path / "a.pgm"), str(tmp_path / "b.pgm")
     f = (np.abs(depth).astype(np.float32) / 1000.0); f[0, 0] = -1.0
-    hip_host.write_image(a, f); reference.write_image(b, f)
-    assert open(a, "rb").read() == open(b, "rb").read()
-    hip_host.write_image(a, depth); reference.write_image(b, depth)
-    assert open(a, "rb").read() == open(b, "rb").read()
+    hip_host.write_image(a, f)
+    written["float_pgm"] = open(a, "rb").read()
+    if reference is not None:
+        reference.write_image(b, f)
+        assert open(a, "rb").read() == open(b, "rb").read()
+    hip_host.write_image(a, depth)
+    if reference is not None:
+        reference.write_image(b, depth)
+        assert open(a, "rb").read() == open(b, "rb").read()
     ca = hip_host.read_rgbd_calib(os.path.join(T.GOLDEN_DIR, "calib_synthetic.txt"))
-    cb = reference.read_rgbd_calib(os.path.join(T.GOLDEN_DIR, "calib_synthetic.txt"))
-    for f_ in ("intr_rgb", "intr_d", "rgb_to_depth", "rgb_to_depth_inv", "disparityParams"):
-        assert list(getattr(ca, f_)) == list(getattr(cb, f_)), f_
-    assert ca.disparityType == cb.disparityType
+    fields = ("intr_rgb", "intr_d", "rgb_to_depth", "rgb_to_depth_inv", "disparityParams")
+    if reference is not None:
+        cb = reference.read_rgbd_calib(os.path.join(T.GOLDEN_DIR, "calib_synthetic.txt"))
+        for f_ in fields:
+            assert list(getattr(ca, f_)) == list(getattr(cb, f_)), f_
+        assert ca.disparityType == cb.disparityType
+    written["calib"] = {f_: [float(x) for x in getattr(ca, f_)] for f_ in fields}
+    written["calib"]["disparityType"] = int(ca.disparityType)
+    ref.check("files", written)

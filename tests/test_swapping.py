@@ -90,20 +90,21 @@ def sanity(frames):
     assert int(np.count_nonzero(frames[-1]["hash"]["ptr"] == -1)) < out_peak
 
 
-def test_oracle_swapping_equals_the_reference_engine(oracle):
-    ref = T.reference_backend()
-    if ref is None:
-        pytest.skip("reference build not available")
-    a, b = run(oracle), run(ref)
-    compare(a, b, "oracle vs reference")
-    sanity(b)
+def test_oracle_swapping_equals_the_reference_engine(oracle, ref):
+    a = run(oracle)
+    if ref.backend is not None:
+        b = run(ref.backend)
+        compare(a, b, "oracle vs reference")
+        sanity(b)
+    sanity(a)
+    ref.check("frames", a)
 
 
-def test_oracle_swapping_colour_voxels_equal_the_reference_engine(oracle):
-    ref = T.reference_backend()
-    if ref is None:
-        pytest.skip("reference build not available")
-    compare(run(oracle, capi.VOXEL_S_RGB, True, frames=9), run(ref, capi.VOXEL_S_RGB, True, frames=9), "oracle vs reference (colour)")
+def test_oracle_swapping_colour_voxels_equal_the_reference_engine(oracle, ref):
+    a = run(oracle, capi.VOXEL_S_RGB, True, frames=9)
+    if ref.backend is not None:
+        compare(a, run(ref.backend, capi.VOXEL_S_RGB, True, frames=9), "oracle vs reference (colour)")
+    ref.check("frames", a)
 
 
 @pytest.mark.gpu

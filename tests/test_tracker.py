@@ -85,32 +85,41 @@ def holes_image():
     return img
 
 
-def test_subsample_oracle_vs_reference(oracle, reference):
+def test_subsample_oracle_vs_reference(oracle, ref):
     img = holes_image()
-    assert np.array_equal(subsample(oracle, img), subsample(reference, img))
+    a = subsample(oracle, img)
+    if ref.backend is not None:
+        assert np.array_equal(a, subsample(ref.backend, img))
+    ref.check("subsample", a)
 
 
 @pytest.mark.parametrize("it", [1, 2, 3])
-def test_g_and_h_oracle_vs_reference(oracle, reference, it):
+def test_g_and_h_oracle_vs_reference(oracle, ref, it):
     res = []
-    for be in (oracle, reference):
+    for be in (oracle, ref.backend) if ref.backend is not None else (oracle,):
         ses, v, nxt = build_maps(be)
         inv = np.linalg.inv(np.asarray(v.M_d, np.float64).reshape(4, 4).T).T.astype(np.float32).reshape(16)   # any fixed matrix works: both get the same
         res.append(g_and_h(be, be.to_backend(nxt), W, H, SC.intr(), ses, inv, v.M_d, 0.01, it))
         ses.close()
-    (n0, f0, g0, h0), (n1, f1, g1, h1) = res
-    assert n0 == n1 and n0 > 5000
+    n0, f0, g0, h0 = res[0]
+    assert n0 > 5000
     np_ = 3 if it != 3 else 6
-    assert f0 == f1 and np.array_equal(g0[:np_], g1[:np_]) and np.array_equal(h0[:np_, :np_], h1[:np_, :np_])
+    if len(res) > 1:
+        n1, f1, g1, h1 = res[1]
+        assert n0 == n1
+        assert f0 == f1 and np.array_equal(g0[:np_], g1[:np_]) and np.array_equal(h0[:np_, :np_], h1[:np_, :np_])
+    ref.check("g_and_h", (n0, f0, g0[:np_], h0[:np_, :np_]))
 
 
-def test_track_camera_oracle_vs_reference(oracle, reference):
+def test_track_camera_oracle_vs_reference(oracle, ref):
     poses = []
-    for be in (oracle, reference):
+    for be in (oracle, ref.backend) if ref.backend is not None else (oracle,):
         ses, v, nxt = build_maps_vga(be)
         poses.append(track(be, ses, v, nxt))
         ses.close()
-    assert np.array_equal(poses[0], poses[1])
+    if len(poses) > 1:
+        assert np.array_equal(poses[0], poses[1])
+    ref.check("pose", poses[0])
     # and it actually tracks: the camera moved 1 cm along x between the two frames
     # (translation only: a sphere on the optical axis in front of a frontal wall leaves the roll unconstrained)
     truth = synth.pose_matrix(SC_VGA.position(SC_VGA.frames))
