@@ -435,6 +435,51 @@ int ITM_FN(tracker_track_camera)(itm_tracker* tracker, const itm_tracker_config*
                                  const float* pointsMap, const float* normalsMap, const float scenePose[16],
                                  float M_d_out[16], itm_stream stream);
 
+/* ---- colour (photometric) tracker ------------------------------------------------------------------
+ * Aligns the rgb image of a view with the coloured point cloud CreatePointCloud wrote for the previous pose.  Device-specific half:
+ *   ITMColorTracker::PrepareForEvaluation           Engine/ITMColorTracker.cpp:49-68 (CopyImage, FilterSubsample, GradientX / Y:
+ *                                                   DeviceAgnostic/ITMLowLevelEngine.h:7-24,73-123, CPU/ITMLowLevelEngine_CPU.cpp:35-104)
+ *   ITMColorTracker_CPU::F_oneLevel / G_oneLevel    DeviceSpecific/CPU/ITMColorTracker_CPU.cpp:14-101,
+ *                                                   DeviceAgnostic/ITMColorTracker.h (getColorDifferenceSq, computePerPointGH_rt_Color)
+ * and the host Levenberg-Marquardt loop around it:
+ *   ITMColorTracker::TrackCamera / minimizeLM / ApplyDelta   Engine/ITMColorTracker.cpp:25-47,70-234
+ * One handle owns the rgb pyramid, its gradients and the reduction buffers of ONE tracker; calls on a handle are serialised by the
+ * handle, different handles are independent (as itm_tracker).  Sums are added in the fixed-order double-precision tree of the ICP
+ * tracker: deterministic, within float rounding of the reference's sequential float sums, the valid count exact. */
+typedef struct itm_colour_tracker itm_colour_tracker;
+typedef struct itm_colour_eval {
+  float f;                 /* F_oneLevel: sum of squared colour differences * noTotalPoints / noValidPoints; 0x7f800000 (MY_INF, read as
+                              the float 2139095040) when nothing is valid                                                              */
+  int32_t noValidPoints;   /* countedPoints_valid                                                                                    */
+  int32_t numPara;         /* numParameters(): 3 for ROTATION, 6 for TRANSLATION and BOTH                                             */
+  float nabla[6];          /* G_oneLevel gradient (numPara entries), scaled as f; zero unless asked for                             */
+  float hessian[36];       /* G_oneLevel hessian, hessian[para + col * numPara] (numPara^2 entries, symmetric)                        */
+} itm_colour_eval;
+int ITM_FN(colour_tracker_create)(itm_colour_tracker** out);
+int ITM_FN(colour_tracker_destroy)(itm_colour_tracker* tracker);
+/* PrepareForEvaluation: level 0 = a copy of view->rgb (w_rgb x h_rgb), level i = FilterSubsample of level i-1 (floor halves),
+ * gradients X / Y of every level (short4, borders 0).  levels: 1..8. */
+int ITM_FN(colour_tracker_prepare)(itm_colour_tracker* tracker, const itm_view* view, int levels, itm_stream stream);
+/* Synchronous read-back of one prepared level: rgb uchar4[h*w], gx / gy short4[h*w] (host pointers, each may be NULL). */
+int ITM_FN(colour_tracker_read_level)(itm_colour_tracker* tracker, int level, uint8_t* rgb, int16_t* gx, int16_t* gy, int* w, int* h,
+                                      itm_stream stream);
+/* F_oneLevel (and G_oneLevel at the same pose when wantGH != 0, from the same pass) on a prepared level: locations / colours =
+ * trackingState->pointCloud (Vector4f[noTotalPoints], device), pose = the rgb camera's world->camera matrix, intrinsics =
+ * view->intr_rgb / 2^level of the last prepare.  Synchronises `stream`. */
+int ITM_FN(colour_tracker_evaluate)(itm_colour_tracker* tracker, int level, const float* locations, const float* colours,
+                                    int noTotalPoints, const float pose[16], int iterationType, int wantGH, itm_colour_eval* out,
+                                    itm_stream stream);
+/* ITMColorTracker::TrackCamera: prepares the pyramid from view->rgb (cfg->noHierarchyLevels levels, cfg->trackingRegime per level;
+ * noICPRunTillLevel / distThresh / terminationThreshold are not used by this tracker), tracks from view->M_d through the
+ * rgb -> depth extrinsics, writes the refined and coerced pose_d to M_d_out.  The point count is read on the device from rs
+ * (itm_counters::noTotalPoints left by create_point_cloud; no extra host round trip), or is noTotalPoints when rs is NULL.
+ * ITM_TRACKER_ITERATION_NONE is rejected (the reference leaves the step undefined).  Synchronises `stream`. */
+int ITM_FN(colour_tracker_track_camera)(itm_colour_tracker* tracker, const itm_tracker_config* cfg, const itm_view* view,
+                                        const itm_render_state* rs, const float* locations, const float* colours, int noTotalPoints,
+                                        float M_d_out[16], itm_stream stream);
+/* Evaluations (each one pass over the point cloud) of the last colour_tracker_track_camera call on this handle. */
+int ITM_FN(colour_tracker_evaluations)(const itm_colour_tracker* tracker, int* out);
+
 /* ---- state access ------------------------------------------------------------------------- */
 /* Blocks until `stream` has drained, then reads the device-side counters. */
 int ITM_FN(get_counters)(const itm_scene* scene, const itm_render_state* rs, itm_counters* out,

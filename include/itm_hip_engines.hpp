@@ -113,6 +113,8 @@ struct ITMLibSettings {
   int trackingRegime[8] = {ITM_TRACKER_ITERATION_BOTH, ITM_TRACKER_ITERATION_BOTH, ITM_TRACKER_ITERATION_ROTATION, ITM_TRACKER_ITERATION_ROTATION,
                            ITM_TRACKER_ITERATION_ROTATION, 0, 0, 0};
   int noICPRunTillLevel = 0;
+  // TRACKER_COLOR: false (default) keeps this fork's behaviour, poses from outside; true builds ITMColorTracker_HIP
+  bool useColourTracker = false;
 };
 
 struct ITMSceneParams : itm_scene_params {
@@ -413,6 +415,41 @@ class ITMDepthTrackerAdapter : public ITMTracker {
   void TrackCamera(ITMTrackingState* ts, const ITMView* view) override { t->TrackCamera(ts, view); }
 };
 
+// ITMColorTracker (Engine/ITMColorTracker.h, .cpp:25-47): TrackCamera aligns the view's rgb image with the coloured point cloud that
+// Prepare's CreatePointCloud left in the tracking state; pyramid, evaluation and reduction on the GPU (itm_colour_tracker_*).  The
+// point count is read on the device from the render state CreatePointCloud wrote into.
+class ITMColorTracker_HIP {
+  itm_tracker_config cfg;
+  itm_colour_tracker* tracker = nullptr;   // this object's rgb hierarchy + reduction buffers; one per tracker object
+
+ public:
+  itm_stream stream = nullptr;
+  ITMColorTracker_HIP(const int* trackingRegime, int noHierarchyLevels) {
+    std::memset(&cfg, 0, sizeof cfg);
+    cfg.noHierarchyLevels = noHierarchyLevels;
+    for (int i = 0; i < noHierarchyLevels && i < 8; ++i) cfg.trackingRegime[i] = trackingRegime[i];
+    check(itm_colour_tracker_create(&tracker), "itm_colour_tracker_create");
+  }
+  ~ITMColorTracker_HIP() { itm_colour_tracker_destroy(tracker); }
+  ITMColorTracker_HIP(const ITMColorTracker_HIP&) = delete;
+  ITMColorTracker_HIP& operator=(const ITMColorTracker_HIP&) = delete;
+  void TrackCamera(ITMTrackingState* trackingState, const ITMView* view, const ITMRenderState* renderState) {
+    itm_view v = make_view(view, trackingState);
+    float M[16];
+    check(itm_colour_tracker_track_camera(tracker, &cfg, &v, renderState->handle, trackingState->pointCloud_locations,
+                                          trackingState->pointCloud_colours, 0, M, stream), "TrackCamera");
+    trackingState->pose_d.SetM(M);
+  }
+};
+// adapter: ITMColorTracker_HIP behind the ITMTracker interface, with the render state that holds the point count
+class ITMColorTrackerAdapter : public ITMTracker {
+  ITMColorTracker_HIP* t;
+  const ITMRenderState* renderState;
+ public:
+  ITMColorTrackerAdapter(ITMColorTracker_HIP* t_, const ITMRenderState* rs) : t(t_), renderState(rs) {}
+  void TrackCamera(ITMTrackingState* ts, const ITMView* view) override { t->TrackCamera(ts, view, renderState); }
+};
+
 // 4x4 product as ORUtils/Matrix.h:96-104 forms it (column-major, r(x, y) accumulated from zero over k)
 inline void matmul4(const float* lhs, const float* rhs, float* out) {
   for (int x = 0; x < 4; ++x) for (int y = 0; y < 4; ++y) {
@@ -476,6 +513,7 @@ class ITMMainEngine_HIP {
   ITMDenseMapper_HIP<TVoxel, TIndex> denseMapper;
   ITMVisualisationEngine_HIP<TVoxel, TIndex> visualisationEngine;
   ITMDepthTracker_HIP* depthTracker = nullptr;
+  ITMColorTracker_HIP* colourTracker = nullptr;
   ITMTracker* tracker = nullptr;
   ITMTrackingController_HIP<TVoxel, TIndex>* trackingController = nullptr;
   ITMViewBuilder_HIP* viewBuilder = nullptr;
@@ -489,7 +527,7 @@ class ITMMainEngine_HIP {
   // calibType / c0 / c1: ITMDisparityCalib (0 = TRAFO_KINECT, 1 = TRAFO_AFFINE); sizes as ITMMainEngine's imgSize_rgb / imgSize_d
   ITMMainEngine_HIP(const ITMLibSettings& settings_, const ITMSceneParams& params, const ITMRGBDCalib& calib, Vector2i imgSize_rgb, Vector2i imgSize_d,
                     int calibType = 1, float c0 = 0.001f, float c1 = 0.0f, int localBlockNum = 0)
-      : settings(settings_), sceneParams(params), scene(&sceneParams, localBlockNum), visualisationEngine(&scene) {
+      : settings((check_settings(settings_), settings_)), sceneParams(params), scene(&sceneParams, localBlockNum), visualisationEngine(&scene) {
     view.calib = calib;
     view.depthSize = imgSize_d; view.rgbSize = imgSize_rgb;
     const size_t P = (size_t)imgSize_d.x * imgSize_d.y;
@@ -502,22 +540,31 @@ class ITMMainEngine_HIP {
     trackingState.pointCloud_locations = (float*)pointsBuf; trackingState.pointCloud_colours = (float*)coloursBuf;
     denseMapper.ResetScene(&scene);
     viewBuilder = new ITMViewBuilder_HIP(&view.calib, calibType, c0, c1);
+    renderState_live = visualisationEngine.CreateRenderState(tracked);
     if (settings.trackerType == ITMLibSettings::TRACKER_ICP) {
       depthTracker = new ITMDepthTracker_HIP(settings.trackingRegime, settings.noHierarchyLevels, settings.noICPRunTillLevel,
                                              settings.depthTrackerICPThreshold, settings.depthTrackerTerminationThreshold);
       tracker = new ITMDepthTrackerAdapter(depthTracker);
+    } else if (settings.trackerType == ITMLibSettings::TRACKER_COLOR && settings.useColourTracker) {
+      colourTracker = new ITMColorTracker_HIP(settings.trackingRegime, settings.noHierarchyLevels);
+      tracker = new ITMColorTrackerAdapter(colourTracker, renderState_live);
     } else {
-      tracker = new ITMExternalTracker();          // TRACKER_EXTERNAL, and TRACKER_COLOR with poses from outside (the colour tracker itself is not part of the path)
+      tracker = new ITMExternalTracker();          // TRACKER_EXTERNAL, and TRACKER_COLOR with poses from outside (useColourTracker = false)
     }
     trackingController = new ITMTrackingController_HIP<TVoxel, TIndex>(tracker, &visualisationEngine, &settings);
-    renderState_live = visualisationEngine.CreateRenderState(tracked);
   }
   ~ITMMainEngine_HIP() {
-    delete renderState_live; delete trackingController; delete tracker; delete depthTracker; delete viewBuilder;
+    delete renderState_live; delete trackingController; delete tracker; delete depthTracker; delete colourTracker; delete viewBuilder;
     for (void* p : {depthBuf, scratchBuf, normalBuf, sigmaBuf, pointsBuf, coloursBuf}) itm_dev_free(p);
   }
   ITMMainEngine_HIP(const ITMMainEngine_HIP&) = delete;
   ITMMainEngine_HIP& operator=(const ITMMainEngine_HIP&) = delete;
+
+  // ITMLibSettings.cpp:81: the colour tracker needs a voxel type with colour information
+  static void check_settings(const ITMLibSettings& st) {
+    if (st.trackerType == ITMLibSettings::TRACKER_COLOR && st.useColourTracker && TVoxel::kType != ITM_VOXEL_S_RGB && TVoxel::kType != ITM_VOXEL_F_RGB)
+      throw std::runtime_error("Color tracker requires a voxel type with color information");
+  }
 
   ITMView* GetView() { return &view; }
   ITMTrackingState* GetTrackingState() { return &trackingState; }

@@ -105,6 +105,12 @@ class TrackerGH(C.Structure):
     _fields_ = [("f", C.c_float), ("nabla", C.c_float * 6), ("hessian", C.c_float * 36), ("noValidPoints", C.c_int32)]
 
 
+class ColourEval(C.Structure):
+    """itm_colour_eval: F_oneLevel / G_oneLevel of the colour tracker (hessian[para + col * numPara])."""
+    _fields_ = [("f", C.c_float), ("noValidPoints", C.c_int32), ("numPara", C.c_int32), ("nabla", C.c_float * 6),
+                ("hessian", C.c_float * 36)]
+
+
 class Counters(C.Structure):
     _fields_ = [("lastFreeBlockId", C.c_int32), ("lastFreeExcessListId", C.c_int32),
                 ("noVisibleEntries", C.c_int32), ("noFwdProjMissingPoints", C.c_int32),
@@ -264,6 +270,15 @@ _HOST_IO_SIGS = {
     "exchange_acquire": (C.c_int, [_P, _P, C.POINTER(_P), C.POINTER(C.c_longlong)]),
     "exchange_release": (C.c_int, [_P, _P]),
     "debug_checksum": (C.c_int, [_P, C.c_size_t, C.c_int, _P, _P]),
+    # colour tracker handles (product only)
+    "colour_tracker_create": (C.c_int, [C.POINTER(_P)]),
+    "colour_tracker_destroy": (C.c_int, [_P]),
+    "colour_tracker_prepare": (C.c_int, [_P, C.POINTER(ViewStruct), C.c_int, _P]),
+    "colour_tracker_read_level": (C.c_int, [_P, C.c_int, _P, _P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), _P]),
+    "colour_tracker_evaluate": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(ColourEval), _P]),
+    "colour_tracker_track_camera": (C.c_int, [_P, C.POINTER(TrackerConfig), C.POINTER(ViewStruct), _P, _P, _P, C.c_int,
+                                              C.POINTER(C.c_float), _P]),
+    "colour_tracker_evaluations": (C.c_int, [_P, C.POINTER(C.c_int)]),
 }
 
 

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "itm_internal.h"
+#include "gh_reduce.h"
 #include "icp_solver.h"
 #include "se3.h"
 #include "wave_utils.h"
@@ -91,37 +92,6 @@ struct GHParams {
   int tileH;                  // rows of a tile (gh_tiling)
 };
 
-constexpr int kGHValues = 1 + 6 + 21;   // f, nabla, packed lower-triangular hessian
-
-// Everything the tracker hands between host and device (and between workgroups) travels as TAGGED GRANULES: 8 aligned bytes = 4 bytes
-// of payload + the 4-byte sequence number of the evaluation they belong to.  An aligned 8-byte store is indivisible for the device,
-// across PCIe and for the host, so a reader that finds the expected number in a granule holds that granule's payload: no stamp
-// written after the values, and therefore no wait for the values to have left before the stamp may follow (one PCIe or memory
-// round trip per hand-off, 1.5-2 us each, measured).
-constexpr int kRecordWords = 2 * kGHValues + 1;   // 28 doubles as two words each, then the count
-struct GHBlockRecord { unsigned long long g[64]; };   // one per workgroup (pinned host memory) and the session's result; granule i = tag << 32 | word i
-static_assert(kRecordWords <= 64, "record granules");
-__host__ __device__ inline unsigned int next_seq(unsigned int s) { ++s; return (s == 0u || s == 0xffffffffu) ? 1u : s; }   // 0 and ~0 are never sequence numbers
-
-// ORDER OF THE ADDITIONS over the workgroups' records, the same wherever they are added (host: per-launch path and coarse levels
-// of a session; device: the gathering workgroup of a session), so that every path yields the same bits: records in segments of
-// kSegBlocks consecutive workgroups, each segment added up in block order, then the kSegs segment sums in segment order (an
-// empty segment contributes +0.0).  A single chain over 240 records was 2.5 us of dependent additions in the gathering workgroup.
-constexpr int kSegBlocks = 32;
-
-// thread i < kGHValues holds value i of the workgroup (`mine`); every thread holds `cnt`.  Lane i of the first wave stores granule i:
-// one store instruction over 512 contiguous bytes, which leaves the CU as whole 64-byte lines (granules written two per lane,
-// 16 bytes apart, crossed PCIe one by one and cost the host's memory a partial-line update each: 7 us per record, measured)
-template <int SCOPE>
-__device__ inline void send_record(GHBlockRecord* r, double mine, int cnt, unsigned int tag) {
-  if (threadIdx.x >= 64) return;
-  const int i = threadIdx.x;
-  const unsigned long long bits = (unsigned long long)__double_as_longlong(__shfl(mine, i >> 1, 64));
-  unsigned int w = (i & 1) ? (unsigned int)(bits >> 32) : (unsigned int)bits;
-  if (i == 2 * kGHValues) w = (unsigned int)cnt;
-  if (i > 2 * kGHValues) w = 0u;
-  __hip_atomic_store(&r->g[i], ((unsigned long long)tag << 32) | w, __ATOMIC_RELAXED, SCOPE);
-}
 
 #ifndef ITM_EXP_TRACKER_TRACE
 #define ITM_EXP_TRACKER_TRACE 0   // measurement build: per-evaluation host-side latencies on stderr
@@ -151,11 +121,6 @@ __device__ inline bool bilinear_holes(const float4* __restrict__ src, float px, 
 // registers (double), so a call delivers at most kGHGroups records to the host whatever the image size -- with one record per
 // tile, the 1 200 records (288 KB over PCIe, two system fences per workgroup) of a 640x480 level cost 113 us per evaluation
 // against 20 us for the 40x30 level (tools/tracker_bench.py).
-constexpr int kGHGroups = 256;
-constexpr int kSegs = (kGHGroups + kSegBlocks - 1) / kSegBlocks;
-constexpr int kGHWaves = 4;      // waves per workgroup (measured per 640x480 evaluation: 4 waves 43 us, 8 waves 51 us, 16 waves 73 us)
-static_assert(kSegBlocks % kGHWaves == 0, "a gathering workgroup splits its segment evenly over its waves");
-constexpr int kGHThreads = 64 * kGHWaves;
 constexpr int kGHTileH = kGHThreads / 16;      // a tile is 16 pixels wide and at most kGHTileH tall
 // Tiling of a w x h level: full tiles (one pixel per thread) where there are many; on the coarse levels, where a full tiling
 // would occupy a handful of compute units and each would push its four waves' divergent map taps through one texture path,
@@ -272,53 +237,6 @@ __device__ inline void gh_accumulate(const float* __restrict__ depth, const floa
   }
 }
 
-// Sum of `s` over the 64 lanes of the wave, the same value in every lane: an inclusive scan inside each row of 16 lanes with DPP
-// row shifts (lanes that would read from outside their row add 0), then the four row totals in row order.  Data-parallel
-// primitives keep the exchange in the ALU; the ds_bpermute butterfly this replaces was one LDS round trip per step and value
-// (2.7 us per evaluation for the block reduction, measured).  The order of the additions is fixed: deterministic sums.
-template <int CTRL>
-__device__ inline double dpp_shifted(double v) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)(unsigned int)b, CTRL, 0xf, 0xf, true);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(unsigned int)(b >> 32), CTRL, 0xf, 0xf, true);
-  return __longlong_as_double((long long)(((unsigned long long)(unsigned int)hi << 32) | (unsigned int)lo));
-}
-__device__ inline double lane_value(double v, int lane) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-  const unsigned int lo = (unsigned int)__builtin_amdgcn_readlane((int)(unsigned int)b, lane), hi = (unsigned int)__builtin_amdgcn_readlane((int)(unsigned int)(b >> 32), lane);
-  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-__device__ inline double wave_sum(double s) {
-  s += dpp_shifted<0x111>(s);   // row_shr:1
-  s += dpp_shifted<0x112>(s);   // row_shr:2
-  s += dpp_shifted<0x114>(s);   // row_shr:4
-  s += dpp_shifted<0x118>(s);   // row_shr:8  -> lane 15 of every row holds the row's sum
-  return ((lane_value(s, 15) + lane_value(s, 31)) + lane_value(s, 47)) + lane_value(s, 63);
-}
-
-// wave sums in double (fixed order), then the waves in order: thread i < kGHValues ends up with value i of the workgroup, every
-// thread with its count
-template <int MODE>
-__device__ inline void gh_block_reduce(const double acc[kGHValues], int valid, double (*lds)[kGHValues], int* ldsCount, double& mine, int& cnt) {
-  constexpr int NP = (MODE == 3) ? 6 : 3;
-  constexpr int NH = NP * (NP + 1) / 2;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < kGHValues; ++i) {
-    const bool used = (i == 0) || (i >= 1 && i < 1 + NP) || (i >= 7 && i < 7 + NH);
-    const double s = used ? wave_sum(acc[i]) : 0.0;
-    if (lane == 0) lds[wave][i] = s;
-  }
-  const int total = wave_reduce_sum(valid);
-  if (lane == 0) ldsCount[wave] = total;
-  __syncthreads();
-  mine = 0.0; cnt = 0;
-#pragma unroll
-  for (int wv = 0; wv < kGHWaves; ++wv) {          // fixed order: deterministic
-    if (threadIdx.x < kGHValues) mine += lds[wv][threadIdx.x];
-    cnt += ldsCount[wv];
-  }
-}
 
 template <int MODE>
 __global__ void __launch_bounds__(kGHThreads) gh_partial_kernel(const float* __restrict__ depth, const float4* __restrict__ pointsMap,
@@ -602,46 +520,6 @@ static itm_tracker* thread_tracker() {
   return mine;
 }
 
-// Adds one tagged record to `sums` / `count` once every granule carries `tag`.  `slow(granule)` is called every 1024 polls of a
-// granule that has not arrived and decides whether the wait goes on (ITM_OK) or ends with an error code.
-// the common order of the additions (kSegBlocks above) on the host
-struct OrderedSums {
-  double seg[kSegs][kGHValues];
-  OrderedSums() { for (int g = 0; g < kSegs; ++g) for (int i = 0; i < kGHValues; ++i) seg[g][i] = 0.0; }
-  double* of_block(size_t b) { return seg[b / kSegBlocks]; }
-  void total(double out[kGHValues]) const {
-    for (int i = 0; i < kGHValues; ++i) {
-      double s = 0.0;
-      for (int g = 0; g < kSegs; ++g) s += seg[g][i];
-      out[i] = s;
-    }
-  }
-};
-
-template <class Slow>
-static inline int read_record(const GHBlockRecord* r, unsigned int tag, double* sums, int* count, Slow&& slow) {
-  unsigned int w[kRecordWords];
-  for (int i = 0; i < kRecordWords; ++i) {
-    const volatile unsigned long long* g = &r->g[i];
-    unsigned long long v;
-    unsigned spins = 0;
-    while ((unsigned int)((v = *g) >> 32) != tag) {
-      __builtin_ia32_pause();
-      if ((++spins & 0x3ffu) != 0u) continue;
-      const int rc = slow(g);
-      if (rc) return rc;
-    }
-    w[i] = (unsigned int)v;
-  }
-  for (int i = 0; i < kGHValues; ++i) {
-    const unsigned long long bits = (unsigned long long)w[2 * i] | ((unsigned long long)w[2 * i + 1] << 32);
-    double d;
-    memcpy(&d, &bits, 8);
-    sums[i] += d;
-  }
-  *count += (int)w[2 * kGHValues];
-  return ITM_OK;
-}
 
 static int compute_g_and_h(itm_tracker* trk, const float* depth, int w, int h, const float* viewIntr, const float* pointsMap, const float* normalsMap,
                            int sceneW, int sceneH, const float* sceneIntr, const float* approxInvPose, const float* scenePose,
@@ -668,32 +546,11 @@ static int compute_g_and_h(itm_tracker* trk, const float* depth, int w, int h, c
   else if (iterationType == 2) gh_partial_kernel<2><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, trk->recDev, seq);
   else gh_partial_kernel<3><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, trk->recDev, seq);
   ITM_LAUNCH_CHECK();
-  // Wait for every workgroup's tagged record and add them in block order (fixed order => deterministic, in double).  The
-  // poll is bounded in TIME: after 20 ms without a granule the stream is queried between polls -- a drained stream without
-  // it, a device error, or pollTimeoutSeconds without progress end the call with ITM_ERR_DEVICE instead of stalling the
-  // host on a kernel that will never finish.
-  OrderedSums ordered;
-  int n = 0;
-  using clock = std::chrono::steady_clock;
-  clock::time_point t0; bool timing = false;
-  for (size_t b = 0; b < blocks; ++b) {
-    rc = read_record(trk->rec + b, seq, ordered.of_block(b), &n, [&](const volatile unsigned long long* g) -> int {
-      if (!timing) { t0 = clock::now(); timing = true; return ITM_OK; }
-      const double waited = std::chrono::duration<double>(clock::now() - t0).count();
-      if (waited < 0.02) return ITM_OK;
-      const hipError_t q = hipStreamQuery(st);
-      if (q == hipSuccess) {
-        if ((unsigned int)(*g >> 32) == seq) return ITM_OK;
-        return set_error(ITM_ERR_DEVICE, "tracker reduction: the stream drained without delivering every record");
-      }
-      if (q != hipErrorNotReady) return hip_fail(q, "tracker reduction", __FILE__, __LINE__);
-      if (waited > trk->pollTimeoutSeconds) return set_error(ITM_ERR_DEVICE, "tracker reduction timed out");
-      return ITM_OK;
-    });
-    if (rc) return rc;
-  }
+  // Wait for every workgroup's tagged record and add them in block order (fixed order => deterministic, in double; bounded wait)
   double sums[kGHValues];
-  ordered.total(sums);
+  int n = 0;
+  rc = collect_records(trk->rec, blocks, seq, st, trk->pollTimeoutSeconds, sums, &n);
+  if (rc) return rc;
   for (int r = 0, k = 0; r < np; ++r)
     for (int c = 0; c <= r; ++c, ++k) out->hessian[r + c * 6] = (float)sums[7 + k];
   for (int r = 0; r < np; ++r)

@@ -114,5 +114,57 @@ def rgb_frame(w, h) -> np.ndarray:
     return img
 
 
+# ---- textured scene for the colour tracker --------------------------------------------------------------------------------
+# Colour is a smooth function of the WORLD point (low-frequency sinusoids per channel), so it moves with the camera and has
+# usable image gradients on every pyramid level.
+
+def texture(X: np.ndarray) -> np.ndarray:
+    """uchar RGB of world points X[..., 3] (metres)."""
+    x, y, z = X[..., 0].astype(np.float64), X[..., 1].astype(np.float64), X[..., 2].astype(np.float64)
+    r = 128.0 + 100.0 * np.sin(9.0 * x + 3.0 * y + 1.0)
+    g = 128.0 + 100.0 * np.sin(8.0 * y - 4.0 * x + 5.0 * z + 2.0)
+    b = 128.0 + 100.0 * np.sin(6.0 * x + 6.0 * y + 7.0 * z + 4.0)
+    return np.stack([r, g, b], -1).round().astype(np.uint8)
+
+
+def surface_points(w: int, h: int, M: np.ndarray, intr=None) -> np.ndarray:
+    """World points (float64, [h, w, 3]) seen through pixel centres of a camera with world->camera pose M (column-major 16)
+    and intrinsics intr: the sphere of depth_z, else the wall z = 2.5 m."""
+    fx, fy, cx, cy = [float(v) for v in (intr or intrinsics_for(w, h))]
+    Mw = np.asarray(M, np.float64).reshape(4, 4).T             # row-major world->camera
+    R, t = Mw[:3, :3], Mw[:3, 3]
+    c = -R.T @ t                                                # camera centre in the world
+    xs, ys = np.meshgrid(np.arange(w, dtype=np.float64), np.arange(h, dtype=np.float64))
+    d = np.stack([(xs - cx) / fx, (ys - cy) / fy, np.ones_like(xs)], -1) @ R   # ray directions in the world (R^T d_cam)
+    o = c - np.array([0.0, 0.0, 1.5])
+    A = (d * d).sum(-1)
+    B = 2.0 * (d @ o)
+    Cq = o @ o - 0.25
+    disc = B * B - 4.0 * A * Cq
+    tau = (-B - np.sqrt(np.maximum(disc, 0.0))) / (2.0 * A)
+    wall = (2.5 - c[2]) / d[..., 2]
+    tau = np.where((disc > 0) & (tau > 0), tau, wall)
+    return c + tau[..., None] * d
+
+
+def textured_rgb_frame(w: int, h: int, M: np.ndarray, intr=None) -> np.ndarray:
+    """uchar4 [h, w, 4] image of the textured sphere + wall scene from world->camera pose M; alpha 255 on the surface."""
+    img = np.empty((h, w, 4), np.uint8)
+    img[..., :3] = texture(surface_points(w, h, M, intr))
+    img[..., 3] = 255
+    return img
+
+
+def textured_point_cloud(w: int, h: int, M: np.ndarray, intr=None, step: int = 1):
+    """What CreatePointCloud leaves for the textured scene seen from M: locations (x, y, z, 1) and colours (rgb / 255, 1) as
+    float32 [n, 4], every `step`-th pixel in x and y."""
+    X = surface_points(w, h, M, intr)[::step, ::step].reshape(-1, 3)
+    loc = np.ones((X.shape[0], 4), F)
+    loc[:, :3] = X.astype(F)
+    col = np.ones((X.shape[0], 4), F)
+    col[:, :3] = texture(X).astype(F) / F(255.0)
+    return np.ascontiguousarray(loc), np.ascontiguousarray(col)
+
+
 def sha256(arr: np.ndarray) -> str:
     return hashlib.sha256(np.ascontiguousarray(arr).tobytes()).hexdigest()
