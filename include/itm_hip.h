@@ -480,6 +480,39 @@ int ITM_FN(colour_tracker_track_camera)(itm_colour_tracker* tracker, const itm_t
 /* Evaluations (each one pass over the point cloud) of the last colour_tracker_track_camera call on this handle. */
 int ITM_FN(colour_tracker_evaluations)(const itm_colour_tracker* tracker, int* out);
 
+/* ---- Ren SDF tracker ----------------------------------------------------------------------------------------------
+ * Registers the depth image of a view directly against the fused TSDF volume of a scene (any voxel type, hash or dense index).
+ * Device-specific half: DeviceSpecific/CPU/ITMRenTracker_CPU.cpp (UnprojectDepthToCam, F_oneLevel, G_oneLevel) with
+ * DeviceAgnostic/ITMRenTracker.h; host loop: ITMRenTracker::TrackCamera (Engine/ITMRenTracker.cpp).  One handle owns the point
+ * image and the reduction buffers of ONE tracker; calls on a handle are serialised by the handle.  Sums are added in the
+ * fixed-order double-precision tree of the ICP tracker: deterministic, within float rounding of the reference's sequential float
+ * sums, the valid count exact.  The scene is read as the calls before left it: engine calls the library recorded but has not
+ * launched yet (itm_scene_set_deferred_fusion) are launched first. */
+typedef struct itm_ren_tracker itm_ren_tracker;
+typedef struct itm_ren_eval {
+  float f;                 /* F_oneLevel: minus the sum over points (w > -1) of 4 e / (e + 1)^2, e = exp(-6 dt); dt == 1 adds 0   */
+  int32_t noValidPoints;   /* G_oneLevel: points with a Jacobian (sdf found and != 1 at the point and its six axis neighbours)     */
+  float nabla[6];          /* G_oneLevel gradient: minus the sum of the Jacobians (translation, then MRP rotation)               */
+  float hessian[36];       /* G_oneLevel hessian, hessian[r + c * 6] (symmetric); nabla / hessian / count zero unless asked for    */
+} itm_ren_eval;
+/* ITMRenTracker constructor / destructor (Engine/ITMRenTracker.cpp) */
+int ITM_FN(ren_tracker_create)(itm_ren_tracker** out);
+int ITM_FN(ren_tracker_destroy)(itm_ren_tracker* tracker);
+/* PrepareForEvaluation, level 0 (Engine/ITMRenTracker.cpp): UnprojectDepthToCam of view->depth (w x h) with view->intr_d --
+ * Vector4f (x z / fx - cx z / fx, y z / fy - cy z / fy, z, 1), (0, 0, 0, -1) where depth <= 0.  The coarser level the reference
+ * builds is never read and is not built.  points_host (may be NULL): Vector4f[h*w] copied back synchronously. */
+int ITM_FN(ren_tracker_prepare)(itm_ren_tracker* tracker, const itm_view* view, float* points_host, itm_stream stream);
+/* ITMRenTracker_CPU::F_oneLevel (and G_oneLevel at the same pose when wantG != 0, from the same pass) on the prepared points at
+ * the camera -> world matrix invM (column-major), voxels read nearest-neighbour at ROUND(invM p / voxelSize).  Synchronises
+ * `stream`. */
+int ITM_FN(ren_tracker_evaluate)(itm_ren_tracker* tracker, const itm_scene* scene, const float invM[16], int wantG,
+                                 itm_ren_eval* out, itm_stream stream);
+/* ITMRenTracker::TrackCamera: prepares the points from view->depth, runs the Levenberg-Marquardt loop from view->M_d (level 0 only;
+ * the tracking regime is not used, as in the reference), writes the refined and coerced pose_d to M_d_out.  evaluations (may be
+ * NULL): passes over the points the call made (each one energy + gradient + Hessian).  Synchronises `stream`. */
+int ITM_FN(ren_tracker_track_camera)(itm_ren_tracker* tracker, const itm_scene* scene, const itm_view* view, float M_d_out[16],
+                                     int* evaluations, itm_stream stream);
+
 /* ---- state access ------------------------------------------------------------------------- */
 /* Blocks until `stream` has drained, then reads the device-side counters. */
 int ITM_FN(get_counters)(const itm_scene* scene, const itm_render_state* rs, itm_counters* out,

@@ -100,7 +100,7 @@ struct ITMTrackingState {
 
 // ITMLibSettings (Utils/ITMLibSettings.h / .cpp:9-90): the members the path's callers read, with the reference's defaults
 struct ITMLibSettings {
-  enum TrackerType { TRACKER_COLOR, TRACKER_ICP, TRACKER_EXTERNAL };
+  enum TrackerType { TRACKER_COLOR, TRACKER_ICP, TRACKER_EXTERNAL, TRACKER_REN };   // TRACKER_REN appended: the others keep their values
   ITMSceneParamsDefaults sceneParamsDefaults;   // (0.02, 100, 0.005, 0.35, 3.0, false), ITMLibSettings.cpp:10
   float depthTrackerICPThreshold = 0.1f * 0.1f;
   float depthTrackerTerminationThreshold = 1e-3f;
@@ -450,6 +450,38 @@ class ITMColorTrackerAdapter : public ITMTracker {
   void TrackCamera(ITMTrackingState* ts, const ITMView* view) override { t->TrackCamera(ts, view, renderState); }
 };
 
+// ITMRenTracker (Engine/ITMRenTracker.h, .cpp; ITMTrackerFactory::MakeRenTracker): TrackCamera registers the view's depth image
+// directly against the scene's TSDF, level 0 only; unprojection, evaluation and reduction on the GPU (itm_ren_tracker_*).  Reads the
+// scene as the last frame left it (engine calls the library recorded are launched first).
+template <class TVoxel, class TIndex>
+class ITMRenTracker_HIP {
+  const ITMScene<TVoxel, TIndex>* scene;
+  itm_ren_tracker* tracker = nullptr;      // this object's point image + reduction buffers; one per tracker object
+
+ public:
+  itm_stream stream = nullptr;
+  explicit ITMRenTracker_HIP(const ITMScene<TVoxel, TIndex>* scene_) : scene(scene_) {
+    check(itm_ren_tracker_create(&tracker), "itm_ren_tracker_create");
+  }
+  ~ITMRenTracker_HIP() { itm_ren_tracker_destroy(tracker); }
+  ITMRenTracker_HIP(const ITMRenTracker_HIP&) = delete;
+  ITMRenTracker_HIP& operator=(const ITMRenTracker_HIP&) = delete;
+  void TrackCamera(ITMTrackingState* trackingState, const ITMView* view) {
+    itm_view v = make_view(view, trackingState);
+    float M[16];
+    check(itm_ren_tracker_track_camera(tracker, scene->handle, &v, M, nullptr, stream), "TrackCamera");
+    trackingState->pose_d.SetM(M);
+  }
+};
+// adapter: ITMRenTracker_HIP behind the ITMTracker interface
+template <class TVoxel, class TIndex>
+class ITMRenTrackerAdapter : public ITMTracker {
+  ITMRenTracker_HIP<TVoxel, TIndex>* t;
+ public:
+  explicit ITMRenTrackerAdapter(ITMRenTracker_HIP<TVoxel, TIndex>* t_) : t(t_) {}
+  void TrackCamera(ITMTrackingState* ts, const ITMView* view) override { t->TrackCamera(ts, view); }
+};
+
 // 4x4 product as ORUtils/Matrix.h:96-104 forms it (column-major, r(x, y) accumulated from zero over k)
 inline void matmul4(const float* lhs, const float* rhs, float* out) {
   for (int x = 0; x < 4; ++x) for (int y = 0; y < 4; ++y) {
@@ -514,6 +546,7 @@ class ITMMainEngine_HIP {
   ITMVisualisationEngine_HIP<TVoxel, TIndex> visualisationEngine;
   ITMDepthTracker_HIP* depthTracker = nullptr;
   ITMColorTracker_HIP* colourTracker = nullptr;
+  ITMRenTracker_HIP<TVoxel, TIndex>* renTracker = nullptr;
   ITMTracker* tracker = nullptr;
   ITMTrackingController_HIP<TVoxel, TIndex>* trackingController = nullptr;
   ITMViewBuilder_HIP* viewBuilder = nullptr;
@@ -548,13 +581,16 @@ class ITMMainEngine_HIP {
     } else if (settings.trackerType == ITMLibSettings::TRACKER_COLOR && settings.useColourTracker) {
       colourTracker = new ITMColorTracker_HIP(settings.trackingRegime, settings.noHierarchyLevels);
       tracker = new ITMColorTrackerAdapter(colourTracker, renderState_live);
+    } else if (settings.trackerType == ITMLibSettings::TRACKER_REN) {
+      renTracker = new ITMRenTracker_HIP<TVoxel, TIndex>(&scene);     // MakeRenTracker: the Ren tracker alone, not a composite with ICP
+      tracker = new ITMRenTrackerAdapter<TVoxel, TIndex>(renTracker);
     } else {
       tracker = new ITMExternalTracker();          // TRACKER_EXTERNAL, and TRACKER_COLOR with poses from outside (useColourTracker = false)
     }
     trackingController = new ITMTrackingController_HIP<TVoxel, TIndex>(tracker, &visualisationEngine, &settings);
   }
   ~ITMMainEngine_HIP() {
-    delete renderState_live; delete trackingController; delete tracker; delete depthTracker; delete colourTracker; delete viewBuilder;
+    delete renderState_live; delete trackingController; delete tracker; delete depthTracker; delete colourTracker; delete renTracker; delete viewBuilder;
     for (void* p : {depthBuf, scratchBuf, normalBuf, sigmaBuf, pointsBuf, coloursBuf}) itm_dev_free(p);
   }
   ITMMainEngine_HIP(const ITMMainEngine_HIP&) = delete;

@@ -111,6 +111,11 @@ class ColourEval(C.Structure):
                 ("hessian", C.c_float * 36)]
 
 
+class RenEval(C.Structure):
+    """itm_ren_eval: F_oneLevel / G_oneLevel of the Ren SDF tracker (hessian[r + c * 6])."""
+    _fields_ = [("f", C.c_float), ("noValidPoints", C.c_int32), ("nabla", C.c_float * 6), ("hessian", C.c_float * 36)]
+
+
 class Counters(C.Structure):
     _fields_ = [("lastFreeBlockId", C.c_int32), ("lastFreeExcessListId", C.c_int32),
                 ("noVisibleEntries", C.c_int32), ("noFwdProjMissingPoints", C.c_int32),
@@ -279,6 +284,12 @@ _HOST_IO_SIGS = {
     "colour_tracker_track_camera": (C.c_int, [_P, C.POINTER(TrackerConfig), C.POINTER(ViewStruct), _P, _P, _P, C.c_int,
                                               C.POINTER(C.c_float), _P]),
     "colour_tracker_evaluations": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    # Ren SDF tracker handles (product only)
+    "ren_tracker_create": (C.c_int, [C.POINTER(_P)]),
+    "ren_tracker_destroy": (C.c_int, [_P]),
+    "ren_tracker_prepare": (C.c_int, [_P, C.POINTER(ViewStruct), _P, _P]),
+    "ren_tracker_evaluate": (C.c_int, [_P, _P, C.POINTER(C.c_float), C.c_int, C.POINTER(RenEval), _P]),
+    "ren_tracker_track_camera": (C.c_int, [_P, _P, C.POINTER(ViewStruct), C.POINTER(C.c_float), C.POINTER(C.c_int), _P]),
 }
 
 
