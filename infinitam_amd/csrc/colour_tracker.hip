@@ -192,35 +192,30 @@ __global__ void __launch_bounds__(kGHThreads) colour_eval_kernel(const float4* _
 
 struct itm_colour_tracker {
   mutable std::mutex mu;
-  int device = -1;
-  itm::GHBlockRecord* rec = nullptr; itm::GHBlockRecord* recDev = nullptr;   // pinned host records + their device address
-  unsigned int seq = 0;
+  itm::GHChannel ch;
   void* pyramidMem = nullptr; size_t pyramidBytes = 0;
   itm::ColourPyramid P = {};
   float intr[4] = {0, 0, 0, 0};    // intr_rgb of the last prepare
   int* totalHost = nullptr;        // pinned: noTotalPoints copied from the render state (track_camera)
-  double pollTimeoutSeconds = 5.0;
   int evaluations = 0;
 };
 
 namespace itm {
 
 static void colour_release(itm_colour_tracker* t) {
-  if (t->rec) (void)hipHostFree(t->rec);
+  t->ch.release();
   if (t->totalHost) (void)hipHostFree(t->totalHost);
   (void)hipFree(t->pyramidMem);
-  t->rec = nullptr; t->recDev = nullptr; t->totalHost = nullptr; t->pyramidMem = nullptr; t->pyramidBytes = 0;
+  t->totalHost = nullptr; t->pyramidMem = nullptr; t->pyramidBytes = 0;
   t->P = ColourPyramid{};
 }
 
 static int colour_reserve(itm_colour_tracker* t, size_t pyramidBytes) {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (t->device != dev) { colour_release(t); t->device = dev; }
-  if (!t->rec) {
-    hipError_t e = hipHostMalloc((void**)&t->rec, kGHGroups * sizeof(GHBlockRecord), hipHostMallocMapped | hipHostMallocCoherent);
-    if (e == hipSuccess) { memset(t->rec, 0, kGHGroups * sizeof(GHBlockRecord)); e = hipHostGetDevicePointer((void**)&t->recDev, t->rec, 0); }
-    if (e == hipSuccess) e = hipHostMalloc((void**)&t->totalHost, sizeof(int), hipHostMallocMapped | hipHostMallocCoherent);
+  if (t->ch.moved()) colour_release(t);
+  int rc = t->ch.reserve(kGHGroups);
+  if (rc) return rc;
+  if (!t->totalHost) {
+    const hipError_t e = hipHostMalloc((void**)&t->totalHost, sizeof(int), hipHostMallocMapped | hipHostMallocCoherent);
     if (e != hipSuccess) { colour_release(t); return hip_fail(e, "colour tracker buffers", __FILE__, __LINE__); }
   }
   if (t->pyramidBytes < pyramidBytes) {
@@ -288,19 +283,19 @@ static int colour_evaluate(itm_colour_tracker* t, int level, const float* locati
   p.countDev = countDev; p.countHost = countHost;
   const int np = colour_num_para(mode);
   const float4* loc = (const float4*)locations; const float4* col = (const float4*)colours;
-  const unsigned int seq = t->seq = next_seq(t->seq);
+  const unsigned int seq = t->ch.begin();
   const dim3 grid(kGHGroups);
   if (np == 3) {
-    if (gh) colour_eval_kernel<3, true><<<grid, kGHThreads, 0, st>>>(loc, col, p, t->recDev, seq);
-    else colour_eval_kernel<3, false><<<grid, kGHThreads, 0, st>>>(loc, col, p, t->recDev, seq);
+    if (gh) colour_eval_kernel<3, true><<<grid, kGHThreads, 0, st>>>(loc, col, p, t->ch.recDev, seq);
+    else colour_eval_kernel<3, false><<<grid, kGHThreads, 0, st>>>(loc, col, p, t->ch.recDev, seq);
   } else {
-    if (gh) colour_eval_kernel<6, true><<<grid, kGHThreads, 0, st>>>(loc, col, p, t->recDev, seq);
-    else colour_eval_kernel<6, false><<<grid, kGHThreads, 0, st>>>(loc, col, p, t->recDev, seq);
+    if (gh) colour_eval_kernel<6, true><<<grid, kGHThreads, 0, st>>>(loc, col, p, t->ch.recDev, seq);
+    else colour_eval_kernel<6, false><<<grid, kGHThreads, 0, st>>>(loc, col, p, t->ch.recDev, seq);
   }
   ITM_LAUNCH_CHECK();
   double sums[kGHValues];
   int valid = 0;
-  const int rc = collect_records(t->rec, kGHGroups, seq, st, t->pollTimeoutSeconds, sums, &valid);
+  const int rc = t->ch.collect(kGHGroups, seq, st, sums, &valid);
   if (rc) return rc;
   // the launch has finished (its records are in): the count it read is in place as well
   const int total = countDev ? *(volatile int*)t->totalHost : countHost;
@@ -310,14 +305,7 @@ static int colour_evaluate(itm_colour_tracker* t, int level, const float* locati
   float sc;
   if (valid == 0) { out->f = (float)0x7f800000 * 1.0f; sc = 1.0f; }
   else { sc = (float)total / (float)valid; out->f = (float)sums[0] * sc; }
-  if (gh) {
-    for (int para = 0, k = 0; para < np; ++para) {
-      out->nabla[para] = (float)sums[1 + para] * sc;
-      for (int c = 0; c <= para; ++c, ++k) out->hessian[para + c * np] = (float)sums[7 + k] * sc;
-    }
-    for (int r = 0; r < np; ++r)
-      for (int c = r + 1; c < np; ++c) out->hessian[r + c * np] = out->hessian[c + r * np];
-  }
+  if (gh) unpack_gh(sums, np, np, sc, out->nabla, out->hessian);
   return ITM_OK;
 }
 

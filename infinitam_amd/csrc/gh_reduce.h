@@ -1,4 +1,5 @@
-// gh_reduce.h -- the deterministic reduction shared by the trackers (tracker.hip: ICP, colour_tracker.hip: photometric).
+// gh_reduce.h -- the deterministic reduction shared by the trackers (tracker.hip: ICP, colour_tracker.hip: photometric,
+// ren_tracker.hip: Ren SDF), device and host halves.
 //
 // One lane per residual accumulates f, the gradient and the packed lower-triangular Hessian in double; a workgroup adds its
 // lanes with DPP row shifts and its waves in order and sends one tagged record; the host (or a gathering workgroup) adds the
@@ -142,10 +143,10 @@ static inline int read_record(const GHBlockRecord* r, unsigned int tag, double* 
 
 // Waits for the records of `blocks` workgroups tagged `seq` (pinned host memory) and adds them in the common order.  The poll is
 // bounded in TIME: after 20 ms without a granule the stream is queried between polls -- a drained stream without it, a device
-// error, or `timeoutSeconds` without progress end the call with ITM_ERR_DEVICE instead of stalling the host on a kernel that will
-// never finish.
-static inline int collect_records(const GHBlockRecord* rec, size_t blocks, unsigned int seq, hipStream_t st, double timeoutSeconds,
-                                  double sums[kGHValues], int* n) {
+// error, or kPollTimeoutSeconds without progress end the call with ITM_ERR_DEVICE instead of stalling the host on a kernel that
+// will never finish.
+constexpr double kPollTimeoutSeconds = 5.0;
+static inline int collect_records(const GHBlockRecord* rec, size_t blocks, unsigned int seq, hipStream_t st, double sums[kGHValues], int* n) {
   OrderedSums ordered;
   *n = 0;
   using clock = std::chrono::steady_clock;
@@ -161,13 +162,59 @@ static inline int collect_records(const GHBlockRecord* rec, size_t blocks, unsig
         return set_error(ITM_ERR_DEVICE, "tracker reduction: the stream drained without delivering every record");
       }
       if (q != hipErrorNotReady) return hip_fail(q, "tracker reduction", __FILE__, __LINE__);
-      if (waited > timeoutSeconds) return set_error(ITM_ERR_DEVICE, "tracker reduction timed out");
+      if (waited > kPollTimeoutSeconds) return set_error(ITM_ERR_DEVICE, "tracker reduction timed out");
       return ITM_OK;
     });
     if (rc) return rc;
   }
   ordered.total(sums);
   return ITM_OK;
+}
+
+// A tracker handle's end of the reduction: the pinned records its launches send (coherent + mapped: device stores become visible
+// to the polling host without a kernel boundary), the device they live on and the handle's sequence numbers.  One channel per
+// handle, so two handles never share records or sequence numbers.
+struct GHChannel {
+  GHBlockRecord* rec = nullptr;      // pinned host records
+  GHBlockRecord* recDev = nullptr;   // their device address
+  size_t capacity = 0;               // in workgroups
+  int device = -1;                   // the device of the last reserve
+  unsigned int seq = 0;
+
+  // the current device is not the one the records were reserved on: the handle's other buffers are of no use here either
+  bool moved() const { int dev = 0; (void)hipGetDevice(&dev); return dev != device; }
+  void release() {
+    if (rec) (void)hipHostFree(rec);
+    rec = nullptr; recDev = nullptr; capacity = 0;
+  }
+  // at least `blocks` records on the current device (grows only); on failure the channel holds none
+  int reserve(size_t blocks) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev == device && capacity >= blocks) return ITM_OK;
+    release();
+    device = dev;
+    hipError_t e = hipHostMalloc((void**)&rec, blocks * sizeof(GHBlockRecord), hipHostMallocMapped | hipHostMallocCoherent);
+    if (e == hipSuccess) { memset(rec, 0, blocks * sizeof(GHBlockRecord)); e = hipHostGetDevicePointer((void**)&recDev, rec, 0); }
+    if (e != hipSuccess) { release(); return hip_fail(e, "tracker records", __FILE__, __LINE__); }
+    capacity = blocks;
+    return ITM_OK;
+  }
+  unsigned int begin() { return seq = next_seq(seq); }   // the tag of the next evaluation's records
+  int collect(size_t blocks, unsigned int tag, hipStream_t st, double sums[kGHValues], int* n) const {
+    return collect_records(rec, blocks, tag, st, sums, n);
+  }
+};
+
+// The gradient nabla[0..np) and the symmetric Hessian hessian[r + c * ld] (column-major) from the sums, each times `scale`.
+// Scale 1 stores the bits of the plain (float) conversion: multiplying by 1.0f is exact.
+static inline void unpack_gh(const double sums[kGHValues], int np, int ld, float scale, float* nabla, float* hessian) {
+  for (int r = 0, k = 0; r < np; ++r) {
+    nabla[r] = (float)sums[1 + r] * scale;
+    for (int c = 0; c <= r; ++c, ++k) hessian[r + c * ld] = (float)sums[7 + k] * scale;
+  }
+  for (int r = 0; r < np; ++r)
+    for (int c = r + 1; c < np; ++c) hessian[r + c * ld] = hessian[c + r * ld];
 }
 
 }  // namespace itm

@@ -1,5 +1,5 @@
 // icp_solver.h -- host side of the ICP depth tracker: damped Gauss-Newton over SE(3).  Plain C++ (no HIP), shared by
-// tracker.hip (cost / gradient / Hessian evaluated on the GPU) and by the CPU check in tests/cpp/icp_solver_check.cpp.
+// tracker.hip (cost / gradient / Hessian evaluated on the GPU) and by the host-only hook itm_debug_icp_track (tests/test_tracker.py).
 #pragma once
 
 #include <cmath>

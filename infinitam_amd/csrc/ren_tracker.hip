@@ -112,33 +112,25 @@ __global__ void __launch_bounds__(kGHThreads) ren_eval_kernel(VolumeView vol, co
 
 struct itm_ren_tracker {
   mutable std::mutex mu;
-  int device = -1;
-  itm::GHBlockRecord* rec = nullptr; itm::GHBlockRecord* recDev = nullptr;   // pinned host records + their device address
-  unsigned int seq = 0;
+  itm::GHChannel ch;
   float4* points = nullptr; size_t pointsBytes = 0;
   int w = 0, h = 0;                // size of the last prepared depth image (0: nothing prepared)
-  double pollTimeoutSeconds = 5.0;
 };
 
 namespace itm {
 
 static void ren_release(itm_ren_tracker* t) {
-  if (t->rec) (void)hipHostFree(t->rec);
+  t->ch.release();
   (void)hipFree(t->points);
-  t->rec = nullptr; t->recDev = nullptr; t->points = nullptr; t->pointsBytes = 0; t->w = t->h = 0;
+  t->points = nullptr; t->pointsBytes = 0; t->w = t->h = 0;
 }
 
 static int ren_prepare(itm_ren_tracker* t, const itm_view* view, hipStream_t st) {
   if (!view || !view->depth) return set_error(ITM_ERR_INVALID, "Ren tracker: null view or depth image");
   if (view->w <= 0 || view->h <= 0) return set_error(ITM_ERR_INVALID, "Ren tracker: empty depth image");
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (t->device != dev) { ren_release(t); t->device = dev; }
-  if (!t->rec) {
-    hipError_t e = hipHostMalloc((void**)&t->rec, kGHGroups * sizeof(GHBlockRecord), hipHostMallocMapped | hipHostMallocCoherent);
-    if (e == hipSuccess) { memset(t->rec, 0, kGHGroups * sizeof(GHBlockRecord)); e = hipHostGetDevicePointer((void**)&t->recDev, t->rec, 0); }
-    if (e != hipSuccess) { ren_release(t); return hip_fail(e, "Ren tracker buffers", __FILE__, __LINE__); }
-  }
+  if (t->ch.moved()) ren_release(t);
+  int rc = t->ch.reserve(kGHGroups);
+  if (rc) return rc;
   const size_t bytes = (size_t)view->w * view->h * sizeof(float4);
   if (t->pointsBytes < bytes) {
     (void)hipFree(t->points);
@@ -148,7 +140,7 @@ static int ren_prepare(itm_ren_tracker* t, const itm_view* view, hipStream_t st)
     t->pointsBytes = bytes;
   }
   // the view's depth image may be the target of a recorded (not yet launched) engine call
-  int rc = flush_overlapping(view->depth, (size_t)view->w * view->h * 4, st);
+  rc = flush_overlapping(view->depth, (size_t)view->w * view->h * 4, st);
   if (rc) return rc;
   const float* in = view->intr_d;
   const float ox = 1.0f / in[0], oy = 1.0f / in[1];
@@ -170,15 +162,15 @@ static int ren_evaluate(itm_ren_tracker* t, const itm_scene* s, const float invM
   p.n = t->w * t->h;
   const VolumeView vol = make_volume(s);
   const bool dense = s->cfg.indexType == ITM_INDEX_DENSE;
-  const unsigned int seq = t->seq = next_seq(t->seq);
+  const unsigned int seq = t->ch.begin();
   const int rc = dispatch_voxel(s->cfg.voxelType, [&](auto vx) {
     using VX = decltype(vx);
     if (dense) {
-      if (gh) ren_eval_kernel<VX, true, true><<<kGHGroups, kGHThreads, 0, st>>>(vol, t->points, p, t->recDev, seq);
-      else ren_eval_kernel<VX, true, false><<<kGHGroups, kGHThreads, 0, st>>>(vol, t->points, p, t->recDev, seq);
+      if (gh) ren_eval_kernel<VX, true, true><<<kGHGroups, kGHThreads, 0, st>>>(vol, t->points, p, t->ch.recDev, seq);
+      else ren_eval_kernel<VX, true, false><<<kGHGroups, kGHThreads, 0, st>>>(vol, t->points, p, t->ch.recDev, seq);
     } else {
-      if (gh) ren_eval_kernel<VX, false, true><<<kGHGroups, kGHThreads, 0, st>>>(vol, t->points, p, t->recDev, seq);
-      else ren_eval_kernel<VX, false, false><<<kGHGroups, kGHThreads, 0, st>>>(vol, t->points, p, t->recDev, seq);
+      if (gh) ren_eval_kernel<VX, false, true><<<kGHGroups, kGHThreads, 0, st>>>(vol, t->points, p, t->ch.recDev, seq);
+      else ren_eval_kernel<VX, false, false><<<kGHGroups, kGHThreads, 0, st>>>(vol, t->points, p, t->ch.recDev, seq);
     }
     return ITM_OK;
   });
@@ -186,17 +178,12 @@ static int ren_evaluate(itm_ren_tracker* t, const itm_scene* s, const float invM
   ITM_LAUNCH_CHECK();
   double sums[kGHValues];
   int valid = 0;
-  const int r = collect_records(t->rec, kGHGroups, seq, st, t->pollTimeoutSeconds, sums, &valid);
+  const int r = t->ch.collect(kGHGroups, seq, st, sums, &valid);
   if (r) return r;
   out->f = -(float)sums[0];
   if (gh) {
     out->noValidPoints = valid;
-    for (int row = 0, k = 0; row < 6; ++row) {
-      out->nabla[row] = (float)sums[1 + row];
-      for (int c = 0; c <= row; ++c, ++k) out->hessian[row + c * 6] = (float)sums[7 + k];
-    }
-    for (int row = 0; row < 6; ++row)
-      for (int c = row + 1; c < 6; ++c) out->hessian[row + c * 6] = out->hessian[c + row * 6];
+    unpack_gh(sums, 6, 6, 1.0f, out->nabla, out->hessian);
   }
   return ITM_OK;
 }

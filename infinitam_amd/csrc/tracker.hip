@@ -441,18 +441,13 @@ __global__ void __launch_bounds__(kGHThreads) gh_session_kernel(const unsigned l
 
 struct itm_tracker {
   std::mutex mu;
-  int device = -1;
-  itm::GHBlockRecord* devRec = nullptr;       // device memory: the workgroups' records of a session's fine levels
-  itm::GHBlockRecord* rec = nullptr; itm::GHBlockRecord* recDev = nullptr;   // pinned host records + their device address
-  size_t blocks = 0;
-  unsigned int seq = 0;
+  itm::GHChannel ch;                      // pinned host records of every evaluation (a session's coarse levels included)
   std::vector<float*> pyramid; std::vector<size_t> pyramidBytes;
-  double pollTimeoutSeconds = 5.0;
-  double sessionTimeoutSeconds = 0.5;     // an evaluation through the resident kernel answers in microseconds; after this long it goes through a launch
   int sessionUsable = -1;                 // -1 not probed yet, 0 launch per evaluation, 1 resident evaluation kernel
   int sessionFallbacks = 0;
   int debugEvaluations = 0;
   // evaluation session (gh_session_kernel)
+  itm::GHBlockRecord* devRec = nullptr;   // device memory: the workgroups' records of a session's fine levels (kGHGroups)
   unsigned long long* cmd = nullptr; unsigned long long* cmdDev = nullptr;   // command granules (BAR-mapped device memory or pinned host memory) + their device address
   itm::GHResult* res = nullptr; itm::GHResult* resDev = nullptr;     // pinned result + its device address
   unsigned long long* devCmd = nullptr;   // device memory: republished command granules
@@ -474,43 +469,38 @@ static void tracker_release(itm_tracker* t) {
     write_exit(t);
     t->sessionOpen = false;
   }
+  t->ch.release();
   (void)hipFree(t->devRec);
-  if (t->rec) (void)hipHostFree(t->rec);
   if (t->cmd) { if (t->cmdDirect) (void)hipFree(t->cmd); else (void)hipHostFree(t->cmd); }
   if (t->res) (void)hipHostFree(t->res);
   (void)hipFree(t->devCmd);
-  t->cmd = nullptr; t->cmdDev = nullptr; t->res = nullptr; t->resDev = nullptr; t->devCmd = nullptr;
+  t->devRec = nullptr; t->cmd = nullptr; t->cmdDev = nullptr; t->res = nullptr; t->resDev = nullptr; t->devCmd = nullptr;
   t->sessionOpen = false;
   for (float* q : t->pyramid) (void)hipFree(q);
-  t->devRec = nullptr; t->rec = nullptr; t->recDev = nullptr; t->blocks = 0;
   t->pyramid.clear(); t->pyramidBytes.clear();
 }
 
-// (re)sizes the reduction buffers for `blocks` workgroups on the current device; on failure the handle is left empty
+// records for `blocks` workgroups on the current device
 static int tracker_reserve(itm_tracker* t, size_t blocks) {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (t->device == dev && t->blocks >= blocks) return ITM_OK;
-  if (t->device != dev) tracker_release(t);           // buffers of another device (incl. the pyramid) are of no use here
-  else {
-    (void)hipFree(t->devRec);
-    if (t->rec) (void)hipHostFree(t->rec);
-    t->devRec = nullptr; t->rec = nullptr; t->recDev = nullptr;
-  }
-  t->blocks = 0; t->device = dev;
-  hipError_t e = hipMalloc((void**)&t->devRec, blocks * sizeof(GHBlockRecord));
-  if (e == hipSuccess) e = hipMemset(t->devRec, 0, blocks * sizeof(GHBlockRecord));        // tag 0: no record
-  // coherent + mapped: device stores become visible to the polling host without a kernel boundary
-  if (e == hipSuccess) e = hipHostMalloc((void**)&t->rec, blocks * sizeof(GHBlockRecord), hipHostMallocMapped | hipHostMallocCoherent);
-  if (e == hipSuccess) { memset(t->rec, 0, blocks * sizeof(GHBlockRecord)); e = hipHostGetDevicePointer((void**)&t->recDev, t->rec, 0); }
-  if (e != hipSuccess) {
-    (void)hipFree(t->devRec);
-    if (t->rec) (void)hipHostFree(t->rec);
-    t->devRec = nullptr; t->rec = nullptr; t->recDev = nullptr;
-    return hip_fail(e, "tracker buffers", __FILE__, __LINE__);
-  }
-  t->blocks = blocks;
-  return ITM_OK;
+  if (t->ch.moved()) tracker_release(t);           // buffers of another device (incl. the pyramid and the session's) are of no use here
+  return t->ch.reserve(blocks);
+}
+
+static GHParams gh_params(int w, int h, const float* viewIntr, int sceneW, int sceneH, const float* sceneIntr, const float* approxInvPose,
+                          const float* scenePose, float distThresh, int tileH) {
+  GHParams p;
+  memcpy(p.approxInvPose.m, approxInvPose, 64); memcpy(p.scenePose.m, scenePose, 64);
+  p.vfx = viewIntr[0]; p.vfy = viewIntr[1]; p.vcx = viewIntr[2]; p.vcy = viewIntr[3];
+  p.sfx = sceneIntr[0]; p.sfy = sceneIntr[1]; p.scx = sceneIntr[2]; p.scy = sceneIntr[3];
+  p.distThresh = distThresh; p.w = w; p.h = h; p.sceneW = sceneW; p.sceneH = sceneH; p.tileH = tileH;
+  return p;
+}
+
+// ITMDepthTracker's result from the sums: f = sqrt(sum of squared residuals) / valid count, 1e5 when too few points are valid
+static void icp_result(const double sums[kGHValues], int n, int np, itm_tracker_gh* out) {
+  unpack_gh(sums, np, 6, 1.0f, out->nabla, out->hessian);
+  out->noValidPoints = n;
+  out->f = (n > 100) ? std::sqrt((float)sums[0]) / n : 1e5f;
 }
 
 // the calling thread's own tracker for the handle-less entry points (never destroyed: HIP may already be gone at thread exit)
@@ -534,30 +524,20 @@ static int compute_g_and_h(itm_tracker* trk, const float* depth, int w, int h, c
   const size_t blocks = grid.x;
   int rc = tracker_reserve(trk, blocks);
   if (rc) return rc;
-  GHParams p;
-  memcpy(p.approxInvPose.m, approxInvPose, 64); memcpy(p.scenePose.m, scenePose, 64);
-  p.vfx = viewIntr[0]; p.vfy = viewIntr[1]; p.vcx = viewIntr[2]; p.vcy = viewIntr[3];
-  p.sfx = sceneIntr[0]; p.sfy = sceneIntr[1]; p.scx = sceneIntr[2]; p.scy = sceneIntr[3];
-  p.distThresh = distThresh; p.w = w; p.h = h; p.sceneW = sceneW; p.sceneH = sceneH; p.tileH = tileH;
+  const GHParams p = gh_params(w, h, viewIntr, sceneW, sceneH, sceneIntr, approxInvPose, scenePose, distThresh, tileH);
   const float4* pm = (const float4*)pointsMap; const float4* nm = (const float4*)normalsMap;
   const int np = (iterationType == ITM_TRACKER_ITERATION_BOTH) ? 6 : 3;
-  const unsigned int seq = trk->seq = next_seq(trk->seq);
-  if (iterationType == 1) gh_partial_kernel<1><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, trk->recDev, seq);
-  else if (iterationType == 2) gh_partial_kernel<2><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, trk->recDev, seq);
-  else gh_partial_kernel<3><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, trk->recDev, seq);
+  const unsigned int seq = trk->ch.begin();
+  if (iterationType == 1) gh_partial_kernel<1><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, trk->ch.recDev, seq);
+  else if (iterationType == 2) gh_partial_kernel<2><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, trk->ch.recDev, seq);
+  else gh_partial_kernel<3><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, trk->ch.recDev, seq);
   ITM_LAUNCH_CHECK();
   // Wait for every workgroup's tagged record and add them in block order (fixed order => deterministic, in double; bounded wait)
   double sums[kGHValues];
   int n = 0;
-  rc = collect_records(trk->rec, blocks, seq, st, trk->pollTimeoutSeconds, sums, &n);
+  rc = trk->ch.collect(blocks, seq, st, sums, &n);
   if (rc) return rc;
-  for (int r = 0, k = 0; r < np; ++r)
-    for (int c = 0; c <= r; ++c, ++k) out->hessian[r + c * 6] = (float)sums[7 + k];
-  for (int r = 0; r < np; ++r)
-    for (int c = r + 1; c < np; ++c) out->hessian[r + c * 6] = out->hessian[c + r * 6];
-  for (int r = 0; r < np; ++r) out->nabla[r] = (float)sums[1 + r];
-  out->noValidPoints = n;
-  out->f = (n > 100) ? std::sqrt((float)sums[0]) / n : 1e5f;
+  icp_result(sums, n, np, out);
   return ITM_OK;
 }
 
@@ -567,6 +547,7 @@ int g_debug_tracker_session_unusable = 0;        // debug key 18: the resident k
 int g_debug_tracker_host_command = 0;            // debug key 11: session commands through pinned host memory even where the device has a large BAR
 
 constexpr int kSessionUnusable = -1000;     // internal: the resident kernel cannot serve this evaluation, use a launch instead
+constexpr double kSessionTimeoutSeconds = 0.5;   // an evaluation through the resident kernel answers in microseconds; after this long it goes through a launch
 
 static int session_reserve(itm_tracker* t) {
   int rc = tracker_reserve(t, kGHGroups);
@@ -593,12 +574,15 @@ static int session_reserve(itm_tracker* t) {
   if (e == hipSuccess) { memset(t->res, 0, sizeof(GHResult)); e = hipHostGetDevicePointer((void**)&t->resDev, t->res, 0); }
   if (e == hipSuccess) e = hipMalloc((void**)&t->devCmd, cmdBytes);
   if (e == hipSuccess) e = hipMemset(t->devCmd, 0, cmdBytes);
+  if (e == hipSuccess) e = hipMalloc((void**)&t->devRec, kGHGroups * sizeof(GHBlockRecord));
+  if (e == hipSuccess) e = hipMemset(t->devRec, 0, kGHGroups * sizeof(GHBlockRecord));        // tag 0: no record
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e != hipSuccess) {
     if (t->cmd) { if (t->cmdDirect) (void)hipFree(t->cmd); else (void)hipHostFree(t->cmd); }
     if (t->res) (void)hipHostFree(t->res);
     (void)hipFree(t->devCmd);
-    t->cmd = nullptr; t->res = nullptr; t->devCmd = nullptr;
+    (void)hipFree(t->devRec);
+    t->cmd = nullptr; t->res = nullptr; t->devCmd = nullptr; t->devRec = nullptr;
     return hip_fail(e, "tracker session buffers", __FILE__, __LINE__);
   }
   return ITM_OK;
@@ -606,7 +590,7 @@ static int session_reserve(itm_tracker* t) {
 
 static int session_launch(itm_tracker* t, unsigned int firstSeq, hipStream_t st) {
   ++t->session;
-  gh_session_kernel<<<kGHGroups, kGHThreads, 0, st>>>(t->cmdDev, t->devCmd, t->devRec, t->resDev, t->recDev, t->session, firstSeq, t->cmdDirect ? 1 : 0);
+  gh_session_kernel<<<kGHGroups, kGHThreads, 0, st>>>(t->cmdDev, t->devCmd, t->devRec, t->resDev, t->ch.recDev, t->session, firstSeq, t->cmdDirect ? 1 : 0);
   ITM_LAUNCH_CHECK();
   t->sessionOpen = true;
   return ITM_OK;
@@ -652,23 +636,20 @@ static int session_g_and_h(itm_tracker* trk, const float* depth, int w, int h, c
       __builtin_ia32_pause();
       if ((++spins & 0xfffu) != 0u) continue;
       if (hipStreamQuery(st) != hipErrorNotReady) break;                 // nothing is running on the stream any more
-      if (std::chrono::duration<double>(clock::now() - t0).count() > trk->pollTimeoutSeconds) return set_error(ITM_ERR_DEVICE, "tracker session did not end");
+      if (std::chrono::duration<double>(clock::now() - t0).count() > kPollTimeoutSeconds) return set_error(ITM_ERR_DEVICE, "tracker session did not end");
     }
   }
   ITM_TT(const auto tt0 = clock::now();)
   GHCommand c;
   memset(&c, 0, sizeof c);
-  memcpy(c.p.approxInvPose.m, approxInvPose, 64); memcpy(c.p.scenePose.m, scenePose, 64);
-  c.p.vfx = viewIntr[0]; c.p.vfy = viewIntr[1]; c.p.vcx = viewIntr[2]; c.p.vcy = viewIntr[3];
-  c.p.sfx = sceneIntr[0]; c.p.sfy = sceneIntr[1]; c.p.scx = sceneIntr[2]; c.p.scy = sceneIntr[3];
-  c.p.distThresh = distThresh; c.p.w = w; c.p.h = h; c.p.sceneW = sceneW; c.p.sceneH = sceneH; c.p.tileH = tileH;
+  c.p = gh_params(w, h, viewIntr, sceneW, sceneH, sceneIntr, approxInvPose, scenePose, distThresh, tileH);
   c.depth = depth; c.points = (const float4*)pointsMap; c.normals = (const float4*)normalsMap;
   c.mode = iterationType; c.activeBlocks = (tiles + rounds - 1) / rounds;       // the grid of the per-launch path: same tiles per block, same sums
   const int nBlocks = c.activeBlocks;
   const bool toHost = nBlocks <= kSessionToHostBlocks;
   c.toHost = toHost ? 1 : 0;
   c.session = trk->sessionOpen ? trk->session : trk->session + 1u;
-  const unsigned int seq = trk->seq = next_seq(trk->seq);
+  const unsigned int seq = trk->ch.begin();
   write_command(trk, c, seq);
   ITM_TT(const auto ttA = clock::now();)
   if (!trk->sessionOpen && (rc = session_launch(trk, seq, st))) return rc;
@@ -693,7 +674,7 @@ static int session_g_and_h(itm_tracker* trk, const float* depth, int w, int h, c
     if (waited < 0.02) return ITM_OK;
     const hipError_t q = hipStreamQuery(st);
     if (q != hipSuccess && q != hipErrorNotReady) { trk->sessionOpen = false; return hip_fail(q, "tracker session", __FILE__, __LINE__); }
-    if (waited > trk->sessionTimeoutSeconds) { session_close(trk); return set_error(kSessionUnusable, "tracker session timed out"); }
+    if (waited > kSessionTimeoutSeconds) { session_close(trk); return set_error(kSessionUnusable, "tracker session timed out"); }
     return ITM_OK;
   };
   double sums[kGHValues];
@@ -701,7 +682,7 @@ static int session_g_and_h(itm_tracker* trk, const float* depth, int w, int h, c
   int n = 0;
   if (toHost) {
     OrderedSums ordered;
-    for (int b = 0; b < nBlocks && !rc; ++b) rc = read_record(trk->rec + b, seq, ordered.of_block(b), &n, slow);
+    for (int b = 0; b < nBlocks && !rc; ++b) rc = read_record(trk->ch.rec + b, seq, ordered.of_block(b), &n, slow);
     ordered.total(sums);
   } else {
     const int segments = (nBlocks + kSegBlocks - 1) / kSegBlocks;          // the device added each segment; the segments in order here
@@ -715,14 +696,7 @@ static int session_g_and_h(itm_tracker* trk, const float* depth, int w, int h, c
                    std::chrono::duration<double, std::micro>(ttA - tt0).count(), std::chrono::duration<double, std::micro>(ttB - ttA).count(),
                    std::chrono::duration<double, std::micro>(ttC - ttB).count(),
                    (double)(r->stamps[4] - r->stamps[0]) / 100.0, (double)(r->stamps[5] - r->stamps[0]) / 100.0, (double)(r->stamps[1] - r->stamps[0]) / 100.0, toHost ? "reduced" : "gathering from", (double)(r->stamps[2] - r->stamps[0]) / 100.0, (double)(r->stamps[3] - r->stamps[0]) / 100.0); })
-  const int np = (iterationType == ITM_TRACKER_ITERATION_BOTH) ? 6 : 3;
-  for (int a = 0, k = 0; a < np; ++a)
-    for (int b = 0; b <= a; ++b, ++k) out->hessian[a + b * 6] = (float)sums[7 + k];
-  for (int a = 0; a < np; ++a)
-    for (int b = a + 1; b < np; ++b) out->hessian[a + b * 6] = out->hessian[b + a * 6];
-  for (int a = 0; a < np; ++a) out->nabla[a] = (float)sums[1 + a];
-  out->noValidPoints = n;
-  out->f = (n > 100) ? std::sqrt((float)sums[0]) / n : 1e5f;
+  icp_result(sums, n, (iterationType == ITM_TRACKER_ITERATION_BOTH) ? 6 : 3, out);
   return ITM_OK;
 }
 
@@ -776,11 +750,11 @@ static int track_camera(itm_tracker* trk, const itm_tracker_config* cfg, const i
   ITM_TT(const auto tc0 = std::chrono::steady_clock::now();)
   if ((rc = build_pyramid(trk, view, levels, pyr, st))) return rc;
   ITM_TT(const auto tc1 = std::chrono::steady_clock::now();)
-  if (g_debug_tracker_launch_per_evaluation)
-    return icp_track(cfg, view->M_d, M_d_out, [&](int level, int mode, const float invPose[16], float distThresh, itm_tracker_gh* e) {
-      return compute_g_and_h(trk, pyr[level].depth, pyr[level].w, pyr[level].h, pyr[level].intr, pointsMap, normalsMap, view->w, view->h,
-                             pyr[0].intr, invPose, scenePose, distThresh, mode, e, st);
-    });
+  auto per_launch = [&](int level, int mode, const float invPose[16], float distThresh, itm_tracker_gh* e) {
+    return compute_g_and_h(trk, pyr[level].depth, pyr[level].w, pyr[level].h, pyr[level].intr, pointsMap, normalsMap, view->w, view->h,
+                           pyr[0].intr, invPose, scenePose, distThresh, mode, e, st);
+  };
+  if (g_debug_tracker_launch_per_evaluation) return icp_track(cfg, view->M_d, M_d_out, per_launch);
   // One resident kernel for all evaluations of this call -- and one such kernel per DEVICE at a time: its workgroups take a compute
   // unit's whole register budget for one wave per SIMD (256 VGPRs), so two sessions cannot share a compute unit, and two sessions
   // that have each got hold of SOME compute units wait for the rest until their idle limits fire (measured with four closed loops
@@ -798,12 +772,8 @@ static int track_camera(itm_tracker* trk, const itm_tracker_config* cfg, const i
     (void)hipGetLastError();
     trk->sessionUsable = (ok && (long long)perCU * cus >= kGHGroups) ? 1 : 0;
   }
-  auto per_launch = [&](int level, int mode, const float invPose[16], float distThresh, itm_tracker_gh* e) {
-    return compute_g_and_h(trk, pyr[level].depth, pyr[level].w, pyr[level].h, pyr[level].intr, pointsMap, normalsMap, view->w, view->h,
-                           pyr[0].intr, invPose, scenePose, distThresh, mode, e, st);
-  };
   if (!trk->sessionUsable) return icp_track(cfg, view->M_d, M_d_out, per_launch);
-  std::lock_guard<std::mutex> oneSession(session_gate(trk->device));
+  std::lock_guard<std::mutex> oneSession(session_gate(trk->ch.device));
   rc = icp_track(cfg, view->M_d, M_d_out, [&](int level, int mode, const float invPose[16], float distThresh, itm_tracker_gh* e) {
     if (trk->sessionUsable) {
       const int r = (g_debug_tracker_session_unusable > 0 && ++trk->debugEvaluations == g_debug_tracker_session_unusable) ? kSessionUnusable : session_g_and_h(trk, pyr[level].depth, pyr[level].w, pyr[level].h, pyr[level].intr, pointsMap, normalsMap, view->w, view->h,
