@@ -63,6 +63,11 @@ typedef int (*itm_icp_evaluate_fn)(void* user, int level, int iterationType, con
                                    float distThresh, itm_tracker_gh* out);
 int ITM_FN(debug_icp_track)(const itm_tracker_config* cfg, const float M_d[16], itm_icp_evaluate_fn evaluate,
                             void* user, float M_d_out[16]);
+/* Test hook (host only, no device work): the weighted ICP tracker's host iteration (ITMWeightedICPTracker::TrackCamera: level
+ * schedule, undamped step, SE(3) update) driven by a caller-supplied evaluator of the weighted sums -- the WICP twin of
+ * itm_debug_icp_track. */
+int ITM_FN(debug_wicp_track)(const itm_tracker_config* cfg, const float M_d[16], itm_icp_evaluate_fn evaluate,
+                             void* user, float M_d_out[16]);
 
 #ifdef __cplusplus
 }

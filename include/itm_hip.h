@@ -435,6 +435,28 @@ int ITM_FN(tracker_track_camera)(itm_tracker* tracker, const itm_tracker_config*
                                  const float* pointsMap, const float* normalsMap, const float scenePose[16],
                                  float M_d_out[16], itm_stream stream);
 
+/* ---- weighted ICP tracker (this fork's ITMWeightedICPTracker, TRACKER_WICP) on the same handle -------------------------------------
+ * The ICP evaluation with a per-pixel weight w = sigmaZ > 0 ? 0.0012f / sigmaZ * 0.5f + 0.5f : 0 from the view's uncertainty image
+ * (ComputeNormalAndWeights: -1 where no normal, the 2-pixel border unwritten); b from the unweighted normal, f from sum b^2 w^2,
+ * nabla = sum w b A, H = sum w^2 A A^T; a pixel of weight 0 still counts in noValidPoints.  Replaces:
+ *   ITMWeightedICPTracker_CPU::ComputeGandH    DeviceSpecific/CPU/ITMWeightedICPTracker_CPU.cpp:14-86,
+ *                                              DeviceAgnostic/ITMWeightedICPTracker.h:10-107 (computePerPointGH_wICP)
+ *   ITMWeightedICPTracker::TrackCamera & co.   Engine/ITMWeightedICPTracker.cpp:10-45,57-100,102-191
+ * The handle adds a sigmaZ pyramid (allocated on first use) to its depth pyramid and reduction records.
+ * weighted_g_and_h: one level's sums, `weight` = that level's sigmaZ image (float[h*w], device).  Synchronises `stream`. */
+int ITM_FN(tracker_weighted_g_and_h)(itm_tracker* tracker, const float* depth, const float* weight, int w, int h,
+                                     const float viewIntr[4], const float* pointsMap, const float* normalsMap, int sceneW,
+                                     int sceneH, const float sceneIntr[4], const float approxInvPose[16],
+                                     const float scenePose[16], float distThresh, int iterationType, itm_tracker_gh* out,
+                                     itm_stream stream);
+/* TrackCamera: pyramids of view->depth and sigmaZ (the view's uncertainty image, float[h*w], device; its border must be <= 0),
+ * coarse to fine from view->M_d, undamped Gauss-Newton steps (the 3x3 block on rotation- or translation-only levels); writes the
+ * refined, coerced pose_d to M_d_out.  Where the weighted system is singular (e.g. every weight 0) the level ends without a step.
+ * Synchronises `stream`. */
+int ITM_FN(tracker_weighted_track_camera)(itm_tracker* tracker, const itm_tracker_config* cfg, const itm_view* view,
+                                          const float* sigmaZ, const float* pointsMap, const float* normalsMap,
+                                          const float scenePose[16], float M_d_out[16], itm_stream stream);
+
 /* ---- colour (photometric) tracker ------------------------------------------------------------------
  * Aligns the rgb image of a view with the coloured point cloud CreatePointCloud wrote for the previous pose.  Device-specific half:
  *   ITMColorTracker::PrepareForEvaluation           Engine/ITMColorTracker.cpp:49-68 (CopyImage, FilterSubsample, GradientX / Y:

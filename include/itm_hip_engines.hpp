@@ -17,6 +17,7 @@
 #include <cstring>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "itm_hip.h"
 
@@ -67,6 +68,7 @@ struct ITMView {
   ITMRGBDCalib calib;
   const float* depth = nullptr;  // device float[h*w]
   const uint8_t* rgb = nullptr;  // device uchar4[h_rgb*w_rgb]
+  const float* depthUncertainty = nullptr;  // device float[h*w]: sigmaZ of ComputeNormalAndWeights (modelSensorNoise, TRACKER_WICP)
   Vector2i depthSize{0, 0}, rgbSize{0, 0};
 };
 
@@ -100,7 +102,7 @@ struct ITMTrackingState {
 
 // ITMLibSettings (Utils/ITMLibSettings.h / .cpp:9-90): the members the path's callers read, with the reference's defaults
 struct ITMLibSettings {
-  enum TrackerType { TRACKER_COLOR, TRACKER_ICP, TRACKER_EXTERNAL, TRACKER_REN };   // TRACKER_REN appended: the others keep their values
+  enum TrackerType { TRACKER_COLOR, TRACKER_ICP, TRACKER_EXTERNAL, TRACKER_REN, TRACKER_WICP };   // TRACKER_REN, TRACKER_WICP appended: the others keep their values
   ITMSceneParamsDefaults sceneParamsDefaults;   // (0.02, 100, 0.005, 0.35, 3.0, false), ITMLibSettings.cpp:10
   float depthTrackerICPThreshold = 0.1f * 0.1f;
   float depthTrackerTerminationThreshold = 1e-3f;
@@ -415,6 +417,41 @@ class ITMDepthTrackerAdapter : public ITMTracker {
   void TrackCamera(ITMTrackingState* ts, const ITMView* view) override { t->TrackCamera(ts, view); }
 };
 
+// ITMWeightedICPTracker (Engine/ITMWeightedICPTracker.h, .cpp): ICP with a per-pixel weight from the view's uncertainty image
+// (view->depthUncertainty); depth and weight pyramids, weighted evaluation and reduction on the GPU (itm_tracker_weighted_*).
+class ITMWeightedICPTracker_HIP {
+  itm_tracker_config cfg;
+  itm_tracker* tracker = nullptr;     // this object's hierarchies + reduction buffers; one per tracker object
+
+ public:
+  itm_stream stream = nullptr;
+  ITMWeightedICPTracker_HIP(const int* trackingRegime, int noHierarchyLevels, int noICPRunTillLevel, float distThresh, float terminationThreshold) {
+    std::memset(&cfg, 0, sizeof cfg);
+    cfg.noHierarchyLevels = noHierarchyLevels;
+    for (int i = 0; i < noHierarchyLevels && i < 8; ++i) cfg.trackingRegime[i] = trackingRegime[i];
+    cfg.noICPRunTillLevel = noICPRunTillLevel; cfg.distThresh = distThresh; cfg.terminationThreshold = terminationThreshold;
+    check(itm_tracker_create(&tracker), "itm_tracker_create");
+  }
+  ~ITMWeightedICPTracker_HIP() { itm_tracker_destroy(tracker); }
+  ITMWeightedICPTracker_HIP(const ITMWeightedICPTracker_HIP&) = delete;
+  ITMWeightedICPTracker_HIP& operator=(const ITMWeightedICPTracker_HIP&) = delete;
+  void TrackCamera(ITMTrackingState* trackingState, const ITMView* view) {
+    if (!view->depthUncertainty) throw std::runtime_error("TrackCamera: the weighted ICP tracker needs the view's uncertainty image");
+    itm_view v = make_view(view, trackingState);
+    float M[16];
+    check(itm_tracker_weighted_track_camera(tracker, &cfg, &v, view->depthUncertainty, trackingState->pointCloud_locations,
+                                            trackingState->pointCloud_colours, trackingState->pose_pointCloud.GetM(), M, stream), "TrackCamera");
+    trackingState->pose_d.SetM(M);
+  }
+};
+// adapter: ITMWeightedICPTracker_HIP behind the ITMTracker interface
+class ITMWeightedICPTrackerAdapter : public ITMTracker {
+  ITMWeightedICPTracker_HIP* t;
+ public:
+  explicit ITMWeightedICPTrackerAdapter(ITMWeightedICPTracker_HIP* t_) : t(t_) {}
+  void TrackCamera(ITMTrackingState* ts, const ITMView* view) override { t->TrackCamera(ts, view); }
+};
+
 // ITMColorTracker (Engine/ITMColorTracker.h, .cpp:25-47): TrackCamera aligns the view's rgb image with the coloured point cloud that
 // Prepare's CreatePointCloud left in the tracking state; pyramid, evaluation and reduction on the GPU (itm_colour_tracker_*).  The
 // point count is read on the device from the render state CreatePointCloud wrote into.
@@ -547,6 +584,7 @@ class ITMMainEngine_HIP {
   ITMDepthTracker_HIP* depthTracker = nullptr;
   ITMColorTracker_HIP* colourTracker = nullptr;
   ITMRenTracker_HIP<TVoxel, TIndex>* renTracker = nullptr;
+  ITMWeightedICPTracker_HIP* wicpTracker = nullptr;
   ITMTracker* tracker = nullptr;
   ITMTrackingController_HIP<TVoxel, TIndex>* trackingController = nullptr;
   ITMViewBuilder_HIP* viewBuilder = nullptr;
@@ -571,6 +609,11 @@ class ITMMainEngine_HIP {
     check(itm_dev_malloc(&normalBuf, P * 16), "malloc"); check(itm_dev_malloc(&sigmaBuf, P * 4), "malloc");
     check(itm_dev_malloc(&pointsBuf, PT * 16), "malloc"); check(itm_dev_malloc(&coloursBuf, PT * 16), "malloc");
     trackingState.pointCloud_locations = (float*)pointsBuf; trackingState.pointCloud_colours = (float*)coloursBuf;
+    {   // ComputeNormalAndWeights writes the interior only: the 2-pixel border keeps the 0 of the reference's cleared image (weight 0)
+      std::vector<float> zeros(P, 0.0f);
+      check(itm_memcpy_h2d(sigmaBuf, zeros.data(), P * 4, nullptr), "clear sigmaZ");
+      check(itm_stream_synchronize(nullptr), "clear sigmaZ");
+    }
     denseMapper.ResetScene(&scene);
     viewBuilder = new ITMViewBuilder_HIP(&view.calib, calibType, c0, c1);
     renderState_live = visualisationEngine.CreateRenderState(tracked);
@@ -584,13 +627,17 @@ class ITMMainEngine_HIP {
     } else if (settings.trackerType == ITMLibSettings::TRACKER_REN) {
       renTracker = new ITMRenTracker_HIP<TVoxel, TIndex>(&scene);     // MakeRenTracker: the Ren tracker alone, not a composite with ICP
       tracker = new ITMRenTrackerAdapter<TVoxel, TIndex>(renTracker);
+    } else if (settings.trackerType == ITMLibSettings::TRACKER_WICP) {
+      wicpTracker = new ITMWeightedICPTracker_HIP(settings.trackingRegime, settings.noHierarchyLevels, settings.noICPRunTillLevel,
+                                                  settings.depthTrackerICPThreshold, settings.depthTrackerTerminationThreshold);
+      tracker = new ITMWeightedICPTrackerAdapter(wicpTracker);
     } else {
       tracker = new ITMExternalTracker();          // TRACKER_EXTERNAL, and TRACKER_COLOR with poses from outside (useColourTracker = false)
     }
     trackingController = new ITMTrackingController_HIP<TVoxel, TIndex>(tracker, &visualisationEngine, &settings);
   }
   ~ITMMainEngine_HIP() {
-    delete renderState_live; delete trackingController; delete tracker; delete depthTracker; delete colourTracker; delete renTracker; delete viewBuilder;
+    delete renderState_live; delete trackingController; delete tracker; delete depthTracker; delete colourTracker; delete renTracker; delete wicpTracker; delete viewBuilder;
     for (void* p : {depthBuf, scratchBuf, normalBuf, sigmaBuf, pointsBuf, coloursBuf}) itm_dev_free(p);
   }
   ITMMainEngine_HIP(const ITMMainEngine_HIP&) = delete;
@@ -610,11 +657,14 @@ class ITMMainEngine_HIP {
   const ITMViewBuilder_HIP* GetViewBuilder() const { return viewBuilder; }
 
   // rgbImage: device uchar4 (may be null without colour), rawDepthImage: device short
+  // ITMLibSettings.cpp:51-54: the weighted ICP tracker switches the sensor-noise model on
+  bool ModelSensorNoise() const { return settings.modelSensorNoise || settings.trackerType == ITMLibSettings::TRACKER_WICP; }
   void ProcessFrame(const uint8_t* rgbImage, const int16_t* rawDepthImage) {
     // prepare image and turn it into a depth image
     view.rgb = rgbImage;
-    viewBuilder->UpdateView(&view, rawDepthImage, (float*)depthBuf, (float*)scratchBuf, settings.useBilateralFilter, settings.modelSensorNoise,
+    viewBuilder->UpdateView(&view, rawDepthImage, (float*)depthBuf, (float*)scratchBuf, settings.useBilateralFilter, ModelSensorNoise(),
                             (float*)normalBuf, (float*)sigmaBuf);
+    view.depthUncertainty = ModelSensorNoise() ? (const float*)sigmaBuf : nullptr;
     ProcessView();
   }
   // The reference's own signature takes the raw frame in HOST memory (Engine/ITMMainEngine.cpp:111): rawDepthHost in page-locked memory
@@ -624,8 +674,9 @@ class ITMMainEngine_HIP {
   // copy instead (ITMViewBuilder_CUDA.cu:53); an image source with two buffers never has to wait here.
   void ProcessFrameFromHost(const uint8_t* rgbImage, const int16_t* rawDepthHost, const int16_t* nextRawDepthHost = nullptr) {
     view.rgb = rgbImage;
-    viewBuilder->UpdateViewFromHost(&view, rawDepthHost, (float*)depthBuf, (float*)scratchBuf, settings.useBilateralFilter, settings.modelSensorNoise,
+    viewBuilder->UpdateViewFromHost(&view, rawDepthHost, (float*)depthBuf, (float*)scratchBuf, settings.useBilateralFilter, ModelSensorNoise(),
                                     (float*)normalBuf, (float*)sigmaBuf);
+    view.depthUncertainty = ModelSensorNoise() ? (const float*)sigmaBuf : nullptr;
     if (nextRawDepthHost) viewBuilder->Prefetch(nextRawDepthHost, view.depthSize);
     ProcessView();
   }

@@ -236,11 +236,17 @@ _HOST_IO_SIGS = {
     "scene_load": (C.c_int, [_P, _P, C.c_char_p, _P]),
     # tracker handles (the oracle / reference shims have no use for them: their trackers are stateless)
     "debug_icp_track": (C.c_int, [C.POINTER(TrackerConfig), C.POINTER(C.c_float), _P, _P, C.POINTER(C.c_float)]),
+    "debug_wicp_track": (C.c_int, [C.POINTER(TrackerConfig), C.POINTER(C.c_float), _P, _P, C.POINTER(C.c_float)]),
     "tracker_create": (C.c_int, [C.POINTER(_P)]),
     "tracker_destroy": (C.c_int, [_P]),
     "tracker_g_and_h": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_float), _P, _P, C.c_int, C.c_int, C.POINTER(C.c_float),
                                   C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_int, C.POINTER(TrackerGH), _P]),
     "tracker_track_camera": (C.c_int, [_P, C.POINTER(TrackerConfig), C.POINTER(ViewStruct), _P, _P, C.POINTER(C.c_float), C.POINTER(C.c_float), _P]),
+    "tracker_weighted_g_and_h": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.POINTER(C.c_float), _P, _P, C.c_int, C.c_int,
+                                           C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_int,
+                                           C.POINTER(TrackerGH), _P]),
+    "tracker_weighted_track_camera": (C.c_int, [_P, C.POINTER(TrackerConfig), C.POINTER(ViewStruct), _P, _P, _P, C.POINTER(C.c_float),
+                                                C.POINTER(C.c_float), _P]),
     "debug_column_cull_rows": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_float, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                          C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "debug_dense_classify_check": (C.c_int, [C.POINTER(C.c_int32), C.c_int]),

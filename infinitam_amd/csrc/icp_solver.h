@@ -11,6 +11,28 @@
 
 namespace itm {
 
+// The pose update of ITMDepthTracker::ApplyDelta + SetInvM + Coerce (Engine/ITMDepthTracker.cpp:114-143,190-192) for the step x of the active
+// parameters: the first-order motion I - [x_rot]x, x_trans applied on the left of the inverse pose, the result projected back onto
+// SE(3).  Shared with the weighted ICP tracker (wicp_solver.h), whose ApplyDelta is the same.
+inline void apply_first_order_step(se3::Rigid& pose, const double x[6], int mode) {
+  double rot[3] = {0, 0, 0}, trans[3] = {0, 0, 0};
+  if (mode == ITM_TRACKER_ITERATION_ROTATION) { rot[0] = x[0]; rot[1] = x[1]; rot[2] = x[2]; }
+  else if (mode == ITM_TRACKER_ITERATION_TRANSLATION) { trans[0] = x[0]; trans[1] = x[1]; trans[2] = x[2]; }
+  else { for (int i = 0; i < 3; ++i) { rot[i] = x[i]; trans[i] = x[3 + i]; } }
+  // first-order motion applied on the left of the inverse pose ...
+  se3::Rigid motion;
+  motion.R[0] = 1.0;     motion.R[1] = rot[2];  motion.R[2] = -rot[1];
+  motion.R[3] = -rot[2]; motion.R[4] = 1.0;     motion.R[5] = rot[0];
+  motion.R[6] = rot[1];  motion.R[7] = -rot[0]; motion.R[8] = 1.0;
+  for (int i = 0; i < 3; ++i) motion.t[i] = trans[i];
+  se3::Rigid inv, moved, back;
+  if (se3::invert(pose, inv)) {
+    moved = se3::compose(motion, inv);
+    // ... and the result, which is no longer a rigid motion, projected back onto SE(3)
+    if (se3::invert(moved, back)) pose = se3::exp(se3::log(back));
+  }
+}
+
 // Behaviour of ITMDepthTracker::TrackCamera (Engine/ITMDepthTracker.cpp:149-200): per hierarchy level, coarse to fine, up
 // to 2(l+1) iterations of { evaluate cost / gradient / Hessian at the current pose; if the cost rose or nothing was valid,
 // go back to the last accepted pose and multiply the damping by 10, else accept and divide it by 10; solve
@@ -49,22 +71,7 @@ struct IcpSolver {
     for (int i = 0; i < 36; ++i) A[i] = H[i];
     for (int i = 0; i < 6; ++i) A[7 * i] *= 1.0 + damping;
     se3::solve_spd(A, 6, n, g, x);
-    double rot[3] = {0, 0, 0}, trans[3] = {0, 0, 0};
-    if (mode == ITM_TRACKER_ITERATION_ROTATION) { rot[0] = x[0]; rot[1] = x[1]; rot[2] = x[2]; }
-    else if (mode == ITM_TRACKER_ITERATION_TRANSLATION) { trans[0] = x[0]; trans[1] = x[1]; trans[2] = x[2]; }
-    else { for (int i = 0; i < 3; ++i) { rot[i] = x[i]; trans[i] = x[3 + i]; } }
-    // first-order motion applied on the left of the inverse pose ...
-    se3::Rigid motion;
-    motion.R[0] = 1.0;     motion.R[1] = rot[2];  motion.R[2] = -rot[1];
-    motion.R[3] = -rot[2]; motion.R[4] = 1.0;     motion.R[5] = rot[0];
-    motion.R[6] = rot[1];  motion.R[7] = -rot[0]; motion.R[8] = 1.0;
-    for (int i = 0; i < 3; ++i) motion.t[i] = trans[i];
-    se3::Rigid inv, moved, back;
-    if (se3::invert(pose, inv)) {
-      moved = se3::compose(motion, inv);
-      // ... and the result, which is no longer a rigid motion, projected back onto SE(3)
-      if (se3::invert(moved, back)) pose = se3::exp(se3::log(back));
-    }
+    apply_first_order_step(pose, x, mode);
     double len = 0.0;
     for (int i = 0; i < 6; ++i) len += x[i] * x[i];
     return std::sqrt(len) / 6.0;

@@ -8,6 +8,9 @@
 //   ITMDepthTracker::TrackCamera & co. Engine/ITMDepthTracker.cpp:79-200
 //   ITMPose::SetParamsFromModelView / SetModelViewFromParams / Coerce   Objects/ITMPose.cpp:84-253,322-326
 //   ORUtils::Cholesky                  ORUtils/Cholesky.h
+//   weighted ICP (TRACKER_WICP): computePerPointGH_wICP  DeviceAgnostic/ITMWeightedICPTracker.h:10-107,
+//     ITMWeightedICPTracker_CPU::ComputeGandH  DeviceSpecific/CPU/ITMWeightedICPTracker_CPU.cpp:14-86,
+//     ITMWeightedICPTracker::PrepareForEvaluation / TrackCamera  Engine/ITMWeightedICPTracker.cpp:57-100,174-191 (host loop: wicp_solver.h)
 //
 // Device part: one lane per depth pixel computes its residual row (A, b) with the reference's float
 // operations; the 1 + 6 + 21 sums and the valid count are reduced per wave with DPP row shifts, one partial per
@@ -27,6 +30,7 @@
 #include "gh_reduce.h"
 #include "icp_solver.h"
 #include "se3.h"
+#include "wicp_solver.h"
 #include "wave_utils.h"
 
 namespace itm {
@@ -90,7 +94,14 @@ struct GHParams {
   float distThresh;
   int w, h, sceneW, sceneH;
   int tileH;                  // rows of a tile (gh_tiling)
+  const float* weight;        // weighted ICP: the view level's uncertainty image (sigmaZ pyramid level); unused by plain ICP
 };
+
+// Weighted ICP (ITMWeightedICPTracker_CPU::ComputeGandH, DeviceSpecific/CPU/ITMWeightedICPTracker_CPU.cpp:27,43): the weight of a
+// view pixel from its uncertainty sigma, in the CPU file's order of operations (the CUDA twin's 0.5f * minSigmaZ / sigma rounds
+// differently); sigma <= 0 -- no normal (-1) or a border pixel ComputeNormalAndWeights never wrote (0) -- weighs 0
+constexpr float kWicpMinSigmaZ = 0.0012f;
+__host__ __device__ inline float wicp_weight(float sigma) { return sigma > 0 ? kWicpMinSigmaZ / sigma * 0.5f + 0.5f : 0.0f; }
 
 
 #ifndef ITM_EXP_TRACKER_TRACE
@@ -172,8 +183,11 @@ __device__ inline bool gh_blend(const GHTaps& t, float px, float py, float4& r) 
   return true;
 }
 
-template <int MODE>
-__device__ inline void gh_row(const GHPixel& px, const GHTaps& tp, const GHTaps& tn, const GHParams& p, double acc[kGHValues], int& valid) {
+// WEIGHTED (computePerPointGH_wICP, DeviceAgnostic/ITMWeightedICPTracker.h:10-107): b from the unweighted normal, f += b b w w, then the
+// normal times w before A is formed -- nabla = sum w b A0, H = sum w^2 A0 A0^T; a pixel of weight 0 still counts as valid
+template <int MODE, bool WEIGHTED = false>
+__device__ inline void gh_row(const GHPixel& px, const GHTaps& tp, const GHTaps& tn, const GHParams& p, double acc[kGHValues], int& valid,
+                              float wgt = 0.0f) {
   constexpr int NP = (MODE == 3) ? 6 : 3;
   constexpr int NH = NP * (NP + 1) / 2;
   float vals[kGHValues];
@@ -188,6 +202,7 @@ __device__ inline void gh_row(const GHPixel& px, const GHTaps& tp, const GHTaps&
       float4 n;
       if (!gh_blend(tn, px.u, px.v, n)) n = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
       const float b = n.x * ex + n.y * ey + n.z * ez;
+      if constexpr (WEIGHTED) { n.x *= wgt; n.y *= wgt; n.z *= wgt; }
       float A[NP];
       if (MODE == 2) { A[0] = n.x; A[1] = n.y; A[2] = n.z; }
       else {
@@ -196,7 +211,7 @@ __device__ inline void gh_row(const GHPixel& px, const GHTaps& tp, const GHTaps&
         A[2] = +px.qy * n.x - px.qx * n.y;
         if constexpr (MODE == 3) { A[3] = n.x; A[4] = n.y; A[5] = n.z; }
       }
-      vals[0] = b * b;
+      vals[0] = WEIGHTED ? b * b * wgt * wgt : b * b;
       int k = 0;
 #pragma unroll
       for (int r = 0; r < NP; ++r) {
@@ -216,7 +231,7 @@ __device__ inline void gh_row(const GHPixel& px, const GHTaps& tp, const GHTaps&
 
 // The tiles blk, blk + nBlocks, ... of one workgroup, two at a time: every lane adds the residual rows of its pixels to `acc`
 // (double, in tile order) and counts them
-template <int MODE>
+template <int MODE, bool WEIGHTED = false>
 __device__ inline void gh_accumulate(const float* __restrict__ depth, const float4* __restrict__ pointsMap, const float4* __restrict__ normalsMap,
                                      const GHParams& p, int blk, int nBlocks, double acc[kGHValues], int& valid ITM_TT(, unsigned long long* tt = nullptr)) {
   const int tilesX = (p.w + 15) / 16, tiles = tilesX * ((p.h + p.tileH - 1) / p.tileH);
@@ -228,17 +243,23 @@ __device__ inline void gh_accumulate(const float* __restrict__ depth, const floa
     const int xB = (tileB % tilesX) * 16 + (threadIdx.x & 15), yB = (tileB / tilesX) * p.tileH + row;
     const GHPixel pa = gh_project(depth, p, xA, yA, xA < p.w && yA < p.h);
     const GHPixel pb = gh_project(depth, p, xB, yB, tileB < tiles && xB < p.w && yB < p.h);
+    // weighted ICP: the pixel's weight, one more coalesced load in flight with the map taps below
+    float wa = 0.0f, wb = 0.0f;
+    if constexpr (WEIGHTED) {
+      wa = wicp_weight(p.weight[pa.live ? xA + yA * p.w : 0]);
+      wb = wicp_weight(p.weight[pb.live ? xB + yB * p.w : 0]);
+    }
     ITM_TT(if (tt && tile == blk) { __builtin_amdgcn_s_waitcnt(0); tt[0] = __builtin_amdgcn_s_memrealtime(); })
     const GHTaps ta = gh_taps(pointsMap, pa, p.sceneW), na = gh_taps(normalsMap, pa, p.sceneW);
     const GHTaps tb = gh_taps(pointsMap, pb, p.sceneW), nb = gh_taps(normalsMap, pb, p.sceneW);
     ITM_TT(if (tt && tile == blk) { __builtin_amdgcn_s_waitcnt(0); tt[1] = __builtin_amdgcn_s_memrealtime(); })
-    gh_row<MODE>(pa, ta, na, p, acc, valid);
-    gh_row<MODE>(pb, tb, nb, p, acc, valid);
+    gh_row<MODE, WEIGHTED>(pa, ta, na, p, acc, valid, wa);
+    gh_row<MODE, WEIGHTED>(pb, tb, nb, p, acc, valid, wb);
   }
 }
 
 
-template <int MODE>
+template <int MODE, bool WEIGHTED = false>
 __global__ void __launch_bounds__(kGHThreads) gh_partial_kernel(const float* __restrict__ depth, const float4* __restrict__ pointsMap,
                                                         const float4* __restrict__ normalsMap, GHParams p, GHBlockRecord* __restrict__ hostRec, unsigned int seq) {
   __shared__ double lds[kGHWaves][kGHValues];
@@ -247,7 +268,7 @@ __global__ void __launch_bounds__(kGHThreads) gh_partial_kernel(const float* __r
 #pragma unroll
   for (int i = 0; i < kGHValues; ++i) acc[i] = 0.0;
   int valid = 0;
-  gh_accumulate<MODE>(depth, pointsMap, normalsMap, p, blockIdx.x, gridDim.x, acc, valid);
+  gh_accumulate<MODE, WEIGHTED>(depth, pointsMap, normalsMap, p, blockIdx.x, gridDim.x, acc, valid);
   const int blk = blockIdx.x;
   double mine; int cnt;
   gh_block_reduce<MODE>(acc, valid, lds, ldsCount, mine, cnt);
@@ -443,6 +464,7 @@ struct itm_tracker {
   std::mutex mu;
   itm::GHChannel ch;                      // pinned host records of every evaluation (a session's coarse levels included)
   std::vector<float*> pyramid; std::vector<size_t> pyramidBytes;
+  std::vector<float*> weightPyramid; std::vector<size_t> weightPyramidBytes;   // weighted ICP: the sigmaZ pyramid (allocated on first use)
   int sessionUsable = -1;                 // -1 not probed yet, 0 launch per evaluation, 1 resident evaluation kernel
   int sessionFallbacks = 0;
   int debugEvaluations = 0;
@@ -478,6 +500,8 @@ static void tracker_release(itm_tracker* t) {
   t->sessionOpen = false;
   for (float* q : t->pyramid) (void)hipFree(q);
   t->pyramid.clear(); t->pyramidBytes.clear();
+  for (float* q : t->weightPyramid) (void)hipFree(q);
+  t->weightPyramid.clear(); t->weightPyramidBytes.clear();
 }
 
 // records for `blocks` workgroups on the current device
@@ -493,6 +517,7 @@ static GHParams gh_params(int w, int h, const float* viewIntr, int sceneW, int s
   p.vfx = viewIntr[0]; p.vfy = viewIntr[1]; p.vcx = viewIntr[2]; p.vcy = viewIntr[3];
   p.sfx = sceneIntr[0]; p.sfy = sceneIntr[1]; p.scx = sceneIntr[2]; p.scy = sceneIntr[3];
   p.distThresh = distThresh; p.w = w; p.h = h; p.sceneW = sceneW; p.sceneH = sceneH; p.tileH = tileH;
+  p.weight = nullptr;
   return p;
 }
 
@@ -513,7 +538,7 @@ static itm_tracker* thread_tracker() {
 
 static int compute_g_and_h(itm_tracker* trk, const float* depth, int w, int h, const float* viewIntr, const float* pointsMap, const float* normalsMap,
                            int sceneW, int sceneH, const float* sceneIntr, const float* approxInvPose, const float* scenePose,
-                           float distThresh, int iterationType, itm_tracker_gh* out, hipStream_t st) {
+                           float distThresh, int iterationType, itm_tracker_gh* out, hipStream_t st, const float* weight = nullptr) {
   memset(out, 0, sizeof *out);
   if (iterationType == ITM_TRACKER_ITERATION_NONE) return ITM_OK;
   if (iterationType < 1 || iterationType > 3) return set_error(ITM_ERR_INVALID, "bad iteration type");
@@ -524,11 +549,16 @@ static int compute_g_and_h(itm_tracker* trk, const float* depth, int w, int h, c
   const size_t blocks = grid.x;
   int rc = tracker_reserve(trk, blocks);
   if (rc) return rc;
-  const GHParams p = gh_params(w, h, viewIntr, sceneW, sceneH, sceneIntr, approxInvPose, scenePose, distThresh, tileH);
+  GHParams p = gh_params(w, h, viewIntr, sceneW, sceneH, sceneIntr, approxInvPose, scenePose, distThresh, tileH);
+  p.weight = weight;
   const float4* pm = (const float4*)pointsMap; const float4* nm = (const float4*)normalsMap;
   const int np = (iterationType == ITM_TRACKER_ITERATION_BOTH) ? 6 : 3;
   const unsigned int seq = trk->ch.begin();
-  if (iterationType == 1) gh_partial_kernel<1><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, trk->ch.recDev, seq);
+  if (weight) {          // weighted ICP (ITMWeightedICPTracker_CPU::ComputeGandH): the same tiles, grid and order of the additions
+    if (iterationType == 1) gh_partial_kernel<1, true><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, trk->ch.recDev, seq);
+    else if (iterationType == 2) gh_partial_kernel<2, true><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, trk->ch.recDev, seq);
+    else gh_partial_kernel<3, true><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, trk->ch.recDev, seq);
+  } else if (iterationType == 1) gh_partial_kernel<1><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, trk->ch.recDev, seq);
   else if (iterationType == 2) gh_partial_kernel<2><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, trk->ch.recDev, seq);
   else gh_partial_kernel<3><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, trk->ch.recDev, seq);
   ITM_LAUNCH_CHECK();
@@ -703,35 +733,49 @@ static int session_g_and_h(itm_tracker* trk, const float* depth, int w, int h, c
 // FilterSubsampleWithHoles pyramid of the view's depth image in the tracker's own buffers (PrepareForEvaluation)
 struct DepthLevel { const float* depth; int w, h; float intr[4]; };
 
-static int build_pyramid(itm_tracker* trk, const itm_view* view, int levels, std::vector<DepthLevel>& out, hipStream_t st) {
-  out.resize(levels);
-  out[0].depth = view->depth; out[0].w = view->w; out[0].h = view->h;
-  for (int k = 0; k < 4; ++k) out[0].intr[k] = view->intr_d[k];
-  if ((int)trk->pyramid.size() < levels) { trk->pyramid.resize(levels, nullptr); trk->pyramidBytes.resize(levels, 0); }
+// FilterSubsampleWithHoles levels 1 .. levels-1 of `src` (w x h) into `bufs` (grown as needed; bufs[0] is not used): one launch of
+// pyramid_kernel for up to four coarser levels, a launch per level otherwise.  lv[i]: level i (lv[0] = src).
+static int subsample_pyramid(const float* src, int w, int h, int levels, std::vector<float*>& bufs, std::vector<size_t>& bufBytes,
+                             std::vector<const float*>& lv, hipStream_t st) {
+  lv.assign(levels, src);
+  if ((int)bufs.size() < levels) { bufs.resize(levels, nullptr); bufBytes.resize(levels, 0); }
+  std::vector<int> lw(levels), lh(levels);
+  lw[0] = w; lh[0] = h;
   for (int i = 1; i < levels; ++i) {
-    DepthLevel& L = out[i];
-    L.w = out[i - 1].w / 2; L.h = out[i - 1].h / 2;
-    if (L.w < 1 || L.h < 1) return set_error(ITM_ERR_INVALID, "image too small for the hierarchy");
-    const size_t bytes = (size_t)L.w * L.h * 4;
-    if (trk->pyramidBytes[i] < bytes) {
-      (void)hipFree(trk->pyramid[i]); trk->pyramid[i] = nullptr; trk->pyramidBytes[i] = 0;
-      ITM_HIP(hipMalloc((void**)&trk->pyramid[i], bytes));
-      trk->pyramidBytes[i] = bytes;
+    lw[i] = lw[i - 1] / 2; lh[i] = lh[i - 1] / 2;
+    if (lw[i] < 1 || lh[i] < 1) return set_error(ITM_ERR_INVALID, "image too small for the hierarchy");
+    const size_t bytes = (size_t)lw[i] * lh[i] * 4;
+    if (bufBytes[i] < bytes) {
+      (void)hipFree(bufs[i]); bufs[i] = nullptr; bufBytes[i] = 0;
+      ITM_HIP(hipMalloc((void**)&bufs[i], bytes));
+      bufBytes[i] = bytes;
     }
-    L.depth = trk->pyramid[i];
-    for (int k = 0; k < 4; ++k) L.intr[k] = out[i - 1].intr[k] * 0.5f;
+    lv[i] = bufs[i];
   }
   if (levels >= 2 && levels <= 5 && !g_debug_tracker_launch_per_evaluation) {
     PyramidLevels P;
     memset(&P, 0, sizeof P);
     P.levels = levels - 1;
-    for (int i = 0; i < levels; ++i) { P.w[i] = out[i].w; P.h[i] = out[i].h; if (i > 0) P.out[i - 1] = trk->pyramid[i]; }
-    pyramid_kernel<<<dim3((view->w + 15) / 16, (view->h + 15) / 16), 256, 0, st>>>(view->depth, P);
+    for (int i = 0; i < levels; ++i) { P.w[i] = lw[i]; P.h[i] = lh[i]; if (i > 0) P.out[i - 1] = bufs[i]; }
+    pyramid_kernel<<<dim3((w + 15) / 16, (h + 15) / 16), 256, 0, st>>>(src, P);
   } else {
     for (int i = 1; i < levels; ++i)
-      subsample_holes_kernel<<<dim3((out[i].w + 15) / 16, (out[i].h + 15) / 16), 256, 0, st>>>(out[i - 1].depth, out[i - 1].w, trk->pyramid[i], out[i].w, out[i].h);
+      subsample_holes_kernel<<<dim3((lw[i] + 15) / 16, (lh[i] + 15) / 16), 256, 0, st>>>(lv[i - 1], lw[i - 1], bufs[i], lw[i], lh[i]);
   }
   ITM_LAUNCH_CHECK();
+  return ITM_OK;
+}
+
+static int build_pyramid(itm_tracker* trk, const itm_view* view, int levels, std::vector<DepthLevel>& out, hipStream_t st) {
+  out.resize(levels);
+  std::vector<const float*> lv;
+  const int rc = subsample_pyramid(view->depth, view->w, view->h, levels, trk->pyramid, trk->pyramidBytes, lv, st);
+  if (rc) return rc;
+  for (int i = 0; i < levels; ++i) {
+    out[i].depth = lv[i];
+    out[i].w = i ? out[i - 1].w / 2 : view->w; out[i].h = i ? out[i - 1].h / 2 : view->h;
+    for (int k = 0; k < 4; ++k) out[i].intr[k] = i ? out[i - 1].intr[k] * 0.5f : view->intr_d[k];
+  }
   return ITM_OK;
 }
 
@@ -791,6 +835,25 @@ static int track_camera(itm_tracker* trk, const itm_tracker_config* cfg, const i
   return rc;
 }
 
+// ITMWeightedICPTracker::TrackCamera (Engine/ITMWeightedICPTracker.cpp:57-100,174-191): the depth pyramid and the sigmaZ pyramid
+// (PrepareForEvaluation: FilterSubsampleWithHoles of both, one launch each), the scene maps at level 0 with the depth intrinsics, one
+// weighted evaluation per iteration (one launch each: the resident session kernel serves plain ICP only), the loop of wicp_solver.h
+static int weighted_track_camera(itm_tracker* trk, const itm_tracker_config* cfg, const itm_view* view, const float* sigmaZ, const float* pointsMap,
+                                 const float* normalsMap, const float scenePose[16], float M_d_out[16], hipStream_t st) {
+  const int levels = cfg->noHierarchyLevels;
+  if (levels < 1 || levels > 8) return set_error(ITM_ERR_INVALID, "noHierarchyLevels must be 1..8");
+  int rc = tracker_reserve(trk, 1);
+  if (rc) return rc;
+  std::vector<DepthLevel> pyr;
+  std::vector<const float*> weights;
+  if ((rc = build_pyramid(trk, view, levels, pyr, st))) return rc;
+  if ((rc = subsample_pyramid(sigmaZ, view->w, view->h, levels, trk->weightPyramid, trk->weightPyramidBytes, weights, st))) return rc;
+  return wicp_track(cfg, view->M_d, M_d_out, [&](int level, int mode, const float invPose[16], float distThresh, itm_tracker_gh* e) {
+    return compute_g_and_h(trk, pyr[level].depth, pyr[level].w, pyr[level].h, pyr[level].intr, pointsMap, normalsMap, view->w, view->h,
+                           pyr[0].intr, invPose, scenePose, distThresh, mode, e, st, weights[level]);
+  });
+}
+
 }  // namespace itm
 
 using namespace itm;
@@ -825,6 +888,14 @@ int itm_debug_icp_track(const itm_tracker_config* cfg, const float M_d[16], itm_
   });
 }
 
+int itm_debug_wicp_track(const itm_tracker_config* cfg, const float M_d[16], itm_icp_evaluate_fn evaluate, void* user, float M_d_out[16]) {
+  if (!cfg || !M_d || !evaluate || !M_d_out) return set_error(ITM_ERR_INVALID, "null argument");
+  if (cfg->noHierarchyLevels < 1 || cfg->noHierarchyLevels > 8) return set_error(ITM_ERR_INVALID, "noHierarchyLevels must be 1..8");
+  return wicp_track(cfg, M_d, M_d_out, [&](int level, int mode, const float invPose[16], float distThresh, itm_tracker_gh* e) {
+    return evaluate(user, level, mode, invPose, distThresh, e);
+  });
+}
+
 int itm_tracker_create(itm_tracker** out) {
   if (!out) return set_error(ITM_ERR_INVALID, "null argument");
   *out = new (std::nothrow) itm_tracker();
@@ -853,6 +924,23 @@ int itm_tracker_track_camera(itm_tracker* t, const itm_tracker_config* cfg, cons
   if (!t || !cfg || !view || !view->depth || !pointsMap || !normalsMap || !scenePose || !M_d_out) return set_error(ITM_ERR_INVALID, "null argument");
   std::lock_guard<std::mutex> lock(t->mu);
   return track_camera(t, cfg, view, pointsMap, normalsMap, scenePose, M_d_out, as_stream(stream));
+}
+
+int itm_tracker_weighted_g_and_h(itm_tracker* t, const float* depth, const float* weight, int w, int h, const float viewIntr[4], const float* pointsMap,
+                                 const float* normalsMap, int sceneW, int sceneH, const float sceneIntr[4], const float approxInvPose[16],
+                                 const float scenePose[16], float distThresh, int iterationType, itm_tracker_gh* out, itm_stream stream) {
+  if (!t || !depth || !weight || !viewIntr || !pointsMap || !normalsMap || !sceneIntr || !approxInvPose || !scenePose || !out || w <= 0 || h <= 0)
+    return set_error(ITM_ERR_INVALID, "bad argument");
+  std::lock_guard<std::mutex> lock(t->mu);
+  return compute_g_and_h(t, depth, w, h, viewIntr, pointsMap, normalsMap, sceneW, sceneH, sceneIntr, approxInvPose, scenePose, distThresh,
+                         iterationType, out, as_stream(stream), weight);
+}
+
+int itm_tracker_weighted_track_camera(itm_tracker* t, const itm_tracker_config* cfg, const itm_view* view, const float* sigmaZ, const float* pointsMap,
+                                      const float* normalsMap, const float scenePose[16], float M_d_out[16], itm_stream stream) {
+  if (!t || !cfg || !view || !view->depth || !sigmaZ || !pointsMap || !normalsMap || !scenePose || !M_d_out) return set_error(ITM_ERR_INVALID, "null argument");
+  std::lock_guard<std::mutex> lock(t->mu);
+  return weighted_track_camera(t, cfg, view, sigmaZ, pointsMap, normalsMap, scenePose, M_d_out, as_stream(stream));
 }
 
 }  // extern "C"
