@@ -13,7 +13,10 @@ The timed region is exactly --steps frames between two barriers; `ms_per_step` i
 --min-measured-s > 0 (off by default) is a region of --steps < 100 frames repeated until that much has been measured;
 `value` / `ms_per_step` are then those of the MEDIAN repetition, `repetitions` says how many there were.  --dump-outputs DIR
 writes what the last timed frame computed (ICP maps, counters, a seeded sample of the voxel pool) as .npy files.
-The roofline kernel is never timed inside the timed region: one extra, untimed repetition brackets EVERY launch of it
+A plain run does only that: set-up, warm-up, the timed region, --dump-outputs and the line.  Everything else it can measure or
+check runs only with --full, after the timed region: the kernel brackets and roofline, the exchange's cost and gathered table,
+the secondary legs, the exploring camera, the CPU baseline with its parity checks and the other configurations as child runs.
+The roofline kernel is never timed inside the timed region: with --full, one extra, untimed repetition brackets EVERY launch of it
 (and of the integration and the visible-list launch) with HIP events, at least 64 samples.
 
 Workloads (--config, names in config.workload):
@@ -72,6 +75,10 @@ def parse():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", type=int, default=2, choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure and check everything beside the headline figure (kernel brackets and roofline, "
+                         "exchange cost and table, secondary legs, exploring camera, CPU baseline and parity checks, other configurations); "
+                         "off: set-up, warm-up, the timed steps, --dump-outputs and the line, nothing else")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-frames", type=int, default=0, help="frames of the CPU baseline sample (0 = per-config default)")
     ap.add_argument("--no-exchange", action="store_true", help="skip the visible-list all-gather at N>1")
@@ -85,7 +92,7 @@ def parse():
     ap.add_argument("--no-host-threads", dest="host_threads", action="store_false",
                     help="feed the k streams of --streams-per-gpu from one host thread instead of one thread per stream")
     ap.add_argument("--timer-frames", type=int, default=0,
-                    help="frames of the extra, untimed repetition in which every launch of the roofline kernel is bracketed by HIP events (0 = max(--steps, 64))")
+                    help="frames of the extra, untimed repetition of --full in which every launch of the roofline kernel is bracketed by HIP events (0 = max(--steps, 64))")
     ap.add_argument("--frame-call", choices=["four", "process_frame", "ahead"], default="four",
                     help="how the timed region issues a frame: the reference's four engine calls (default, the headline), itm_process_frame, or "
                          "itm_process_frame_ahead (a marked line: the next frame's pose is handed over before this frame is done)")
@@ -101,9 +108,9 @@ def parse():
                     help="X,Y,Z metres added to every camera position (scene and trajectory translated together: same depth images, "
                          "block coordinates far from the world origin)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the child runs of BASELINE configs[2] (dense 512^3) and configs[4] (1280x960 colour) that the default single-GPU run appends as `other_configs`")
+                    help="skip the child runs of BASELINE configs[2] (dense 512^3) and configs[4] (1280x960 colour) that a --full single-GPU run appends as `other_configs`")
     ap.add_argument("--no-extra-legs", action="store_true",
-                    help="skip the secondary measurements of the default run (PCIe-inclusive rate, table-walk ray cast, stream-copy peak)")
+                    help="skip the secondary measurements of a --full run (PCIe-inclusive rate, table-walk ray cast, stream-copy peak)")
     ap.add_argument("--lib", default=None, help="alternative shared library exporting the same C-ABI (tests: a host-memory backend)")
     ap.add_argument("--lib-prefix", default="itm_")
     ap.add_argument("--debug-keys", default="", help="comma-separated itm_debug_set keys switched on for the run (A/B of a replaced code path; a marked line, not the headline)")
@@ -582,7 +589,7 @@ def worker(args) -> int:
     # ---- the roofline kernel: one extra, UNTIMED repetition with an event pair around EVERY launch of it (and of the integration and
     # the visible-list launch), then empty brackets on the same stream for what an event pair itself adds to an interval ----
     kernel_times = None
-    if rank == 0 and product and on_gpu:
+    if args.full and rank == 0 and product and on_gpu:
         s0 = streams[0]
         nt = args.timer_frames if args.timer_frames > 0 else max(args.steps, 64)
         timed_set = sorted({timed_kernel, TK["request"], TK["integrate"], TK["visible_list"], TK["raycast"]} if wl["index"] == "hash" else {timed_kernel, TK["raycast"]})
@@ -604,12 +611,12 @@ def worker(args) -> int:
         sync()
         kernel_times = s0.scene.profile_read(reset=True)
         s0.scene.profile_enable(0)
-    if world > 1:
+    if args.full and world > 1:
         barrier()
 
     # what the exchange costs THIS run: the same frames once more without it (every rank, no collective involved)
     exchange_cost = None
-    if exchange and (on_gpu or world > 1):
+    if args.full and exchange and (on_gpu or world > 1):
         n3 = min(args.steps, 200)
         was, exchange = exchange, False
         run(0, min(args.warmup, 20)); sync()
@@ -626,7 +633,7 @@ def worker(args) -> int:
 
     # what the exchange delivered: rank 0 decodes the newest gathered table -- one block per rank: pose + visible ids
     exchange_table = None
-    if exchange and exs:
+    if args.full and exchange and exs:
         drain()
         try:
             tab = exs[0].table()
@@ -653,9 +660,9 @@ def worker(args) -> int:
     if rank == 0 and product and kernel_times is not None:
         roofline = read_roofline(args.config, wl, kernel_times, counters, streams[0].scene)
 
-    # ---- secondary figures of the default single-GPU run (after the timed region; none of them is `value`) --------------------
+    # ---- secondary figures of a --full single-GPU run (after the timed region; none of them is `value`) --------------------
     extra = {}
-    if rank == 0 and world == 1 and product and k_streams == 1 and on_gpu and not exchange and not args.no_extra_legs and not args.raw_depth:
+    if args.full and rank == 0 and world == 1 and product and k_streams == 1 and on_gpu and not exchange and not args.no_extra_legs and not args.raw_depth:
         s0 = streams[0]
         n2 = max(args.steps, 100)
 
@@ -753,7 +760,7 @@ def worker(args) -> int:
     # (4) an EXPLORING camera: the headline trajectory is 100-periodic, so from frame 100 on nothing is allocated; here the camera of the
     #     parity trajectory (1 cm per frame along x, never turning back) starts on a reset scene -- every frame requests and allocates
     #     blocks, the allocation sweep of _CPU.cpp:175-227 and the visible-list re-tests have work in every frame
-    if (rank == 0 and world == 1 and product and k_streams == 1 and on_gpu and not exchange and not args.no_extra_legs and not args.raw_depth
+    if (args.full and rank == 0 and world == 1 and product and k_streams == 1 and on_gpu and not exchange and not args.no_extra_legs and not args.raw_depth
             and args.config == 2 and mode["call"] == "four"):
         extra["exploring"] = run_exploring(streams[0], be, capi, synth, torch, wl, issue, sync, timed_set=("request", "visible_list", "integrate", "raycast"))
     if rank == 0 and world == 1 and product and on_gpu and roofline is not None and not args.no_extra_legs:
@@ -767,15 +774,15 @@ def worker(args) -> int:
                 o["frac_of_measured_copy_peak"] = round(o["achieved"] / pm["copy_GBs"], 4)
 
     cpu_baseline, parity_check = None, None
-    if rank == 0 and world == 1 and product and k_streams == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and product and k_streams == 1 and not args.no_cpu_baseline:
         cpu_baseline, parity_check = run_cpu_baseline(args.config, wl, args.cpu_frames, on_gpu)
         if "exploring" in extra and on_gpu:
             extra["exploring"].update(run_exploring_check(wl))
 
     # the other single-GPU configurations of BASELINE.json, each as its own bench.py process (its own scene, its own parity check and
-    # CPU sample), after everything of this run has been measured: the driver's ONE line then carries all three
+    # CPU sample), after everything of this run has been measured: the ONE line of --full then carries all three
     other_configs = None
-    if (rank == 0 and world == 1 and product and k_streams == 1 and on_gpu and not args.no_extra_legs and not args.no_other_configs
+    if (args.full and rank == 0 and world == 1 and product and k_streams == 1 and on_gpu and not args.no_extra_legs and not args.no_other_configs
             and not args.raw_depth and args.config == 2 and not args.debug_keys):
         sync()
         other_configs = {f"config{c}": run_other_config(c, args) for c in (3, 5)}
@@ -811,7 +818,8 @@ def worker(args) -> int:
                                       "ahead": "itm_process_frame_ahead (NOT the headline: the next frame's pose is handed over before this frame is done)"}[mode["call"]],
                        "input": ("16-bit raw depth from pinned host memory: H2D + itm_update_view inside the timed region" if args.raw_depth
                                  else "float depth frames resident in HBM"),
-                       "timing_note": "no event timers inside the timed region; kernels are timed in one extra, untimed repetition (roofline.launches_timed)",
+                       "timing_note": "no event timers inside the timed region; with --full, kernels are timed in one extra, untimed repetition (roofline.launches_timed)",
+                       "full": args.full,
                        **({"debug_keys": args.debug_keys} if args.debug_keys else {}),
                        "backend": be.version()},
             "roofline": roofline, "cpu_baseline": cpu_baseline, "parity_check": parity_check,
@@ -874,7 +882,7 @@ def dump_outputs(directory, s, capi):
 
 
 # -------------------------------------------------------------------------------------------------------------
-# secondary legs of the default single-GPU run
+# secondary legs of a --full single-GPU run
 # -------------------------------------------------------------------------------------------------------------
 EXPLORING_FRAMES = 200
 
@@ -965,7 +973,7 @@ def run_other_config(c, args):
     """`bench.py --config c` as a child process (this process's GPU work is done and synchronised; the child is started, never exec'd
     into): the same measurement the flag gives on its own -- timed region, kernel brackets, parity check against the oracle, CPU sample --
     reduced to the figures a reader of the driver's line needs."""
-    cmd = [sys.executable, os.path.abspath(__file__), "--config", str(c), "--gpus", "1", "--steps", "100", "--warmup", "20", "--no-extra-legs", "--no-other-configs"]
+    cmd = [sys.executable, os.path.abspath(__file__), "--config", str(c), "--gpus", "1", "--steps", "100", "--warmup", "20", "--full", "--no-extra-legs", "--no-other-configs"]
     if args.no_cpu_baseline:
         cmd.append("--no-cpu-baseline")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "ITM_BENCH_SPAWNED")}
@@ -989,7 +997,7 @@ def run_other_config(c, args):
            "cpu_baseline": ({k: cb.get(k) for k in ("value", "unit", "cores", "kind", "sample")} | ({"all_cores": cb["all_cores"]} if "all_cores" in cb else {})) if cb else None,
            "visible_blocks_last_frame": d["config"].get("visible_blocks_last_frame"),
            "child_wall_s": round(time.perf_counter() - t0, 1),
-           "how": "python bench.py --config %d --steps 100 --warmup 20 --no-extra-legs, run as a child of this process after its own measurements" % c}
+           "how": "python bench.py --config %d --steps 100 --warmup 20 --full --no-extra-legs, run as a child of this process after its own measurements" % c}
     return out
 
 

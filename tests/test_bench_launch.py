@@ -10,6 +10,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 import itm_testlib as T
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -51,11 +53,25 @@ def test_bench_single_rank_line():
     assert out["n_gpus"] == 1 and out["config"]["streams"] == 1
 
 
+def test_bench_plain_run_measures_the_exchange_only_with_full():
+    """A plain run does set-up, warm-up, the timed steps and the line; the exchange's decoded table (and, on a GPU or with several ranks,
+    its cost: the frames once more without it) comes only with --full."""
+    res = _run(["--steps", "2", "--warmup", "1", "--force-exchange"])
+    assert res.returncode == 0, res.stderr[-2000:]
+    cfg = json.loads(res.stdout.strip().splitlines()[-1])["config"]
+    assert cfg["full"] is False and cfg["exchange_cost_measured"] is None and cfg["exchange_table"] is None
+    res = _run(["--steps", "2", "--warmup", "1", "--force-exchange", "--full"])
+    assert res.returncode == 0, res.stderr[-2000:]
+    cfg = json.loads(res.stdout.strip().splitlines()[-1])["config"]
+    assert cfg["full"] is True
+    assert cfg["exchange_table"]["blocks"] == 1                  # (one rank: one record in the table)
+
+
 def test_bench_eight_ranks_on_host_memory():
     """World 8 -- the size the driver's scaling run ends with -- on the host-memory backend: eight rank processes, gloo, a collective every
     second frame, every rank on its own share of the host cores; rank 0's line names eight GPUs' worth of streams and the gathered
     table decodes into eight blocks whose cameras are the eight streams' (0.05 g m apart in y)."""
-    res = _run(["--gpus", "8", "--steps", "4", "--warmup", "2", "--exchange-batch", "2"], timeout=900)
+    res = _run(["--gpus", "8", "--steps", "4", "--warmup", "2", "--exchange-batch", "2", "--full"], timeout=900)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, res.stdout
@@ -114,3 +130,21 @@ def test_bench_times_exactly_steps_and_dumps_the_last_frame(tmp_path):
     assert a["icp_points"].shape == (480, 640, 4) and np.isfinite(a["icp_points"]).any()
     assert a["counters"][2] > 1000                       # visible blocks of the last frame
     assert set(a) == set(b) and all(np.array_equal(a[k], b[k], equal_nan=True) for k in a)
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_of_the_product_is_the_timed_region_alone():
+    """The product's plain line: the headline fields, and none of the figures that --full measures after the timed region."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE")}
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"],
+                         capture_output=True, text=True, timeout=600, env=env)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, res.stdout
+    out = json.loads(lines[0])
+    assert out["metric"] == "fused depth frames/sec (640x480, hash TSDF)" and out["unit"] == "frames/s" and out["higher_is_better"] is True
+    assert out["dtype"] == "f32" and out["steps"] == 20 and out["warmup"] == 5 and out["value"] > 0 and out["ms_per_step"] > 0
+    assert out["data"] == "synthetic" and out["config"]["full"] is False and out["config"]["visible_blocks_last_frame"] > 5000
+    assert out["roofline"] is None and out["cpu_baseline"] is None and out["parity_check"] is None
+    assert not {"other_configs", "exploring", "process_frame_entry_point", "with_lookahead", "with_h2d_raw_depth", "table_walk_fallback",
+                "paged_mirror"} & set(out)

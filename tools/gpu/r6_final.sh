@@ -9,9 +9,9 @@ if [ -z "$SKIP_TESTS" ]; then
   ITM_MIRROR=paged timeout 1500 python -m pytest tests/test_hip_parity.py tests/test_random_stress.py tests/test_accel_origin.py tests/test_swapping.py tests/test_engine_api.py tests/test_golden.py tests/test_frame_ahead.py tests/test_deferred_fusion.py -m gpu -q > $O/pytest_gpu_paged.log 2>&1; grep -E "passed|failed|FAILED" $O/pytest_gpu_paged.log | tail -3
   timeout 600 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
 fi
-timeout 1200 python bench.py > $O/bench_default.json 2>$O/bench_default.err; echo "bench default rc $?"
-timeout 1200 python bench.py --steps 20 --warmup 5 > $O/bench_driver_like.json 2>$O/bench_driver_like.err; echo "bench driver-like rc $?"
-B="timeout 600 python bench.py --steps 400 --warmup 40 --no-cpu-baseline --no-extra-legs"
+timeout 1200 python bench.py --full > $O/bench_default.json 2>$O/bench_default.err; echo "bench default rc $?"
+timeout 1200 python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_like.json 2>$O/bench_driver_like.err; echo "bench driver-like rc $?"
+B="timeout 600 python bench.py --full --steps 400 --warmup 40 --no-cpu-baseline --no-extra-legs"
 $B --config 3 > $O/bench_c3.json 2>$O/e.err
 $B --config 5 > $O/bench_c5.json 2>$O/e.err
 if [ -z "$SKIP_LEGS" ]; then

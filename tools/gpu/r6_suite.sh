@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/../.."
 O=gpurun_out/r6suite; rm -rf $O; mkdir -p $O
 timeout 3000 python -m pytest tests -m gpu -q -x > $O/pytest.log 2>&1; tail -5 $O/pytest.log
-B="python bench.py --no-cpu-baseline --no-extra-legs --steps 400 --warmup 40"
+B="python bench.py --full --no-cpu-baseline --no-extra-legs --steps 400 --warmup 40"
 for rep in 1 2; do
   $B > $O/c2_bits_default_$rep.json 2>$O/e.err
   ITM_MIRROR_BITS=8 $B > $O/c2_bits8_$rep.json 2>$O/e.err
