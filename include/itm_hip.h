@@ -577,6 +577,28 @@ int ITM_FN(mesh_download)(const itm_mesh* mesh, float* dst_host, uint32_t capaci
 /* ITMMesh::WriteOBJ (Objects/ITMMesh.h:34-62) and ITMMesh::WriteSTL (:64-110), byte-identical files */
 int ITM_FN(mesh_write_obj)(const itm_mesh* mesh, const char* path, itm_stream stream);
 int ITM_FN(mesh_write_stl)(const itm_mesh* mesh, const char* path, itm_stream stream);
+/* Vertex attributes of the triangles the last itm_mesh_scene left in the buffer (the reference's ITMMesh has none; the two per-point
+ * functions are the reference's).  For every vertex v, in buffer order (triangle i: p0, p1, p2), at p = v / voxelSize (three IEEE
+ * divisions; a function of the stored vertex alone, so equal positions get equal attributes):
+ *   ITM_MESH_NORMALS  g = computeSingleNormalFromSDF(p) (DeviceAgnostic/ITMRepresentationAccess.h:224-337), n = g * (1 / sqrt(g.g)),
+ *                     (0, 0, 0) where the length is zero or n is not finite; n points from the surface into free space.
+ *   ITM_MESH_COLOURS  readFromSDF_color4u_interpolated(p) (:187-222) converted as drawPixelColour does
+ *                     (DeviceAgnostic/ITMVisualisationEngine.h:270-279): (uchar)(c * 255.0f) per channel, alpha 255.  Scenes whose
+ *                     voxel type stores no colour: ITM_ERR_INVALID.
+ * `what` is one of them or both (further calls add to what is current).  itm_mesh_scene makes the attributes stale; their buffers
+ * are allocated by the first call that needs them.  Dense scenes: an empty mesh, empty attributes. */
+#define ITM_MESH_NORMALS 1
+#define ITM_MESH_COLOURS 2
+int ITM_FN(mesh_attributes)(const itm_scene* scene, itm_mesh* mesh, int what, itm_stream stream);
+/* copies the attributes of min(noTotalTriangles, capacity) triangles to host memory: normals_host 3 vertices x float[3] per triangle,
+ * colours_host 3 vertices x {r, g, b, 255} per triangle; either may be NULL.  A non-NULL pointer whose attribute is stale or was
+ * never computed: ITM_ERR_INVALID.  Synchronises `stream`. */
+int ITM_FN(mesh_download_attributes)(const itm_mesh* mesh, float* normals_host, uint8_t* colours_host, uint32_t capacityTriangles,
+                                     uint32_t* noTotalTriangles, itm_stream stream);
+/* PLY, binary_little_endian 1.0: 3 vertices per triangle in buffer order -- float x, y, z, then float nx, ny, nz if the normals are
+ * current, then uchar red, green, blue if the colours are -- and one face {3, 3i + 2, 3i + 1, 3i} per triangle (the winding of
+ * ITMMesh::WriteOBJ, Objects/ITMMesh.h:34-62).  With neither attribute current the file holds positions only. */
+int ITM_FN(mesh_write_ply)(const itm_mesh* mesh, const char* path, itm_stream stream);
 
 /* ---- multi-stream exchange (BASELINE configs[3]) ------------------------------------------------------------------
  * One depth stream per GPU; fusion needs no collective.  Per frame every rank publishes the record of itm_export_visible_record

@@ -593,6 +593,7 @@ class ITMMainEngine_HIP {
   ITMView view;
   void *depthBuf = nullptr, *scratchBuf = nullptr, *normalBuf = nullptr, *sigmaBuf = nullptr, *pointsBuf = nullptr, *coloursBuf = nullptr;
   bool fusionActive = true, mainProcessingActive = true;
+  itm_mesh* exportMesh = nullptr;      // created by the first SaveSceneTo* call
 
  public:
   // calibType / c0 / c1: ITMDisparityCalib (0 = TRAFO_KINECT, 1 = TRAFO_AFFINE); sizes as ITMMainEngine's imgSize_rgb / imgSize_d
@@ -637,6 +638,7 @@ class ITMMainEngine_HIP {
     trackingController = new ITMTrackingController_HIP<TVoxel, TIndex>(tracker, &visualisationEngine, &settings);
   }
   ~ITMMainEngine_HIP() {
+    itm_mesh_destroy(exportMesh);
     delete renderState_live; delete trackingController; delete tracker; delete depthTracker; delete colourTracker; delete renTracker; delete wicpTracker; delete viewBuilder;
     for (void* p : {depthBuf, scratchBuf, normalBuf, sigmaBuf, pointsBuf, coloursBuf}) itm_dev_free(p);
   }
@@ -697,9 +699,30 @@ class ITMMainEngine_HIP {
   void turnOffIntegration() { fusionActive = false; }
   void turnOnMainProcessing() { mainProcessingActive = true; }
   void turnOffMainProcessing() { mainProcessingActive = false; }
+
+  // ITMMainEngine::SaveSceneToMesh (Engine/ITMMainEngine.cpp:104-109): meshes the scene and writes it as binary STL
+  void SaveSceneToMesh(const char* fileName) {
+    MeshForExport(0);
+    check(itm_mesh_write_stl(exportMesh, fileName, nullptr), "WriteSTL");
+  }
+  // the same mesh as a binary PLY with per-vertex normals and, for the voxel types that store colour, colours (itm_mesh_attributes)
+  void SaveSceneToPLY(const char* fileName) {
+    const bool colour = TVoxel::kType == ITM_VOXEL_S_RGB || TVoxel::kType == ITM_VOXEL_F_RGB;
+    MeshForExport(ITM_MESH_NORMALS | (colour ? ITM_MESH_COLOURS : 0));
+    check(itm_mesh_write_ply(exportMesh, fileName, nullptr), "WritePLY");
+  }
+
+ private:
+  void MeshForExport(int attributes) {
+    if (!exportMesh) check(itm_mesh_create(scene.handle, 0, &exportMesh), "itm_mesh_create");
+    check(itm_mesh_scene(scene.handle, exportMesh, nullptr), "MeshScene");
+    if (attributes) check(itm_mesh_attributes(scene.handle, exportMesh, attributes, nullptr), "itm_mesh_attributes");
+  }
 };
 
 // ITMMesh (Objects/ITMMesh.h:14-124): the triangle buffer lives in HBM; WriteOBJ / WriteSTL produce the reference's files.
+// ComputeAttributes / WritePLY go beyond the reference's ITMMesh: per-vertex normals and colours of the buffer's triangles
+// (itm_mesh_attributes: computeSingleNormalFromSDF and readFromSDF_color4u_interpolated at vertex / voxelSize) and a binary PLY.
 class ITMMesh {
  public:
   itm_mesh* handle = nullptr;
@@ -716,6 +739,15 @@ class ITMMesh {
   const float* triangles() const { const float* p = nullptr; check(itm_mesh_info(handle, nullptr, nullptr, &p, stream), "itm_mesh_info"); return p; }   // device pointer
   void WriteOBJ(const char* fileName) const { check(itm_mesh_write_obj(handle, fileName, stream), "WriteOBJ"); }
   void WriteSTL(const char* fileName) const { check(itm_mesh_write_stl(handle, fileName, stream), "WriteSTL"); }
+  // what: ITM_MESH_NORMALS, ITM_MESH_COLOURS or both; stale after the next MeshScene
+  template <class TVoxel, class TIndex>
+  void ComputeAttributes(const ITMScene<TVoxel, TIndex>* scene, int what) { check(itm_mesh_attributes(scene->handle, handle, what, stream), "ComputeAttributes"); }
+  // host copies: 3 x float[3] / 3 x {r, g, b, 255} per triangle, buffer order
+  void DownloadAttributes(float* normals, uint8_t* colours, uint32_t capacityTriangles) const {
+    uint32_t n = 0;
+    check(itm_mesh_download_attributes(handle, normals, colours, capacityTriangles, &n, stream), "DownloadAttributes");
+  }
+  void WritePLY(const char* fileName) const { check(itm_mesh_write_ply(handle, fileName, stream), "WritePLY"); }
 };
 
 // ITMMeshingEngine<TVoxel,TIndex>::MeshScene (Engine/ITMMeshingEngine.h:19-26)

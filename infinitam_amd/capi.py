@@ -28,6 +28,7 @@ RENDER_SHADED_GREYSCALE, RENDER_COLOUR_FROM_VOLUME, RENDER_COLOUR_FROM_NORMAL = 
  BUF_VISIBLE_TYPE, BUF_RANGE_IMAGE, BUF_RAYCAST_RESULT, BUF_RAYCAST_IMAGE, BUF_FORWARD_PROJECTION,
  BUF_MISSING_POINTS, BUF_SWAP_STATES) = range(12)
 ERR_INVALID, ERR_DEVICE, ERR_UNSUPPORTED = -1, -2, -3
+MESH_NORMALS, MESH_COLOURS = 1, 2
 
 VOXEL_NAMES = {VOXEL_S: "ITMVoxel_s", VOXEL_F: "ITMVoxel_f", VOXEL_S_RGB: "ITMVoxel_s_rgb",
                VOXEL_F_RGB: "ITMVoxel_f_rgb"}
@@ -296,6 +297,10 @@ _HOST_IO_SIGS = {
     "ren_tracker_prepare": (C.c_int, [_P, C.POINTER(ViewStruct), _P, _P]),
     "ren_tracker_evaluate": (C.c_int, [_P, _P, C.POINTER(C.c_float), C.c_int, C.POINTER(RenEval), _P]),
     "ren_tracker_track_camera": (C.c_int, [_P, _P, C.POINTER(ViewStruct), C.POINTER(C.c_float), C.POINTER(C.c_int), _P]),
+    # mesh vertex attributes and the PLY writer (product only: the reference's ITMMesh holds positions alone)
+    "mesh_attributes": (C.c_int, [_P, _P, C.c_int, _P]),
+    "mesh_download_attributes": (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(C.c_uint32), _P]),
+    "mesh_write_ply": (C.c_int, [_P, C.c_char_p, _P]),
 }
 
 
@@ -621,6 +626,30 @@ class Mesh:
 
     def WriteSTL(self, path: str, stream=None):
         self.scene.be.check(self.scene.be.fn["mesh_write_stl"](_P(self.h), path.encode(), _P(stream)), "mesh_write_stl")
+
+    def ComputeAttributes(self, what: int = MESH_NORMALS, stream=None):
+        """Per-vertex normals (MESH_NORMALS) and / or colours (MESH_COLOURS) of the triangles MeshScene left in the buffer."""
+        self.scene.be.check(self.scene.be.fn["mesh_attributes"](_P(self.scene.h), _P(self.h), int(what), _P(stream)), "mesh_attributes")
+
+    def _attributes(self, normals: bool, stream):
+        n, _ = self.info(stream)
+        out = np.zeros((n, 3, 3), np.float32) if normals else np.zeros((n, 3, 4), np.uint8)
+        got = C.c_uint32()
+        p = out.ctypes.data_as(_P)
+        self.scene.be.check(self.scene.be.fn["mesh_download_attributes"](_P(self.h), p if normals else None, None if normals else p, n,
+                                                                         C.byref(got), _P(stream)), "mesh_download_attributes")
+        return out
+
+    def normals(self, stream=None) -> np.ndarray:
+        """(noTotalTriangles, 3, 3) float32: the unit normal of p0, p1, p2 per triangle."""
+        return self._attributes(True, stream)
+
+    def colours(self, stream=None) -> np.ndarray:
+        """(noTotalTriangles, 3, 4) uint8: r, g, b, 255 of p0, p1, p2 per triangle."""
+        return self._attributes(False, stream)
+
+    def WritePLY(self, path: str, stream=None):
+        self.scene.be.check(self.scene.be.fn["mesh_write_ply"](_P(self.h), path.encode(), _P(stream)), "mesh_write_ply")
 
     def close(self):
         if self.h:

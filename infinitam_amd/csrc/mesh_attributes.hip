@@ -1,0 +1,283 @@
+// mesh_attributes.hip -- per-vertex normals and colours of the marching-cubes mesh, and the PLY writer that carries them.
+//
+// Reference behaviour (the reference's ITMMesh holds positions only; the two per-point functions are the reference's own):
+//   computeSingleNormalFromSDF            DeviceAgnostic/ITMRepresentationAccess.h:224-337   (shading_device.h: sdf_gradient)
+//   readFromSDF_color4u_interpolated      DeviceAgnostic/ITMRepresentationAccess.h:187-222   (shading_device.h: colour_at)
+//   drawPixelColour (float -> uchar)      DeviceAgnostic/ITMVisualisationEngine.h:270-279
+// evaluated at p = vertex / voxelSize (three IEEE divisions) for every vertex of the triangles the last itm_mesh_scene left in
+// the buffer, in buffer order.  The normal is the gradient times 1 / sqrt(g.g) (as normal_from_sdf forms it, no light test) and
+// (0, 0, 0) where that is not finite; it points from the surface into free space.
+//
+// MI355X design: the triangles of one voxel block lie together in the buffer (meshing.hip: base(block) from the scan that
+// itm_mesh_scene leaves in blockTriangles), and every vertex of the block's cells samples voxels within two of the block.  So
+// mesh_attr_block_kernel runs one 256-lane workgroup per listed block that has triangles: the 13^3 raw sdf values (and packed
+// colours) of planes -2 .. +10 of the block are staged in LDS once through the block directory -- 27 block look-ups per block
+// instead of 40 per vertex -- and the lanes then work through the block's vertices from LDS with the reference's float
+// operations.  floor(p) may sit one voxel under the cell's corner (a lattice coordinate that `* voxelSize / voxelSize` returned
+// one ulp low): planes -2 and +10 are there for those.  A vertex whose floor(p) leaves [-1, 8] takes the global path, which is
+// also the whole of mesh_attr_vertex_kernel (one lane per vertex; ITM_DEBUG_MESH_ATTR_PER_VERTEX).
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "itm_internal.h"
+#include "mesh_types.h"
+#include "shading_device.h"
+
+namespace itm {
+
+int g_debug_mesh_attr_per_vertex = 0;
+
+constexpr int kHaloLow = 2;                       // planes below the block
+constexpr int kHaloSide = kBlockSide + 5;         // -2 .. +10
+constexpr int kHaloCells = kHaloSide * kHaloSide * kHaloSide;
+
+// sdf_gradient (shading_device.h) over any source of raw sdf values: `raw(dx, dy, dz)` is the voxel at floor(p) + (dx, dy, dz).
+// The products and sums are gradient_component's, term for term.
+template <class VX, int AXIS, class S>
+__device__ inline float gradient_axis(S&& raw, float fa, float fu, float fv) {
+  auto sample = [&](int k, int u, int v) {
+    const int dx = (AXIS == 0) ? k : u;
+    const int dy = (AXIS == 1) ? k : (AXIS == 0 ? u : v);
+    const int dz = (AXIS == 2) ? k : v;
+    return raw(dx, dy, dz);
+  };
+  const float gu = 1.0f - fu, gv = 1.0f - fv, ga = 1.0f - fa;
+  float plane[4];
+#pragma unroll
+  for (int k = -1; k <= 2; ++k)
+    plane[k + 1] = sample(k, 0, 0) * gu * gv + sample(k, 1, 0) * fu * gv + sample(k, 0, 1) * gu * fv + sample(k, 1, 1) * fu * fv;
+  const float lower = plane[1] * fa + plane[0] * ga;
+  return VX::to_float(plane[2] * ga + plane[3] * fa - lower);
+}
+
+// colour_at (shading_device.h) over any source of packed colours (r | g << 8 | b << 16; 0 where no voxel is stored)
+template <class C>
+__device__ inline float4 colour_from(C&& packed, float cx, float cy, float cz) {
+  float r[3] = {0.0f, 0.0f, 0.0f};
+  auto add = [&](int dx, int dy, int dz, float wgt) {
+    const uint32_t c = packed(dx, dy, dz);
+    r[0] += wgt * (float)(int)(c & 0xffu); r[1] += wgt * (float)(int)((c >> 8) & 0xffu); r[2] += wgt * (float)(int)((c >> 16) & 0xffu);
+  };
+  add(0, 0, 0, (1.0f - cx) * (1.0f - cy) * (1.0f - cz));
+  add(1, 0, 0, (cx) * (1.0f - cy) * (1.0f - cz));
+  add(0, 1, 0, (1.0f - cx) * (cy) * (1.0f - cz));
+  add(1, 1, 0, (cx) * (cy) * (1.0f - cz));
+  add(0, 0, 1, (1.0f - cx) * (1.0f - cy) * cz);
+  add(1, 0, 1, (cx) * (1.0f - cy) * cz);
+  add(0, 1, 1, (1.0f - cx) * (cy)*cz);
+  add(1, 1, 1, (cx) * (cy)*cz);
+  return make_float4(r[0] / 255.0f, r[1] / 255.0f, r[2] / 255.0f, 255.0f / 255.0f);
+}
+
+__device__ inline void store_normal(float* __restrict__ o, float gx, float gy, float gz) {
+  const float sc = 1.0f / sqrtf(gx * gx + gy * gy + gz * gz);
+  float nx = gx * sc, ny = gy * sc, nz = gz * sc;
+  if (!(__builtin_isfinite(nx) && __builtin_isfinite(ny) && __builtin_isfinite(nz))) nx = ny = nz = 0.0f;   // zero or overflowing length
+  o[0] = nx; o[1] = ny; o[2] = nz;
+}
+
+__device__ inline uchar4 colour_bytes(float4 c) {   // drawPixelColour
+  return make_uchar4((unsigned char)(c.x * 255.0f), (unsigned char)(c.y * 255.0f), (unsigned char)(c.z * 255.0f), 255);
+}
+
+// the attributes of vertex v through the hash (directory / mirror where they cover): the reference's functions as the renders use them
+template <class VX>
+__device__ inline void vertex_global(const VolumeView& vol, size_t v, float px, float py, float pz, uint32_t what,
+                                     float* __restrict__ normals, uchar4* __restrict__ colours) {
+  if (what & ITM_MESH_NORMALS) {
+    float gx, gy, gz;
+    sdf_gradient<VX, false>(vol, px, py, pz, gx, gy, gz);
+    store_normal(normals + 3 * v, gx, gy, gz);
+  }
+  if constexpr (VX::kColor) {
+    if (what & ITM_MESH_COLOURS) colours[v] = colour_bytes(colour_at<VX, false>(vol, px, py, pz));
+  }
+}
+
+template <class VX>
+__global__ void __launch_bounds__(256) mesh_attr_vertex_kernel(VolumeView vol, const float* __restrict__ triangles, const uint32_t* __restrict__ totals,
+                                                               float voxelSize, uint32_t what, float* __restrict__ normals, uchar4* __restrict__ colours) {
+  const size_t nVertices = (size_t)totals[1] * 3;
+  for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < nVertices; v += (size_t)gridDim.x * 256) {
+    const float* p = triangles + 3 * v;
+    vertex_global<VX>(vol, v, p[0] / voxelSize, p[1] / voxelSize, p[2] / voxelSize, what, normals, colours);
+  }
+}
+
+template <class VX>
+__global__ void __launch_bounds__(256) mesh_attr_block_kernel(VolumeView vol, const int32_t* __restrict__ slots, const RenderCounters* __restrict__ lc,
+                                                              const int32_t* __restrict__ blockTriangles, const float* __restrict__ triangles,
+                                                              const uint32_t* __restrict__ totals, int capBlocks, float voxelSize, uint32_t what,
+                                                              float* __restrict__ normals, uchar4* __restrict__ colours) {
+  __shared__ float sdf[kHaloCells];                          // raw sdf; the default voxel's where none is stored (readVoxel)
+  __shared__ uint32_t clr[VX::kColor ? kHaloCells : 1];      // r | g << 8 | b << 16; 0 where none is stored
+  __shared__ int nbBase[27];
+  const uint32_t generated = totals[0], count = totals[1];
+  if (count == 0u) return;                                   // nothing meshed (yet): the block list may never have been written
+  const int nBlocks = lc->noVisibleEntries < capBlocks ? lc->noVisibleEntries : capBlocks;
+  const int t = threadIdx.x;
+  const bool wantColour = VX::kColor && (what & ITM_MESH_COLOURS);
+  for (int b = blockIdx.x; b < nBlocks; b += gridDim.x) {
+    // the block's triangles: [prefix(b), prefix(b + 1)), cut at the count a full buffer stops at
+    uint32_t t0 = (uint32_t)blockTriangles[b], t1 = (b + 1 < nBlocks) ? (uint32_t)blockTriangles[b + 1] : generated;
+    t0 = t0 < count ? t0 : count; t1 = t1 < count ? t1 : count;
+    if (t0 == t1) continue;                                  // (uniform) no surface in this block: nothing is staged
+    const HashEntry he = unpack_entry(vol.hash[slots[b]]);
+    __syncthreads();                                         // previous block's LDS contents are no longer needed
+    if (t < 27) nbBase[t] = (t == 13) ? he.ptr * kBlockVoxels : block_base(vol, he.px + t % 3 - 1, he.py + (t / 3) % 3 - 1, he.pz + t / 9 - 1);
+    __syncthreads();
+    for (int i = t; i < kHaloCells; i += 256) {
+      const int x = i % kHaloSide - kHaloLow, y = (i / kHaloSide) % kHaloSide - kHaloLow, z = i / (kHaloSide * kHaloSide) - kHaloLow;
+      const int base = nbBase[((x + 8) >> 3) + 3 * ((y + 8) >> 3) + 9 * ((z + 8) >> 3)];
+      float v = VX::kShort ? 32767.0f : 1.0f;
+      uint32_t c = 0u;
+      if (base >= 0) {
+        const size_t a = (size_t)(base + (x & 7) + ((y & 7) << 3) + ((z & 7) << 6));
+        if constexpr (VX::kColor) {
+          if (wantColour) {
+            const typename VX::Reg r = VX::load(vol.vba, a);
+            int rgb[3], wc;
+            VX::get_color(r, rgb, wc);
+            v = VX::raw_sdf(r);
+            c = (uint32_t)rgb[0] | ((uint32_t)rgb[1] << 8) | ((uint32_t)rgb[2] << 16);
+          } else v = VX::load_raw_sdf(vol.vba, a);
+        } else v = VX::load_raw_sdf(vol.vba, a);
+      }
+      sdf[i] = v;
+      if constexpr (VX::kColor) clr[i] = c;
+    }
+    __syncthreads();
+    const int ox = he.px * kBlockSide, oy = he.py * kBlockSide, oz = he.pz * kBlockSide;
+    const uint32_t nV = (t1 - t0) * 3u;
+    for (uint32_t k = t; k < nV; k += 256) {
+      const size_t v = (size_t)t0 * 3 + k;
+      const float* p = triangles + 3 * v;
+      const float px = p[0] / voxelSize, py = p[1] / voxelSize, pz = p[2] / voxelSize;
+      const float bx = floorf(px), by = floorf(py), bz = floorf(pz);
+      const float fx = px - bx, fy = py - by, fz = pz - bz;
+      const int lx = (int)bx - ox, ly = (int)by - oy, lz = (int)bz - oz;
+      // reads reach floor(p) - 1 .. floor(p) + 2: staged for floor(p) in [-1, 8] per axis
+      if ((uint32_t)(lx + 1) > 9u || (uint32_t)(ly + 1) > 9u || (uint32_t)(lz + 1) > 9u) {
+        vertex_global<VX>(vol, v, px, py, pz, what, normals, colours);
+        continue;
+      }
+      const int at = (lx + kHaloLow) + (ly + kHaloLow) * kHaloSide + (lz + kHaloLow) * kHaloSide * kHaloSide;
+      if (what & ITM_MESH_NORMALS) {
+        auto raw = [&](int dx, int dy, int dz) { return sdf[at + dx + dy * kHaloSide + dz * kHaloSide * kHaloSide]; };
+        const float gx = gradient_axis<VX, 0>(raw, fx, fy, fz);
+        const float gy = gradient_axis<VX, 1>(raw, fy, fx, fz);
+        const float gz = gradient_axis<VX, 2>(raw, fz, fx, fy);
+        store_normal(normals + 3 * v, gx, gy, gz);
+      }
+      if constexpr (VX::kColor) {
+        if (wantColour) {
+          auto packed = [&](int dx, int dy, int dz) { return clr[at + dx + dy * kHaloSide + dz * kHaloSide * kHaloSide]; };
+          colours[v] = colour_bytes(colour_from(packed, fx, fy, fz));
+        }
+      }
+    }
+  }
+}
+
+static bool voxel_has_colour(int voxelType) { return voxelType == ITM_VOXEL_S_RGB || voxelType == ITM_VOXEL_F_RGB; }
+
+}  // namespace itm
+
+using namespace itm;
+
+extern "C" {
+
+int itm_mesh_attributes(const itm_scene* s, itm_mesh* m, int what, itm_stream stream) {
+  if (!s || !m) return set_error(ITM_ERR_INVALID, "null argument");
+  if (m->scene != s) return set_error(ITM_ERR_INVALID, "mesh belongs to another scene");
+  if (what <= 0 || (what & ~(ITM_MESH_NORMALS | ITM_MESH_COLOURS))) return set_error(ITM_ERR_INVALID, "what: ITM_MESH_NORMALS, ITM_MESH_COLOURS or both");
+  if ((what & ITM_MESH_COLOURS) && !voxel_has_colour(s->cfg.voxelType))
+    return set_error(ITM_ERR_INVALID, "the scene's voxel type stores no colour: the mesh has no colour attribute");
+  { const int rc = enter_scene(s, nullptr); if (rc) return rc; }
+  hipStream_t st = as_stream(stream);
+  if (s->cfg.indexType != ITM_INDEX_HASH) { m->attrCurrent |= (uint32_t)what; return ITM_OK; }   // dense scenes: an empty mesh, empty attributes
+  if ((what & ITM_MESH_NORMALS) && !m->normals) {
+    const hipError_t e = hipMalloc((void**)&m->normals, (size_t)m->maxTriangles * 36);
+    if (e != hipSuccess) { m->normals = nullptr; return hip_fail(e, "mesh normals", __FILE__, __LINE__); }
+  }
+  if ((what & ITM_MESH_COLOURS) && !m->colours) {
+    const hipError_t e = hipMalloc((void**)&m->colours, (size_t)m->maxTriangles * 12);
+    if (e != hipSuccess) { m->colours = nullptr; return hip_fail(e, "mesh colours", __FILE__, __LINE__); }
+  }
+  const VolumeView vol = make_volume(s);
+  const int grid = 256 * 8;
+  const int rc = dispatch_voxel(s->cfg.voxelType, [&](auto vx) {
+    using VX = decltype(vx);
+    if (g_debug_mesh_attr_per_vertex)
+      mesh_attr_vertex_kernel<VX><<<grid, 256, 0, st>>>(vol, m->triangles, m->totals, s->prm.voxelSize, (uint32_t)what, m->normals, m->colours);
+    else
+      mesh_attr_block_kernel<VX><<<grid, 256, 0, st>>>(vol, m->slots, m->listCounters, m->blockTriangles, m->triangles, m->totals, m->capBlocks, s->prm.voxelSize,
+                                                      (uint32_t)what, m->normals, m->colours);
+    return ITM_OK;
+  });
+  if (rc) return rc;
+  ITM_LAUNCH_CHECK();
+  m->attrCurrent |= (uint32_t)what;
+  return ITM_OK;
+}
+
+int itm_mesh_download_attributes(const itm_mesh* m, float* normals_host, uint8_t* colours_host, uint32_t capacityTriangles,
+                                 uint32_t* noTotalTriangles, itm_stream stream) {
+  if (!m || !noTotalTriangles) return set_error(ITM_ERR_INVALID, "null argument");
+  if (normals_host && !(m->attrCurrent & ITM_MESH_NORMALS))
+    return set_error(ITM_ERR_INVALID, "no normals for this mesh: itm_mesh_attributes has not computed them since the last itm_mesh_scene");
+  if (colours_host && !(m->attrCurrent & ITM_MESH_COLOURS))
+    return set_error(ITM_ERR_INVALID, "no colours for this mesh: itm_mesh_attributes has not computed them since the last itm_mesh_scene");
+  { const int rc = enter_scene(m->scene, nullptr); if (rc) return rc; }
+  int rc = itm_mesh_info(m, noTotalTriangles, nullptr, nullptr, stream);
+  if (rc) return rc;
+  const uint32_t n = *noTotalTriangles < capacityTriangles ? *noTotalTriangles : capacityTriangles;
+  hipStream_t st = as_stream(stream);
+  if (n && normals_host) ITM_HIP(hipMemcpyAsync(normals_host, m->normals, (size_t)n * 36, hipMemcpyDeviceToHost, st));
+  if (n && colours_host) ITM_HIP(hipMemcpyAsync(colours_host, m->colours, (size_t)n * 12, hipMemcpyDeviceToHost, st));
+  ITM_HIP(hipStreamSynchronize(st));
+  return ITM_OK;
+}
+
+// binary_little_endian PLY: positions, then the attributes that are current; faces with WriteOBJ's winding
+int itm_mesh_write_ply(const itm_mesh* m, const char* path, itm_stream stream) {
+  if (!m || !path) return set_error(ITM_ERR_INVALID, "null argument");
+  { const int rc = enter_scene(m->scene, nullptr); if (rc) return rc; }
+  uint32_t n = 0;
+  int rc = itm_mesh_info(m, &n, nullptr, nullptr, stream);
+  if (rc) return rc;
+  const bool withNormals = (m->attrCurrent & ITM_MESH_NORMALS) != 0, withColours = (m->attrCurrent & ITM_MESH_COLOURS) != 0;
+  std::vector<float> tri((size_t)n * 9), nrm(withNormals ? (size_t)n * 9 : 0);
+  std::vector<uint8_t> col(withColours ? (size_t)n * 12 : 0);
+  if ((rc = itm_mesh_download(m, tri.data(), n, &n, stream))) return rc;
+  if (withNormals || withColours)
+    if ((rc = itm_mesh_download_attributes(m, withNormals ? nrm.data() : nullptr, withColours ? col.data() : nullptr, n, &n, stream))) return rc;
+  std::string head = "ply\nformat binary_little_endian 1.0\ncomment itm-hip mesh\nelement vertex " + std::to_string((unsigned long long)n * 3ull) +
+                     "\nproperty float x\nproperty float y\nproperty float z\n";
+  if (withNormals) head += "property float nx\nproperty float ny\nproperty float nz\n";
+  if (withColours) head += "property uchar red\nproperty uchar green\nproperty uchar blue\n";
+  head += "element face " + std::to_string(n) + "\nproperty list uchar int vertex_indices\nend_header\n";
+  const size_t vertexBytes = 12 + (withNormals ? 12 : 0) + (withColours ? 3 : 0);
+  std::vector<uint8_t> body((size_t)n * 3 * vertexBytes + (size_t)n * 13);
+  uint8_t* o = body.data();
+  for (size_t v = 0; v < (size_t)n * 3; ++v) {
+    memcpy(o, &tri[v * 3], 12); o += 12;
+    if (withNormals) { memcpy(o, &nrm[v * 3], 12); o += 12; }
+    if (withColours) { memcpy(o, &col[v * 4], 3); o += 3; }
+  }
+  for (uint32_t i = 0; i < n; ++i) {
+    const int32_t idx[3] = {(int32_t)(i * 3 + 2), (int32_t)(i * 3 + 1), (int32_t)(i * 3)};
+    *o++ = 3;
+    memcpy(o, idx, 12); o += 12;
+  }
+  FILE* f = fopen(path, "wb");
+  if (!f) return set_error(ITM_ERR_INVALID, std::string("cannot create ") + path);
+  bool ok = fwrite(head.data(), 1, head.size(), f) == head.size();
+  ok = (body.empty() || fwrite(body.data(), 1, body.size(), f) == body.size()) && ok;
+  ok = (fclose(f) == 0) && ok;
+  return ok ? ITM_OK : set_error(ITM_ERR_INVALID, std::string("short write to ") + path);
+}
+
+}  // extern "C"

@@ -28,20 +28,8 @@
 #include "itm_internal.h"
 #include "mc_tables.h"
 #include "shading_device.h"
+#include "mesh_types.h"
 #include "wave_utils.h"
-
-struct itm_mesh {
-  const itm_scene* scene = nullptr;
-  uint32_t maxTriangles = 0;
-  float* triangles = nullptr;        // ITMMesh::Triangle[maxTriangles]: 9 floats (p0, p1, p2)
-  int32_t* slots = nullptr;          // allocated slots in ascending order
-  int32_t* blockTriangles = nullptr; // per listed block: triangle count, then exclusive prefix
-  uint8_t* flags = nullptr;          // per slot: allocated?
-  int32_t* chunkCount = nullptr;
-  itm::RenderCounters* listCounters = nullptr;   // noVisibleEntries = number of listed blocks
-  uint32_t* totals = nullptr;        // [0] triangles generated, [1] noTotalTriangles (after the cap)
-  int capBlocks = 0;
-};
 
 namespace itm {
 
@@ -81,17 +69,6 @@ __device__ inline void edge_vertex(const float* p1, const float* p2, float v1, f
   out[0] = p1[0] + t * (p2[0] - p1[0]);
   out[1] = p1[1] + t * (p2[1] - p1[1]);
   out[2] = p1[2] + t * (p2[2] - p1[2]);
-}
-
-// block base (voxel index of its first voxel) of block (bx, by, bz), or -1: directory where it covers, table walk elsewhere
-__device__ inline int block_base(const VolumeView& vol, int bx, int by, int bz) {
-  const uint32_t ux = (uint32_t)(bx - vol.org.dx), uy = (uint32_t)(by - vol.org.dy), uz = (uint32_t)(bz - vol.org.dz);
-  if (vol.dirPtr && dir_covers(ux, uy, uz)) {
-    const int ptr = vol.dirPtr[dir_cell(ux, uy, uz)];
-    return ptr < 0 ? -1 : ptr * kBlockVoxels;
-  }
-  if ((int)(int16_t)bx != bx || (int)(int16_t)by != by || (int)(int16_t)bz != bz) return -1;   // beyond the table's short coordinates
-  return resolve_block(vol, unpack_entry(vol.hash[hash_index(bx, by, bz, vol.mask)]), bx, by, bz);
 }
 
 template <class VX, bool WRITE>
@@ -211,6 +188,7 @@ static void free_mesh(itm_mesh* m) {
   if (!m) return;
   (void)hipFree(m->triangles); (void)hipFree(m->slots); (void)hipFree(m->blockTriangles); (void)hipFree(m->flags);
   (void)hipFree(m->chunkCount); (void)hipFree(m->listCounters); (void)hipFree(m->totals);
+  (void)hipFree(m->normals); (void)hipFree(m->colours);
   delete m;
 }
 
@@ -265,6 +243,7 @@ int itm_mesh_scene(const itm_scene* s, itm_mesh* m, itm_stream stream) {
   if (m->scene != s) return set_error(ITM_ERR_INVALID, "mesh belongs to another scene");
   { const int rc = enter_scene(s, nullptr); if (rc) return rc; }
   hipStream_t st = as_stream(stream);
+  m->attrCurrent = 0;                                          // vertex attributes belong to the mesh that is being replaced
   // mesh->triangles->Clear()
   ITM_HIP(hipMemsetAsync(m->triangles, 0, (size_t)m->maxTriangles * 36, st));
   ITM_HIP(hipMemsetAsync(m->totals, 0, 8, st));

@@ -460,7 +460,8 @@ class ITMVisualisationEngine_HIP : public ITMVisualisationEngine<TVoxel, TIndex>
 
 // ITMMeshingEngine<TVoxel, TIndex> (Engine/ITMMeshingEngine.h:19-26) on the device scene twin: the mesh is built in HBM in the
 // reference's triangle order and mirrored into the reference's ITMMesh (triangles + noTotalTriangles), so WriteOBJ / WriteSTL of
-// the reference object work unchanged.
+// the reference object work unchanged.  The reference's ITMMesh has no room for the per-vertex normals and colours of
+// itm_mesh_attributes: they are out of this binding's scope (use the C-ABI or include/itm_hip_engines.hpp for them).
 template <class TVoxel, class TIndex>
 class ITMMeshingEngine_HIP : public ITMMeshingEngine<TVoxel, TIndex> {
   itm_mesh* dev = nullptr;

@@ -1,0 +1,71 @@
+// Exports a coloured mesh through the C++ adapter: two frames of a corrugated wall with a colour pattern are fused into an
+// ITMVoxel_s_rgb scene like ITMMainEngine::ProcessFrame does, the scene is meshed (ITMMeshingEngine_HIP), the per-vertex normals and
+// colours are computed (ITMMesh::ComputeAttributes) and the mesh is written as a binary PLY.
+//   mesh_ply_demo <out.ply>
+// Prints the counts as JSON; tests/test_mesh_attributes.py builds the same scene through the Python binding and compares the files.
+#include <cstdio>
+#include <cstdint>
+#include <vector>
+
+#include "itm_hip_engines.hpp"
+
+using namespace itmhip;
+typedef ITMVoxel_s_rgb V;
+typedef ITMVoxelBlockHash I;
+
+int main(int argc, char** argv) {
+  if (argc != 2) { fprintf(stderr, "usage: %s <out.ply>\n", argv[0]); return 2; }
+  const int W = 160, H = 120, P = W * H;
+  ITMSceneParams params(0.02f, 100, 0.01f, 0.35f, 3.0f, false);
+  ITMScene<V, I> scene(&params);
+  ITMDenseMapper_HIP<V, I> mapper;
+  ITMVisualisationEngine_HIP<V, I> vis(&scene);
+  ITMTrackingController_HIP<V, I> controller(&vis);
+  mapper.ResetScene(&scene);
+  ITMRenderState* rs = vis.CreateRenderState(Vector2i{W, H});
+
+  std::vector<float> depth(P);
+  std::vector<uint8_t> rgb((size_t)P * 4);
+  for (int y = 0; y < H; ++y)
+    for (int x = 0; x < W; ++x) {
+      depth[x + y * W] = 1.5f + 0.002f * (float)((x * 7 + y * 13) % 50);
+      uint8_t* c = &rgb[(size_t)(x + y * W) * 4];
+      c[0] = (uint8_t)((x * 3) & 255); c[1] = (uint8_t)((y * 5) & 255); c[2] = (uint8_t)((x + y) & 255); c[3] = 255;
+    }
+  void *dDepth, *dRgb, *dPts, *dNrm;
+  check(itm_dev_malloc(&dDepth, P * 4), "malloc"); check(itm_dev_malloc(&dRgb, P * 4), "malloc");
+  check(itm_dev_malloc(&dPts, P * 16), "malloc"); check(itm_dev_malloc(&dNrm, P * 16), "malloc");
+  check(itm_memcpy_h2d(dDepth, depth.data(), P * 4, nullptr), "h2d");
+  check(itm_memcpy_h2d(dRgb, rgb.data(), P * 4, nullptr), "h2d");
+
+  ITMView view;
+  view.calib.intrinsics_d.SetFrom(145.f, 145.f, 80.f, 60.f);
+  view.calib.intrinsics_rgb = view.calib.intrinsics_d;
+  view.depth = (const float*)dDepth; view.rgb = (const uint8_t*)dRgb;
+  view.depthSize = Vector2i{W, H}; view.rgbSize = Vector2i{W, H};
+  ITMTrackingState ts;
+  ts.pointCloud_locations = (float*)dPts; ts.pointCloud_colours = (float*)dNrm;
+
+  for (int k = 0; k < 2; ++k) {
+    float M[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, -0.01f * k, 0, 0, 1};
+    ts.pose_d.SetM(M);
+    controller.Track(&ts, &view);
+    mapper.ProcessFrame(&view, &ts, &scene, rs);
+    controller.Prepare(&ts, &view, rs);
+  }
+  ITMMesh mesh(&scene);
+  ITMMeshingEngine_HIP<V, I> mesher;
+  mesher.MeshScene(&mesh, &scene);
+  mesh.ComputeAttributes(&scene, ITM_MESH_NORMALS | ITM_MESH_COLOURS);
+  mesh.WritePLY(argv[1]);
+  std::vector<float> normals((size_t)mesh.noTotalTriangles * 9);
+  std::vector<uint8_t> colours((size_t)mesh.noTotalTriangles * 12);
+  mesh.DownloadAttributes(normals.data(), colours.data(), mesh.noTotalTriangles);
+  double nz = 0; long red = 0;
+  for (size_t i = 2; i < normals.size(); i += 3) nz += normals[i];
+  for (size_t i = 0; i < colours.size(); i += 4) red += colours[i];
+  printf("{\"triangles\": %u, \"sum_nz\": %.9g, \"sum_red\": %ld}\n", mesh.noTotalTriangles, nz, red);
+  delete rs;
+  itm_dev_free(dDepth); itm_dev_free(dRgb); itm_dev_free(dPts); itm_dev_free(dNrm);
+  return 0;
+}
