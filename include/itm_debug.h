@@ -37,6 +37,7 @@ extern "C" {
 #define ITM_DEBUG_EXCHANGE_DEVICE_COPY 24        /* exchanges created while it is set: a ONE-rank exchange performs its collective as a device copy instead of ncclAllGather (a test pins both to the same table) */
 #define ITM_DEBUG_EXCHANGE_CORRUPT_WORD 25       /* exchanges created while it is >= 0: the self-check behind every collective sees this word of the rank's own block flipped (the check must fire); -1 = off */
 #define ITM_DEBUG_MESH_ATTR_PER_VERTEX 26        /* itm_mesh_attributes: one lane per vertex reading through the hash instead of one workgroup per block reading from LDS */
+#define ITM_DEBUG_MESH_INDEX_WEAK_HASH 27        /* itm_mesh_index: the hash cut to 8 bits (256 start slots spread over the table, the last 64 slots before its end): probe chains hundreds of slots long and the wrap-around on small meshes */
 int ITM_FN(debug_set)(int key, int value);
 /* A stand-in for a device-side consumer of the exchange's table (tests of itm_exchange_acquire): dst[0] = sum over `rounds` passes of a
  * position-weighted checksum of src[0 .. words), computed by ONE workgroup on `stream` -- slow on purpose, so that collectives of later

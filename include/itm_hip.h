@@ -599,6 +599,38 @@ int ITM_FN(mesh_download_attributes)(const itm_mesh* mesh, float* normals_host, 
  * current, then uchar red, green, blue if the colours are -- and one face {3, 3i + 2, 3i + 1, 3i} per triangle (the winding of
  * ITMMesh::WriteOBJ, Objects/ITMMesh.h:34-62).  With neither attribute current the file holds positions only. */
 int ITM_FN(mesh_write_ply)(const itm_mesh* mesh, const char* path, itm_stream stream);
+/* Indexed mesh: the triangle soup welded into shared vertices (the reference has none; defined in terms of its triangle buffer).  With
+ * s_j, j = 0 .. 3 * noTotalTriangles - 1, the buffer's vertices in buffer order: two of them are the same vertex iff their three floats
+ * have the same 96 bits (no tolerance; -0.0f != +0.0f).  first[k] = the smallest j that holds the k-th distinct position, strictly
+ * ascending -- unique vertices are numbered in the order of their first occurrence --, vertices[k] = s_first[k], faces[i] = the indices of
+ * s_3i, s_3i+1, s_3i+2.  Every triangle is kept, also those whose corners coincide after welding: vertices[faces] is the soup bit for
+ * bit.  The result is deterministic.  itm_mesh_index builds the three arrays for the present contents of the buffer in device memory
+ * owned by the mesh (allocated / grown from the counts; the call synchronises `stream` to read them) and leaves the triangle buffer as
+ * it is; itm_mesh_scene makes the index stale.  An empty buffer (dense scenes) gives an empty index. */
+int ITM_FN(mesh_index)(itm_mesh* mesh, itm_stream stream);
+/* number of unique vertices / of triangles of the index and its device arrays (float[3] per vertex, uint32[3] per triangle, uint32 per
+ * vertex; NULL for an empty index); synchronises `stream`.  Any output pointer may be NULL.  Stale or missing index: ITM_ERR_INVALID. */
+int ITM_FN(mesh_index_info)(const itm_mesh* mesh, uint32_t* noVertices, uint32_t* noTriangles, const float** vertices,
+                            const uint32_t** faces, const uint32_t** first, itm_stream stream);
+/* copies min(noVertices, capacityVertices) vertices (3 floats each) and entries of `first`, and min(noTriangles, capacityTriangles)
+ * faces (3 uint32 each) to host memory; any pointer may be NULL.  Stale or missing index: ITM_ERR_INVALID.  Synchronises `stream`. */
+int ITM_FN(mesh_download_indexed)(const itm_mesh* mesh, float* vertices_host, uint32_t* first_host, uint32_t capacityVertices,
+                                  uint32_t* faces_host, uint32_t capacityTriangles, uint32_t* noVertices, uint32_t* noTriangles,
+                                  itm_stream stream);
+/* itm_mesh_attributes for the unique vertices of the index: normal[k], colour[k] = the attribute of s_first[k] (a function of the position
+ * alone), evaluated once per unique vertex.  The same refusals as itm_mesh_attributes, and ITM_ERR_INVALID on a stale or missing index.
+ * itm_mesh_scene and itm_mesh_index make them stale; they and the soup's attributes are independent of each other. */
+int ITM_FN(mesh_indexed_attributes)(const itm_scene* scene, itm_mesh* mesh, int what, itm_stream stream);
+/* copies the attributes of min(noVertices, capacity) unique vertices to host memory: normals_host float[3], colours_host {r, g, b, 255}
+ * per vertex; either may be NULL.  A non-NULL pointer whose attribute is stale or was never computed: ITM_ERR_INVALID.  Synchronises. */
+int ITM_FN(mesh_download_indexed_attributes)(const itm_mesh* mesh, float* normals_host, uint8_t* colours_host, uint32_t capacityVertices,
+                                             uint32_t* noVertices, itm_stream stream);
+/* The indexed mesh as a file.  PLY: the header lines and property order of itm_mesh_write_ply with `element vertex noVertices`, the
+ * attributes written when the INDEXED attributes are current, one face {3, f2, f1, f0} per triangle.  OBJ: the format of
+ * ITMMesh::WriteOBJ (Objects/ITMMesh.h:34-62), "v %f %f %f" per unique vertex, then "f c+1 b+1 a+1" per triangle (a, b, c).  Stale or
+ * missing index: ITM_ERR_INVALID. */
+int ITM_FN(mesh_write_ply_indexed)(const itm_mesh* mesh, const char* path, itm_stream stream);
+int ITM_FN(mesh_write_obj_indexed)(const itm_mesh* mesh, const char* path, itm_stream stream);
 
 /* ---- multi-stream exchange (BASELINE configs[3]) ------------------------------------------------------------------
  * One depth stream per GPU; fusion needs no collective.  Per frame every rank publishes the record of itm_export_visible_record

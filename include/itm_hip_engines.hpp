@@ -711,6 +711,15 @@ class ITMMainEngine_HIP {
     MeshForExport(ITM_MESH_NORMALS | (colour ? ITM_MESH_COLOURS : 0));
     check(itm_mesh_write_ply(exportMesh, fileName, nullptr), "WritePLY");
   }
+  // the mesh welded into shared vertices (itm_mesh_index): a binary PLY with one vertex per distinct position, faces through the
+  // index, and the same attributes evaluated once per unique vertex (itm_mesh_indexed_attributes)
+  void SaveSceneToIndexedPLY(const char* fileName) {
+    const bool colour = TVoxel::kType == ITM_VOXEL_S_RGB || TVoxel::kType == ITM_VOXEL_F_RGB;
+    MeshForExport(0);
+    check(itm_mesh_index(exportMesh, nullptr), "itm_mesh_index");
+    check(itm_mesh_indexed_attributes(scene.handle, exportMesh, ITM_MESH_NORMALS | (colour ? ITM_MESH_COLOURS : 0), nullptr), "itm_mesh_indexed_attributes");
+    check(itm_mesh_write_ply_indexed(exportMesh, fileName, nullptr), "WriteIndexedPLY");
+  }
 
  private:
   void MeshForExport(int attributes) {
@@ -748,6 +757,16 @@ class ITMMesh {
     check(itm_mesh_download_attributes(handle, normals, colours, capacityTriangles, &n, stream), "DownloadAttributes");
   }
   void WritePLY(const char* fileName) const { check(itm_mesh_write_ply(handle, fileName, stream), "WritePLY"); }
+  // the indexed form of the buffer's triangles (bit-equal positions are one vertex); stale after the next MeshScene
+  uint32_t noVertices = 0;
+  void Index() {
+    check(itm_mesh_index(handle, stream), "Index");
+    check(itm_mesh_index_info(handle, &noVertices, nullptr, nullptr, nullptr, nullptr, stream), "itm_mesh_index_info");
+  }
+  template <class TVoxel, class TIndex>
+  void ComputeIndexedAttributes(const ITMScene<TVoxel, TIndex>* scene, int what) { check(itm_mesh_indexed_attributes(scene->handle, handle, what, stream), "ComputeIndexedAttributes"); }
+  void WriteIndexedPLY(const char* fileName) const { check(itm_mesh_write_ply_indexed(handle, fileName, stream), "WriteIndexedPLY"); }
+  void WriteIndexedOBJ(const char* fileName) const { check(itm_mesh_write_obj_indexed(handle, fileName, stream), "WriteIndexedOBJ"); }
 };
 
 // ITMMeshingEngine<TVoxel,TIndex>::MeshScene (Engine/ITMMeshingEngine.h:19-26)

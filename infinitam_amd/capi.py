@@ -301,6 +301,14 @@ _HOST_IO_SIGS = {
     "mesh_attributes": (C.c_int, [_P, _P, C.c_int, _P]),
     "mesh_download_attributes": (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(C.c_uint32), _P]),
     "mesh_write_ply": (C.c_int, [_P, C.c_char_p, _P]),
+    # indexed mesh: the soup welded into shared vertices (product only)
+    "mesh_index": (C.c_int, [_P, _P]),
+    "mesh_index_info": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P]),
+    "mesh_download_indexed": (C.c_int, [_P, _P, _P, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _P]),
+    "mesh_indexed_attributes": (C.c_int, [_P, _P, C.c_int, _P]),
+    "mesh_download_indexed_attributes": (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(C.c_uint32), _P]),
+    "mesh_write_ply_indexed": (C.c_int, [_P, C.c_char_p, _P]),
+    "mesh_write_obj_indexed": (C.c_int, [_P, C.c_char_p, _P]),
 }
 
 
@@ -650,6 +658,63 @@ class Mesh:
 
     def WritePLY(self, path: str, stream=None):
         self.scene.be.check(self.scene.be.fn["mesh_write_ply"](_P(self.h), path.encode(), _P(stream)), "mesh_write_ply")
+
+    def Index(self, stream=None):
+        """Welds the triangles MeshScene left in the buffer into shared vertices (bit-equal positions are one vertex)."""
+        self.scene.be.check(self.scene.be.fn["mesh_index"](_P(self.h), _P(stream)), "mesh_index")
+
+    def index_info(self, stream=None):
+        """(number of unique vertices, number of triangles) of the index"""
+        nv, nt = C.c_uint32(), C.c_uint32()
+        self.scene.be.check(self.scene.be.fn["mesh_index_info"](_P(self.h), C.byref(nv), C.byref(nt), None, None, None, _P(stream)), "mesh_index_info")
+        return nv.value, nt.value
+
+    def _indexed(self, which: int, stream):
+        nv, nt = self.index_info(stream)
+        out = (np.zeros((nv, 3), np.float32), np.zeros(nv, np.uint32), np.zeros((nt, 3), np.uint32))[which]
+        p = [None, None, None]
+        p[which] = out.ctypes.data_as(_P)
+        self.scene.be.check(self.scene.be.fn["mesh_download_indexed"](_P(self.h), p[0], p[1], nv, p[2], nt, None, None, _P(stream)), "mesh_download_indexed")
+        return out
+
+    def vertices(self, stream=None) -> np.ndarray:
+        """(noVertices, 3) float32: the distinct positions in the order of their first occurrence in the triangle buffer."""
+        return self._indexed(0, stream)
+
+    def first(self, stream=None) -> np.ndarray:
+        """(noVertices,) uint32: the first soup vertex (3 * triangle + corner) that holds each unique vertex, strictly ascending."""
+        return self._indexed(1, stream)
+
+    def faces(self, stream=None) -> np.ndarray:
+        """(noTotalTriangles, 3) uint32: vertices()[faces()] is triangles()."""
+        return self._indexed(2, stream)
+
+    def ComputeIndexedAttributes(self, what: int = MESH_NORMALS, stream=None):
+        """Normals and / or colours per unique vertex of the index, evaluated once per vertex."""
+        self.scene.be.check(self.scene.be.fn["mesh_indexed_attributes"](_P(self.scene.h), _P(self.h), int(what), _P(stream)), "mesh_indexed_attributes")
+
+    def _indexed_attributes(self, normals: bool, stream):
+        nv, _ = self.index_info(stream)
+        out = np.zeros((nv, 3), np.float32) if normals else np.zeros((nv, 4), np.uint8)
+        got = C.c_uint32()
+        p = out.ctypes.data_as(_P)
+        self.scene.be.check(self.scene.be.fn["mesh_download_indexed_attributes"](_P(self.h), p if normals else None, None if normals else p, nv,
+                                                                                 C.byref(got), _P(stream)), "mesh_download_indexed_attributes")
+        return out
+
+    def vertex_normals(self, stream=None) -> np.ndarray:
+        """(noVertices, 3) float32: the unit normal of every unique vertex."""
+        return self._indexed_attributes(True, stream)
+
+    def vertex_colours(self, stream=None) -> np.ndarray:
+        """(noVertices, 4) uint8: r, g, b, 255 of every unique vertex."""
+        return self._indexed_attributes(False, stream)
+
+    def WriteIndexedPLY(self, path: str, stream=None):
+        self.scene.be.check(self.scene.be.fn["mesh_write_ply_indexed"](_P(self.h), path.encode(), _P(stream)), "mesh_write_ply_indexed")
+
+    def WriteIndexedOBJ(self, path: str, stream=None):
+        self.scene.be.check(self.scene.be.fn["mesh_write_obj_indexed"](_P(self.h), path.encode(), _P(stream)), "mesh_write_obj_indexed")
 
     def close(self):
         if self.h:

@@ -16,6 +16,11 @@
 // operations.  floor(p) may sit one voxel under the cell's corner (a lattice coordinate that `* voxelSize / voxelSize` returned
 // one ulp low): planes -2 and +10 are there for those.  A vertex whose floor(p) leaves [-1, 8] takes the global path, which is
 // also the whole of mesh_attr_vertex_kernel (one lane per vertex; ITM_DEBUG_MESH_ATTR_PER_VERTEX).
+//
+// itm_mesh_indexed_attributes runs the same kernel over the unique vertices of the indexed mesh (mesh_index.hip): `first` ascends,
+// so the unique vertices whose first occurrence lies in block b's triangles are one contiguous range [blockVertex[b], blockVertex
+// [b + 1]) -- vertices of that block's cells, for which the staged planes hold as they do for the soup.  One evaluation per distinct
+// position instead of one per occurrence.
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -106,7 +111,9 @@ __global__ void __launch_bounds__(256) mesh_attr_vertex_kernel(VolumeView vol, c
   }
 }
 
-template <class VX>
+// INDEXED: `blockTriangles` is blockVertex (per listed block its first unique vertex, one entry past the last block = nV), `triangles`
+// the unique vertices, and the attributes are stored per unique vertex
+template <class VX, bool INDEXED>
 __global__ void __launch_bounds__(256) mesh_attr_block_kernel(VolumeView vol, const int32_t* __restrict__ slots, const RenderCounters* __restrict__ lc,
                                                               const int32_t* __restrict__ blockTriangles, const float* __restrict__ triangles,
                                                               const uint32_t* __restrict__ totals, int capBlocks, float voxelSize, uint32_t what,
@@ -121,8 +128,13 @@ __global__ void __launch_bounds__(256) mesh_attr_block_kernel(VolumeView vol, co
   const bool wantColour = VX::kColor && (what & ITM_MESH_COLOURS);
   for (int b = blockIdx.x; b < nBlocks; b += gridDim.x) {
     // the block's triangles: [prefix(b), prefix(b + 1)), cut at the count a full buffer stops at
-    uint32_t t0 = (uint32_t)blockTriangles[b], t1 = (b + 1 < nBlocks) ? (uint32_t)blockTriangles[b + 1] : generated;
-    t0 = t0 < count ? t0 : count; t1 = t1 < count ? t1 : count;
+    uint32_t t0, t1;
+    if constexpr (INDEXED) {                                 // the unique vertices first seen in the block: [t0, t1)
+      t0 = (uint32_t)blockTriangles[b]; t1 = (uint32_t)blockTriangles[b + 1];
+    } else {
+      t0 = (uint32_t)blockTriangles[b]; t1 = (b + 1 < nBlocks) ? (uint32_t)blockTriangles[b + 1] : generated;
+      t0 = t0 < count ? t0 : count; t1 = t1 < count ? t1 : count;
+    }
     if (t0 == t1) continue;                                  // (uniform) no surface in this block: nothing is staged
     const HashEntry he = unpack_entry(vol.hash[slots[b]]);
     __syncthreads();                                         // previous block's LDS contents are no longer needed
@@ -150,9 +162,9 @@ __global__ void __launch_bounds__(256) mesh_attr_block_kernel(VolumeView vol, co
     }
     __syncthreads();
     const int ox = he.px * kBlockSide, oy = he.py * kBlockSide, oz = he.pz * kBlockSide;
-    const uint32_t nV = (t1 - t0) * 3u;
+    const uint32_t nV = INDEXED ? t1 - t0 : (t1 - t0) * 3u;
     for (uint32_t k = t; k < nV; k += 256) {
-      const size_t v = (size_t)t0 * 3 + k;
+      const size_t v = (INDEXED ? (size_t)t0 : (size_t)t0 * 3) + k;
       const float* p = triangles + 3 * v;
       const float px = p[0] / voxelSize, py = p[1] / voxelSize, pz = p[2] / voxelSize;
       const float bx = floorf(px), by = floorf(py), bz = floorf(pz);
@@ -213,7 +225,7 @@ int itm_mesh_attributes(const itm_scene* s, itm_mesh* m, int what, itm_stream st
     if (g_debug_mesh_attr_per_vertex)
       mesh_attr_vertex_kernel<VX><<<grid, 256, 0, st>>>(vol, m->triangles, m->totals, s->prm.voxelSize, (uint32_t)what, m->normals, m->colours);
     else
-      mesh_attr_block_kernel<VX><<<grid, 256, 0, st>>>(vol, m->slots, m->listCounters, m->blockTriangles, m->triangles, m->totals, m->capBlocks, s->prm.voxelSize,
+      mesh_attr_block_kernel<VX, false><<<grid, 256, 0, st>>>(vol, m->slots, m->listCounters, m->blockTriangles, m->triangles, m->totals, m->capBlocks, s->prm.voxelSize,
                                                       (uint32_t)what, m->normals, m->colours);
     return ITM_OK;
   });
@@ -237,6 +249,58 @@ int itm_mesh_download_attributes(const itm_mesh* m, float* normals_host, uint8_t
   hipStream_t st = as_stream(stream);
   if (n && normals_host) ITM_HIP(hipMemcpyAsync(normals_host, m->normals, (size_t)n * 36, hipMemcpyDeviceToHost, st));
   if (n && colours_host) ITM_HIP(hipMemcpyAsync(colours_host, m->colours, (size_t)n * 12, hipMemcpyDeviceToHost, st));
+  ITM_HIP(hipStreamSynchronize(st));
+  return ITM_OK;
+}
+
+// the attributes of the unique vertices of the indexed mesh: one evaluation per distinct position, through the staged kernel
+int itm_mesh_indexed_attributes(const itm_scene* s, itm_mesh* m, int what, itm_stream stream) {
+  if (!s || !m) return set_error(ITM_ERR_INVALID, "null argument");
+  if (m->scene != s) return set_error(ITM_ERR_INVALID, "mesh belongs to another scene");
+  if (what <= 0 || (what & ~(ITM_MESH_NORMALS | ITM_MESH_COLOURS))) return set_error(ITM_ERR_INVALID, "what: ITM_MESH_NORMALS, ITM_MESH_COLOURS or both");
+  if ((what & ITM_MESH_COLOURS) && !voxel_has_colour(s->cfg.voxelType))
+    return set_error(ITM_ERR_INVALID, "the scene's voxel type stores no colour: the mesh has no colour attribute");
+  if (!m->indexCurrent) return set_error(ITM_ERR_INVALID, "no index for this mesh: itm_mesh_index has not built it since the last itm_mesh_scene");
+  { const int rc = enter_scene(s, nullptr); if (rc) return rc; }
+  hipStream_t st = as_stream(stream);
+  if (m->noVertices == 0) { m->indexedAttrCurrent |= (uint32_t)what; return ITM_OK; }   // an empty index (dense scenes, nothing meshed): empty attributes
+  int rc;
+  if ((what & ITM_MESH_NORMALS) && (rc = grow_device((void**)&m->vertexNormals, &m->capVertexNormals, (size_t)m->noVertices * 3, 4, "vertex normals"))) {
+    m->indexedAttrCurrent &= ~(uint32_t)ITM_MESH_NORMALS;
+    return rc;
+  }
+  if ((what & ITM_MESH_COLOURS) && (rc = grow_device((void**)&m->vertexColours, &m->capVertexColours, (size_t)m->noVertices, 4, "vertex colours"))) {
+    m->indexedAttrCurrent &= ~(uint32_t)ITM_MESH_COLOURS;
+    return rc;
+  }
+  const VolumeView vol = make_volume(s);
+  const int grid = 256 * 8;
+  rc = dispatch_voxel(s->cfg.voxelType, [&](auto vx) {
+    using VX = decltype(vx);
+    mesh_attr_block_kernel<VX, true><<<grid, 256, 0, st>>>(vol, m->slots, m->listCounters, m->blockVertex, m->vertices, m->totals, m->capBlocks, s->prm.voxelSize,
+                                                          (uint32_t)what, m->vertexNormals, m->vertexColours);
+    return ITM_OK;
+  });
+  if (rc) return rc;
+  ITM_LAUNCH_CHECK();
+  m->indexedAttrCurrent |= (uint32_t)what;
+  return ITM_OK;
+}
+
+int itm_mesh_download_indexed_attributes(const itm_mesh* m, float* normals_host, uint8_t* colours_host, uint32_t capacityVertices,
+                                         uint32_t* noVertices, itm_stream stream) {
+  if (!m || !noVertices) return set_error(ITM_ERR_INVALID, "null argument");
+  if (!m->indexCurrent) return set_error(ITM_ERR_INVALID, "no index for this mesh: itm_mesh_index has not built it since the last itm_mesh_scene");
+  if (normals_host && !(m->indexedAttrCurrent & ITM_MESH_NORMALS))
+    return set_error(ITM_ERR_INVALID, "no normals for the indexed mesh: itm_mesh_indexed_attributes has not computed them since the last itm_mesh_index");
+  if (colours_host && !(m->indexedAttrCurrent & ITM_MESH_COLOURS))
+    return set_error(ITM_ERR_INVALID, "no colours for the indexed mesh: itm_mesh_indexed_attributes has not computed them since the last itm_mesh_index");
+  { const int rc = enter_scene(m->scene, nullptr); if (rc) return rc; }
+  *noVertices = m->noVertices;
+  const uint32_t n = m->noVertices < capacityVertices ? m->noVertices : capacityVertices;
+  hipStream_t st = as_stream(stream);
+  if (n && normals_host) ITM_HIP(hipMemcpyAsync(normals_host, m->vertexNormals, (size_t)n * 12, hipMemcpyDeviceToHost, st));
+  if (n && colours_host) ITM_HIP(hipMemcpyAsync(colours_host, m->vertexColours, (size_t)n * 4, hipMemcpyDeviceToHost, st));
   ITM_HIP(hipStreamSynchronize(st));
   return ITM_OK;
 }

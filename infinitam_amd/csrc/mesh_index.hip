@@ -1,0 +1,333 @@
+// mesh_index.hip -- the indexed form of the marching-cubes mesh: the triangle soup of itm_mesh_scene welded into shared vertices.
+//
+// The reference's ITMMesh is a buffer of independent triangles (Objects/ITMMesh.h:14-124); it has no indexed mesh.  This one is
+// defined in terms of that buffer: with s_j, j = 0 .. 3n - 1, the soup's vertices in buffer order,
+//   * two soup vertices are the same vertex iff their three floats have the same 96 bits (no tolerance, -0.0f != +0.0f);
+//   * first[k] = the smallest j that holds the k-th distinct position, first strictly ascending (unique vertices are numbered in the
+//     order of their first occurrence); vertices[k] = s_first[k];
+//   * faces[j] = the k with the position of s_j.  Every triangle is kept, also those whose corners coincide after welding, so
+//     vertices[faces] reproduces the soup bit for bit.
+// Nothing in the result depends on the order in which lanes ran.
+//
+// MI355X design: a hash set of uint32 representatives in HBM, open addressing with linear probing, at least two slots per soup
+// vertex (a power of two), so it cannot fill.
+//   1. mesh_index_insert_kernel: lane j hashes its 96 position bits; an empty slot is claimed with atomicCAS(slot, EMPTY, j); on a
+//      claimed slot the lane compares its position with the representative's (read from the triangle buffer): equal -> atomicMin
+//      (slot, j), different -> next slot.  The POSITION of a slot never changes once it is claimed, only its representative falls, so
+//      a stale read of a slot can at worst cause an atomicMin that changes nothing, and the table ends with min j per position
+//      whatever the order: that is `first`.
+//   2. mesh_index_resolve_kernel: every lane looks its position up again -> rep[j]; j is the first occurrence iff rep[j] == j; one
+//      count per chunk of 1024 soup vertices.
+//   3. mesh_index_scan_kernel: exclusive scan of the chunk counts by one workgroup; the sum is nV (read by the host: the vertex
+//      buffers are sized from it).
+//   4. mesh_index_compact_kernel: ordered compaction (workgroup scans, as the slot list of meshing.hip): the k-th first occurrence
+//      writes first[k], vertices[k] and its own faces[j] = k.
+//   5. mesh_index_faces_kernel: every other soup vertex takes faces[j] = faces[rep[j]].
+//   6. mesh_index_blocks_kernel: blockVertex[b] = the number of unique vertices first seen before block b's triangles, so that the
+//      vertices first seen in block b are the range [blockVertex[b], blockVertex[b + 1]) (itm_mesh_indexed_attributes stages per block).
+// ITM_DEBUG_MESH_INDEX_WEAK_HASH cuts the hash to 8 bits (256 start slots spread over the table, the last one 64 slots before its
+// end), so that probe chains hundreds of slots long and the wrap-around are exercised on small scenes.
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "itm_internal.h"
+#include "mesh_types.h"
+#include "wave_utils.h"
+
+namespace itm {
+
+int g_debug_mesh_index_weak_hash = 0;
+
+constexpr uint32_t kIndexEmpty = 0xffffffffu;
+constexpr int kIndexChunk = 1024;                 // soup vertices per workgroup of the counting and compacting passes
+constexpr size_t kIndexMinTable = 1024;
+
+__device__ inline uint32_t index_start_slot(uint32_t x, uint32_t y, uint32_t z, uint32_t mask, int weak) {
+  uint32_t h = x * 0x9E3779B1u ^ y * 0x85EBCA77u ^ z * 0xC2B2AE3Du;
+  h ^= h >> 15; h *= 0x2C1B3C6Du; h ^= h >> 12; h *= 0x297A2D39u; h ^= h >> 15;
+  if (weak) h = ((h & 0xffu) + 1u) * ((mask + 1u) >> 8) - 64u;      // 256 start slots; value 255 starts 64 slots before the table's end
+  return h & mask;
+}
+
+__device__ inline bool same_position(const uint32_t* __restrict__ soup, uint32_t r, uint32_t x, uint32_t y, uint32_t z) {
+  const uint32_t* q = soup + 3 * (size_t)r;
+  return q[0] == x && q[1] == y && q[2] == z;
+}
+
+__global__ void __launch_bounds__(256) mesh_index_insert_kernel(const uint32_t* __restrict__ soup, uint32_t nSoup, uint32_t* table, uint32_t mask, int weak) {
+  for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < nSoup; j += gridDim.x * 256u) {
+    const uint32_t x = soup[3 * (size_t)j], y = soup[3 * (size_t)j + 1], z = soup[3 * (size_t)j + 2];
+    uint32_t slot = index_start_slot(x, y, z, mask, weak);
+    // the table has at least twice as many slots as there are soup vertices: an empty slot is met before the probe comes round
+    for (uint32_t probe = 0; probe <= mask; ++probe, slot = (slot + 1u) & mask) {
+      uint32_t r = table[slot];
+      if (r == kIndexEmpty) {
+        r = atomicCAS(table + slot, kIndexEmpty, j);
+        if (r == kIndexEmpty) break;                                   // claimed for this position
+      }
+      if (r == j) break;
+      if (same_position(soup, r, x, y, z)) {
+        if (r > j) atomicMin(table + slot, j);
+        break;
+      }
+    }
+  }
+}
+
+// the representative of position (x, y, z) in the finished table
+__device__ inline uint32_t index_lookup(const uint32_t* __restrict__ soup, const uint32_t* __restrict__ table, uint32_t mask, int weak,
+                                        uint32_t x, uint32_t y, uint32_t z, uint32_t self) {
+  uint32_t slot = index_start_slot(x, y, z, mask, weak);
+  for (uint32_t probe = 0; probe <= mask; ++probe, slot = (slot + 1u) & mask) {
+    const uint32_t r = table[slot];
+    if (r == kIndexEmpty) break;                                       // (cannot happen: every position was inserted)
+    if (r == self || same_position(soup, r, x, y, z)) return r;
+  }
+  return self;
+}
+
+__global__ void __launch_bounds__(256) mesh_index_resolve_kernel(const uint32_t* __restrict__ soup, uint32_t nSoup, const uint32_t* __restrict__ table,
+                                                                 uint32_t mask, int weak, uint32_t* __restrict__ rep, uint32_t* __restrict__ chunkCount) {
+  __shared__ int lds[4];
+  int n = 0;
+#pragma unroll
+  for (int i = 0; i < kIndexChunk / 256; ++i) {
+    const uint32_t j = blockIdx.x * (uint32_t)kIndexChunk + i * 256u + threadIdx.x;
+    if (j < nSoup) {
+      const uint32_t r = index_lookup(soup, table, mask, weak, soup[3 * (size_t)j], soup[3 * (size_t)j + 1], soup[3 * (size_t)j + 2], j);
+      rep[j] = r;
+      n += (r == j) ? 1 : 0;
+    }
+  }
+  const int sum = block_reduce_sum<4>(n, lds);
+  if (threadIdx.x == 0) chunkCount[blockIdx.x] = (uint32_t)sum;
+}
+
+// exclusive scan of the chunk counts (in place) by one workgroup; chunks[slotOfTotal] = their sum = nV
+__global__ void __launch_bounds__(1024) mesh_index_scan_kernel(uint32_t* __restrict__ chunks, int nChunks, int slotOfTotal) {
+  __shared__ int lds[17];
+  __shared__ uint32_t carry;
+  if (threadIdx.x == 0) carry = 0u;
+  __syncthreads();
+  for (int base = 0; base < nChunks; base += 1024) {
+    const int i = base + threadIdx.x;
+    const int v = (i < nChunks) ? (int)chunks[i] : 0;
+    int total;
+    const int ex = block_exclusive_scan<16>(v, lds, &total);
+    const uint32_t c = carry;
+    if (i < nChunks) chunks[i] = c + (uint32_t)ex;
+    __syncthreads();
+    if (threadIdx.x == 0) carry = c + (uint32_t)total;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) chunks[slotOfTotal] = carry;
+}
+
+__global__ void __launch_bounds__(256) mesh_index_compact_kernel(const uint32_t* __restrict__ soup, uint32_t nSoup, const uint32_t* __restrict__ rep,
+                                                                 const uint32_t* __restrict__ chunkOffset, uint32_t nUnique, uint32_t* __restrict__ first,
+                                                                 uint32_t* __restrict__ vertices, uint32_t* __restrict__ faces) {
+  __shared__ int lds[5];
+  uint32_t base = chunkOffset[blockIdx.x];
+#pragma unroll
+  for (int i = 0; i < kIndexChunk / 256; ++i) {
+    const uint32_t j = blockIdx.x * (uint32_t)kIndexChunk + i * 256u + threadIdx.x;
+    const int flag = (j < nSoup && rep[j] == j) ? 1 : 0;
+    int total;
+    const int ex = block_exclusive_scan<4>(flag, lds, &total);
+    const uint32_t k = base + (uint32_t)ex;
+    if (flag && k < nUnique) {                                         // (k < nUnique always: nUnique is the sum of the flags)
+      first[k] = j;
+      vertices[3 * (size_t)k] = soup[3 * (size_t)j]; vertices[3 * (size_t)k + 1] = soup[3 * (size_t)j + 1]; vertices[3 * (size_t)k + 2] = soup[3 * (size_t)j + 2];
+      faces[j] = k;
+    }
+    base += (uint32_t)total;
+  }
+}
+
+// reads faces[] of first occurrences only (written by the launch before), writes faces[] of the others only
+__global__ void __launch_bounds__(256) mesh_index_faces_kernel(uint32_t nSoup, const uint32_t* __restrict__ rep, uint32_t* faces) {
+  for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < nSoup; j += gridDim.x * 256u) {
+    const uint32_t r = rep[j];
+    if (r != j && r < nSoup) faces[j] = faces[r];
+  }
+}
+
+__global__ void __launch_bounds__(256) mesh_index_blocks_kernel(const RenderCounters* __restrict__ lc, const int32_t* __restrict__ blockTriangles,
+                                                                const uint32_t* __restrict__ totals, int capBlocks, const uint32_t* __restrict__ first,
+                                                                uint32_t nUnique, int32_t* __restrict__ blockVertex) {
+  const int nBlocks = lc->noVisibleEntries < capBlocks ? lc->noVisibleEntries : capBlocks;
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b > nBlocks) return;
+  uint32_t lo = nUnique;
+  if (b < nBlocks) {
+    const uint32_t count = totals[1];
+    uint32_t t0 = (uint32_t)blockTriangles[b];
+    t0 = t0 < count ? t0 : count;
+    const uint32_t j0 = 3u * t0;                                       // lower bound of j0 in first[]
+    uint32_t hi = nUnique;
+    lo = 0u;
+    while (lo < hi) {
+      const uint32_t mid = lo + ((hi - lo) >> 1);
+      if (first[mid] < j0) lo = mid + 1u; else hi = mid;
+    }
+  }
+  blockVertex[b] = (int32_t)lo;
+}
+
+static int index_is_current(const itm_mesh* m) {
+  if (!m->indexCurrent) return set_error(ITM_ERR_INVALID, "no index for this mesh: itm_mesh_index has not built it since the last itm_mesh_scene");
+  return ITM_OK;
+}
+
+}  // namespace itm
+
+using namespace itm;
+
+extern "C" {
+
+int itm_mesh_index(itm_mesh* m, itm_stream stream) {
+  if (!m) return set_error(ITM_ERR_INVALID, "null mesh");
+  hipStream_t st = as_stream(stream);
+  uint32_t n = 0;
+  int rc = itm_mesh_info(m, &n, nullptr, nullptr, stream);
+  if (rc) return rc;
+  m->indexCurrent = false;
+  m->indexedAttrCurrent = 0;                                           // attributes of the unique vertices belong to the index that is replaced
+  m->noVertices = 0; m->noIndexedTriangles = n;
+  if (n == 0) { m->indexCurrent = true; return ITM_OK; }               // nothing meshed, or a dense scene: an empty index
+  const size_t nSoup = (size_t)n * 3;                                  // < 2^32: the buffer holds less than 2^32 / 36 triangles
+  if (nSoup >= 0x7fffffffull) return set_error(ITM_ERR_INVALID, "mesh too large to index");
+  size_t tableSize = kIndexMinTable;
+  while (tableSize < 2 * nSoup) tableSize <<= 1;                       // at least two slots per soup vertex: it cannot fill
+  const int nChunks = (int)((nSoup + kIndexChunk - 1) / kIndexChunk);
+  if ((rc = grow_device((void**)&m->indexTable, &m->capIndexTable, tableSize, 4, "mesh index table"))) return rc;
+  if ((rc = grow_device((void**)&m->rep, &m->capRep, nSoup, 4, "mesh index representatives"))) return rc;
+  if ((rc = grow_device((void**)&m->faces, &m->capFaces, nSoup, 4, "mesh faces"))) return rc;
+  if ((rc = grow_device((void**)&m->indexChunks, &m->capIndexChunks, (size_t)nChunks + 1, 4, "mesh index chunk counts"))) return rc;
+  const uint32_t* soup = (const uint32_t*)m->triangles;
+  const uint32_t mask = (uint32_t)(tableSize - 1);
+  const int weak = g_debug_mesh_index_weak_hash;
+  const int grid = 256 * 8;
+  ITM_HIP(hipMemsetAsync(m->indexTable, 0xff, tableSize * 4, st));
+  mesh_index_insert_kernel<<<grid, 256, 0, st>>>(soup, (uint32_t)nSoup, m->indexTable, mask, weak);
+  mesh_index_resolve_kernel<<<nChunks, 256, 0, st>>>(soup, (uint32_t)nSoup, m->indexTable, mask, weak, m->rep, m->indexChunks);
+  mesh_index_scan_kernel<<<1, 1024, 0, st>>>(m->indexChunks, nChunks, nChunks);
+  ITM_LAUNCH_CHECK();
+  uint32_t nV = 0;
+  ITM_HIP(hipMemcpyAsync(&nV, m->indexChunks + nChunks, 4, hipMemcpyDeviceToHost, st));
+  ITM_HIP(hipStreamSynchronize(st));
+  if (nV == 0 || nV > nSoup) return set_error(ITM_ERR_DEVICE, "mesh index: impossible vertex count");
+  if ((rc = grow_device((void**)&m->first, &m->capFirst, nV, 4, "mesh first occurrences"))) return rc;
+  if ((rc = grow_device((void**)&m->vertices, &m->capVertices, (size_t)nV * 3, 4, "mesh vertices"))) return rc;
+  mesh_index_compact_kernel<<<nChunks, 256, 0, st>>>(soup, (uint32_t)nSoup, m->rep, m->indexChunks, nV, m->first, (uint32_t*)m->vertices, m->faces);
+  mesh_index_faces_kernel<<<grid, 256, 0, st>>>((uint32_t)nSoup, m->rep, m->faces);
+  if (m->capBlocks > 0) {
+    if (!m->blockVertex) ITM_HIP(hipMalloc((void**)&m->blockVertex, ((size_t)m->capBlocks + 1) * 4));
+    mesh_index_blocks_kernel<<<(m->capBlocks + 1 + 255) / 256, 256, 0, st>>>(m->listCounters, m->blockTriangles, m->totals, m->capBlocks, m->first, nV, m->blockVertex);
+  }
+  ITM_LAUNCH_CHECK();
+  m->noVertices = nV;
+  m->indexCurrent = true;
+  return ITM_OK;
+}
+
+int itm_mesh_index_info(const itm_mesh* m, uint32_t* noVertices, uint32_t* noTriangles, const float** vertices_dev, const uint32_t** faces_dev,
+                        const uint32_t** first_dev, itm_stream stream) {
+  if (!m) return set_error(ITM_ERR_INVALID, "null mesh");
+  { const int rc = index_is_current(m); if (rc) return rc; }
+  ITM_HIP(hipStreamSynchronize(as_stream(stream)));
+  if (noVertices) *noVertices = m->noVertices;
+  if (noTriangles) *noTriangles = m->noIndexedTriangles;
+  if (vertices_dev) *vertices_dev = m->noVertices ? m->vertices : nullptr;
+  if (faces_dev) *faces_dev = m->noIndexedTriangles ? m->faces : nullptr;
+  if (first_dev) *first_dev = m->noVertices ? m->first : nullptr;
+  return ITM_OK;
+}
+
+int itm_mesh_download_indexed(const itm_mesh* m, float* vertices_host, uint32_t* first_host, uint32_t capacityVertices, uint32_t* faces_host,
+                              uint32_t capacityTriangles, uint32_t* noVertices, uint32_t* noTriangles, itm_stream stream) {
+  if (!m) return set_error(ITM_ERR_INVALID, "null mesh");
+  { const int rc = index_is_current(m); if (rc) return rc; }
+  if (noVertices) *noVertices = m->noVertices;
+  if (noTriangles) *noTriangles = m->noIndexedTriangles;
+  const uint32_t nv = m->noVertices < capacityVertices ? m->noVertices : capacityVertices;
+  const uint32_t nt = m->noIndexedTriangles < capacityTriangles ? m->noIndexedTriangles : capacityTriangles;
+  hipStream_t st = as_stream(stream);
+  if (nv && vertices_host) ITM_HIP(hipMemcpyAsync(vertices_host, m->vertices, (size_t)nv * 12, hipMemcpyDeviceToHost, st));
+  if (nv && first_host) ITM_HIP(hipMemcpyAsync(first_host, m->first, (size_t)nv * 4, hipMemcpyDeviceToHost, st));
+  if (nt && faces_host) ITM_HIP(hipMemcpyAsync(faces_host, m->faces, (size_t)nt * 12, hipMemcpyDeviceToHost, st));
+  ITM_HIP(hipStreamSynchronize(st));
+  return ITM_OK;
+}
+
+// the indexed mesh on the host, with the attributes of the unique vertices that are current
+static int fetch_indexed(const itm_mesh* m, std::vector<float>& vtx, std::vector<uint32_t>& faces, std::vector<float>* nrm, std::vector<uint8_t>* col,
+                         itm_stream stream) {
+  { const int rc = index_is_current(m); if (rc) return rc; }
+  { const int rc = enter_scene(m->scene, nullptr); if (rc) return rc; }
+  uint32_t nv = m->noVertices, nt = m->noIndexedTriangles;
+  vtx.resize((size_t)nv * 3); faces.resize((size_t)nt * 3);
+  int rc = itm_mesh_download_indexed(m, vtx.data(), nullptr, nv, faces.data(), nt, nullptr, nullptr, stream);
+  if (rc) return rc;
+  const bool withNormals = nrm && (m->indexedAttrCurrent & ITM_MESH_NORMALS), withColours = col && (m->indexedAttrCurrent & ITM_MESH_COLOURS);
+  if (withNormals) nrm->resize((size_t)nv * 3);
+  if (withColours) col->resize((size_t)nv * 4);
+  if (withNormals || withColours)
+    if ((rc = itm_mesh_download_indexed_attributes(m, withNormals ? nrm->data() : nullptr, withColours ? col->data() : nullptr, nv, &nv, stream))) return rc;
+  return ITM_OK;
+}
+
+// binary_little_endian PLY as itm_mesh_write_ply writes it, with one vertex per distinct position and the faces through the index
+int itm_mesh_write_ply_indexed(const itm_mesh* m, const char* path, itm_stream stream) {
+  if (!m || !path) return set_error(ITM_ERR_INVALID, "null argument");
+  std::vector<float> vtx, nrm;
+  std::vector<uint32_t> faces;
+  std::vector<uint8_t> col;
+  const int rc = fetch_indexed(m, vtx, faces, &nrm, &col, stream);
+  if (rc) return rc;
+  const size_t nv = m->noVertices, nt = m->noIndexedTriangles;
+  const bool withNormals = (m->indexedAttrCurrent & ITM_MESH_NORMALS) != 0, withColours = (m->indexedAttrCurrent & ITM_MESH_COLOURS) != 0;
+  std::string head = "ply\nformat binary_little_endian 1.0\ncomment itm-hip mesh\nelement vertex " + std::to_string((unsigned long long)nv) +
+                     "\nproperty float x\nproperty float y\nproperty float z\n";
+  if (withNormals) head += "property float nx\nproperty float ny\nproperty float nz\n";
+  if (withColours) head += "property uchar red\nproperty uchar green\nproperty uchar blue\n";
+  head += "element face " + std::to_string((unsigned long long)nt) + "\nproperty list uchar int vertex_indices\nend_header\n";
+  const size_t vertexBytes = 12 + (withNormals ? 12 : 0) + (withColours ? 3 : 0);
+  std::vector<uint8_t> body(nv * vertexBytes + nt * 13);
+  uint8_t* o = body.data();
+  for (size_t v = 0; v < nv; ++v) {
+    memcpy(o, &vtx[v * 3], 12); o += 12;
+    if (withNormals) { memcpy(o, &nrm[v * 3], 12); o += 12; }
+    if (withColours) { memcpy(o, &col[v * 4], 3); o += 3; }
+  }
+  for (size_t i = 0; i < nt; ++i) {
+    const int32_t idx[3] = {(int32_t)faces[i * 3 + 2], (int32_t)faces[i * 3 + 1], (int32_t)faces[i * 3]};
+    *o++ = 3;
+    memcpy(o, idx, 12); o += 12;
+  }
+  FILE* f = fopen(path, "wb");
+  if (!f) return set_error(ITM_ERR_INVALID, std::string("cannot create ") + path);
+  bool ok = fwrite(head.data(), 1, head.size(), f) == head.size();
+  ok = (body.empty() || fwrite(body.data(), 1, body.size(), f) == body.size()) && ok;
+  ok = (fclose(f) == 0) && ok;
+  return ok ? ITM_OK : set_error(ITM_ERR_INVALID, std::string("short write to ") + path);
+}
+
+// the format of ITMMesh::WriteOBJ (Objects/ITMMesh.h:34-62) with one "v" line per unique vertex; faces 1-based, winding reversed
+int itm_mesh_write_obj_indexed(const itm_mesh* m, const char* path, itm_stream stream) {
+  if (!m || !path) return set_error(ITM_ERR_INVALID, "null argument");
+  std::vector<float> vtx;
+  std::vector<uint32_t> faces;
+  const int rc = fetch_indexed(m, vtx, faces, nullptr, nullptr, stream);
+  if (rc) return rc;
+  FILE* f = fopen(path, "w+");
+  if (!f) return set_error(ITM_ERR_INVALID, std::string("cannot create ") + path);
+  for (size_t v = 0; v < m->noVertices; ++v) fprintf(f, "v %f %f %f\n", vtx[v * 3], vtx[v * 3 + 1], vtx[v * 3 + 2]);
+  for (size_t i = 0; i < m->noIndexedTriangles; ++i) fprintf(f, "f %u %u %u\n", faces[i * 3 + 2] + 1u, faces[i * 3 + 1] + 1u, faces[i * 3] + 1u);
+  const bool ok = fclose(f) == 0;
+  return ok ? ITM_OK : set_error(ITM_ERR_INVALID, std::string("short write to ") + path);
+}
+
+}  // extern "C"

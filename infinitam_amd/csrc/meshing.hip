@@ -189,6 +189,8 @@ static void free_mesh(itm_mesh* m) {
   (void)hipFree(m->triangles); (void)hipFree(m->slots); (void)hipFree(m->blockTriangles); (void)hipFree(m->flags);
   (void)hipFree(m->chunkCount); (void)hipFree(m->listCounters); (void)hipFree(m->totals);
   (void)hipFree(m->normals); (void)hipFree(m->colours);
+  (void)hipFree(m->vertices); (void)hipFree(m->faces); (void)hipFree(m->first); (void)hipFree(m->rep); (void)hipFree(m->indexTable);
+  (void)hipFree(m->indexChunks); (void)hipFree(m->blockVertex); (void)hipFree(m->vertexNormals); (void)hipFree(m->vertexColours);
   delete m;
 }
 
@@ -244,6 +246,7 @@ int itm_mesh_scene(const itm_scene* s, itm_mesh* m, itm_stream stream) {
   { const int rc = enter_scene(s, nullptr); if (rc) return rc; }
   hipStream_t st = as_stream(stream);
   m->attrCurrent = 0;                                          // vertex attributes belong to the mesh that is being replaced
+  m->indexCurrent = false; m->indexedAttrCurrent = 0;          // and so does the indexed form
   // mesh->triangles->Clear()
   ITM_HIP(hipMemsetAsync(m->triangles, 0, (size_t)m->maxTriangles * 36, st));
   ITM_HIP(hipMemsetAsync(m->totals, 0, 8, st));
