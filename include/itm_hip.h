@@ -330,6 +330,20 @@ int ITM_FN(update_view)(const int16_t* raw, int w, int h, int calibType, float c
                         int useBilateralFilter, int modelSensorNoise, float* depth_out, float* scratch,
                         float* normals, float* sigmaZ, itm_stream stream);
 
+/* ---- colour maps of the display path (ITMMainEngine::GetImage, Engine/ITMMainEngine.cpp:148-160) ----------------------
+ * IITMVisualisationEngine::DepthToUchar4 / WeightToUchar4 / NormalToUchar4  Engine/ITMVisualisationEngine.cpp:7-57, :82-107,
+ * :59-79 -- host loops there, kernels here.  All pointers are DEVICE pointers: src float[h*w], src4 float4[h*w], dst_rgba
+ * uchar4[h*w].  The result is the reference's byte for byte; every output pixel is written (0 where the reference leaves its
+ * cleared image untouched: the caller clears nothing).  Depth: the pixels > 0 are scaled between their minimum and maximum and
+ * coloured by the reference's ramp, alpha 255; weight: red / green from min / value, alpha 0; normal: 0.3 + (c + 1) * 0.35 per
+ * component where w >= 0, alpha 0.  Where the reference's float -> uchar conversion is undefined (a value outside [0, 256): a
+ * normal component beyond +-1, garbage) the value saturates to 0 / 255 and NaN gives 0.
+ * Stream-ordered like the view-builder calls, at most two launches, no allocation after the first call on a stream and nothing
+ * returns to the host: the limits stay in device memory, in words that belong to the call's stream. */
+int ITM_FN(depth_to_uchar4)(const float* src, uint8_t* dst_rgba, int w, int h, itm_stream stream);
+int ITM_FN(weight_to_uchar4)(const float* src, uint8_t* dst_rgba, int w, int h, itm_stream stream);
+int ITM_FN(normal_to_uchar4)(const float* src4, uint8_t* dst_rgba, int w, int h, itm_stream stream);
+
 /* ---- raw frames from the host: the first statement of ITMViewBuilder_CUDA::UpdateView, shortImage->SetFrom(rawDepthImage, CPU_TO_CUDA)
  * (Engine/DeviceSpecific/CUDA/ITMViewBuilder_CUDA.cu:53), a synchronous copy there.  A stager owns `slots` device images of w x h
  * shorts and a copy stream: itm_depth_stager_upload puts a frame (PINNED host memory) on the copy stream and returns at once -- up to

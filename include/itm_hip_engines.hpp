@@ -36,6 +36,27 @@ struct ITMVoxelBlockHash { static constexpr int kType = ITM_INDEX_HASH; };
 struct ITMPlainVoxelArray { static constexpr int kType = ITM_INDEX_DENSE; };
 
 struct Vector2i { int x, y; };
+struct Vector4u { uint8_t x, y, z, w; };
+
+// ITMUChar4Image (Utils/ITMLibDefines.h, ORUtils/Image.h) as far as ITMMainEngine::GetImage needs it: a host image of Vector4u
+class ITMUChar4Image {
+  std::vector<Vector4u> data;
+
+ public:
+  Vector2i noDims{0, 0};
+  size_t dataSize = 0;
+  ITMUChar4Image() {}
+  explicit ITMUChar4Image(Vector2i dims) { ChangeDims(dims); Clear(); }
+  // ORUtils/Image.h:50-59: a new size gives a new buffer; the pixels are the caller's to fill
+  void ChangeDims(Vector2i newDims) {
+    if (newDims.x == noDims.x && newDims.y == noDims.y) return;
+    noDims = newDims; dataSize = (size_t)newDims.x * (size_t)newDims.y;
+    data.assign(dataSize, Vector4u{0, 0, 0, 0});
+  }
+  void Clear(uint8_t defaultValue = 0) { if (dataSize) std::memset(data.data(), defaultValue, dataSize * sizeof(Vector4u)); }
+  Vector4u* GetData() { return data.data(); }
+  const Vector4u* GetData() const { return data.data(); }
+};
 
 // ITMPose: only the model-view matrix is needed by the path (Objects/ITMPose.h GetM()).
 struct ITMPose {
@@ -594,6 +615,8 @@ class ITMMainEngine_HIP {
   void *depthBuf = nullptr, *scratchBuf = nullptr, *normalBuf = nullptr, *sigmaBuf = nullptr, *pointsBuf = nullptr, *coloursBuf = nullptr;
   bool fusionActive = true, mainProcessingActive = true;
   itm_mesh* exportMesh = nullptr;      // created by the first SaveSceneTo* call
+  ITMRenderState* renderState_freeview = nullptr;      // created by the first free-camera GetImage
+  void* depthImageBuf = nullptr;                       // device uchar4 of the depth size: the coloured depth / uncertainty image of GetImage
 
  public:
   // calibType / c0 / c1: ITMDisparityCalib (0 = TRAFO_KINECT, 1 = TRAFO_AFFINE); sizes as ITMMainEngine's imgSize_rgb / imgSize_d
@@ -639,6 +662,7 @@ class ITMMainEngine_HIP {
   }
   ~ITMMainEngine_HIP() {
     itm_mesh_destroy(exportMesh);
+    delete renderState_freeview; itm_dev_free(depthImageBuf);
     delete renderState_live; delete trackingController; delete tracker; delete depthTracker; delete colourTracker; delete renTracker; delete wicpTracker; delete viewBuilder;
     for (void* p : {depthBuf, scratchBuf, normalBuf, sigmaBuf, pointsBuf, coloursBuf}) itm_dev_free(p);
   }
@@ -699,6 +723,91 @@ class ITMMainEngine_HIP {
   void turnOffIntegration() { fusionActive = false; }
   void turnOnMainProcessing() { mainProcessingActive = true; }
   void turnOffMainProcessing() { mainProcessingActive = false; }
+
+  // ITMMainEngine::GetImageType (Engine/ITMMainEngine.h:88-97)
+  enum GetImageType {
+    InfiniTAM_IMAGE_ORIGINAL_RGB,
+    InfiniTAM_IMAGE_ORIGINAL_DEPTH,
+    InfiniTAM_IMAGE_SCENERAYCAST,
+    InfiniTAM_IMAGE_FREECAMERA_SHADED,
+    InfiniTAM_IMAGE_FREECAMERA_COLOUR_FROM_VOLUME,
+    InfiniTAM_IMAGE_FREECAMERA_COLOUR_FROM_NORMAL,
+    InfiniTAM_IMAGE_UNKNOWN
+  };
+  // ITMMainEngine::GetImageSize (Engine/ITMMainEngine.cpp:129-132): the live render state's raycastImage->noDims
+  Vector2i GetImageSize() const { return renderState_live->imgSize; }
+
+  // The images of GetImage left in DEVICE memory: returns the device uchar4 image and its size, no host copy -- a host that displays
+  // through its own GPU path pays no PCIe trip.  Everything is submitted on the engine's stream (the default one); the pointer is the
+  // engine's or the view's and holds the image until the next ProcessFrame / GetImage call of the same type.  nullptr (size 0 x 0)
+  // before the first frame and for InfiniTAM_IMAGE_UNKNOWN.  freeviewSize: the size of a free-camera image (GetImage passes
+  // out->noDims); pose / intrinsics are read by the free-camera types only.
+  // Tracking and fusion are not disturbed: the free camera has a render state of its own, so the live visible list, range image and
+  // ICP maps stay as the frame left them; calls that name the scene launch what the library had recorded first (include/itm_hip.h).
+  const uint8_t* GetImageDevice(Vector2i* size, GetImageType getImageType, const ITMPose* pose = nullptr, const ITMIntrinsics* intrinsics = nullptr,
+                                Vector2i freeviewSize = Vector2i{0, 0}) {
+    *size = Vector2i{0, 0};
+    if (view.depth == nullptr) return nullptr;      // `if (view == NULL) return;`: no frame has been processed
+    switch (getImageType) {
+      case InfiniTAM_IMAGE_ORIGINAL_RGB:
+        *size = view.rgbSize;
+        return view.rgb;
+      case InfiniTAM_IMAGE_ORIGINAL_DEPTH: {
+        if (!depthImageBuf) check(itm_dev_malloc(&depthImageBuf, (size_t)view.depthSize.x * view.depthSize.y * 4), "malloc");
+        // WeightToUchar4 of the uncertainty image for the weighted ICP tracker (its 2-pixel border is the 0 the constructor cleared),
+        // DepthToUchar4 of the depth image otherwise -- on the device, where both images live
+        if (settings.trackerType == ITMLibSettings::TRACKER_WICP)
+          check(itm_weight_to_uchar4(view.depthUncertainty, (uint8_t*)depthImageBuf, view.depthSize.x, view.depthSize.y, nullptr), "WeightToUchar4");
+        else
+          check(itm_depth_to_uchar4(view.depth, (uint8_t*)depthImageBuf, view.depthSize.x, view.depthSize.y, nullptr), "DepthToUchar4");
+        *size = view.depthSize;
+        return (const uint8_t*)depthImageBuf;
+      }
+      case InfiniTAM_IMAGE_SCENERAYCAST:
+        check(itm_flush(scene.handle, renderState_live->handle, nullptr), "itm_flush");
+        *size = renderState_live->imgSize;
+        return (const uint8_t*)itm_buffer_ptr(scene.handle, renderState_live->handle, ITM_BUF_RAYCAST_IMAGE);
+      case InfiniTAM_IMAGE_FREECAMERA_SHADED:
+      case InfiniTAM_IMAGE_FREECAMERA_COLOUR_FROM_VOLUME:
+      case InfiniTAM_IMAGE_FREECAMERA_COLOUR_FROM_NORMAL: {
+        typedef ITMVisualisationEngine_HIP<TVoxel, TIndex> Vis;
+        typename Vis::RenderImageType type = Vis::RENDER_SHADED_GREYSCALE;
+        if (getImageType == InfiniTAM_IMAGE_FREECAMERA_COLOUR_FROM_VOLUME) type = Vis::RENDER_COLOUR_FROM_VOLUME;
+        else if (getImageType == InfiniTAM_IMAGE_FREECAMERA_COLOUR_FROM_NORMAL) type = Vis::RENDER_COLOUR_FROM_NORMAL;
+        if (!pose || !intrinsics) throw std::runtime_error("GetImage: the free camera needs a pose and intrinsics");
+        if (freeviewSize.x <= 0 || freeviewSize.y <= 0) throw std::runtime_error("GetImage: the free camera needs an image size");
+        // The reference creates renderState_freeview once, at the size of the first call, and never again
+        // (Engine/ITMMainEngine.cpp:178): a later call with an image of another size renders into the old one -- a latent bug
+        // there.  Here the state is recreated when the size differs.
+        if (renderState_freeview && (renderState_freeview->imgSize.x != freeviewSize.x || renderState_freeview->imgSize.y != freeviewSize.y)) {
+          check(itm_stream_synchronize(nullptr), "GetImage (free view)");      // nothing still renders into the state that goes away
+          delete renderState_freeview; renderState_freeview = nullptr;
+        }
+        if (renderState_freeview == nullptr) renderState_freeview = visualisationEngine.CreateRenderState(freeviewSize);
+        visualisationEngine.FindVisibleBlocks(pose, intrinsics, renderState_freeview);
+        visualisationEngine.CreateExpectedDepths(pose, intrinsics, renderState_freeview);
+        visualisationEngine.RenderImage(pose, intrinsics, renderState_freeview, nullptr, type);      // into renderState_freeview->raycastImage
+        *size = renderState_freeview->imgSize;
+        return (const uint8_t*)itm_buffer_ptr(scene.handle, renderState_freeview->handle, ITM_BUF_RAYCAST_IMAGE);
+      }
+      case InfiniTAM_IMAGE_UNKNOWN:
+        break;
+    }
+    return nullptr;
+  }
+
+  // ITMMainEngine::GetImage (Engine/ITMMainEngine.cpp:134-192), statement for statement: GetImageDevice plus one copy to the host
+  // and a stream synchronise.  Before the first frame `out` is not touched; InfiniTAM_IMAGE_UNKNOWN leaves it cleared.
+  void GetImage(ITMUChar4Image* out, GetImageType getImageType, const ITMPose* pose = nullptr, const ITMIntrinsics* intrinsics = nullptr) {
+    if (view.depth == nullptr) return;
+    out->Clear();
+    Vector2i size;
+    const uint8_t* image = GetImageDevice(&size, getImageType, pose, intrinsics, out->noDims);
+    if (!image) return;
+    out->ChangeDims(size);
+    check(itm_memcpy_d2h(out->GetData(), image, out->dataSize * sizeof(Vector4u), nullptr), "GetImage");
+    check(itm_stream_synchronize(nullptr), "GetImage");
+  }
 
   // ITMMainEngine::SaveSceneToMesh (Engine/ITMMainEngine.cpp:104-109): meshes the scene and writes it as binary STL
   void SaveSceneToMesh(const char* fileName) {

@@ -309,6 +309,10 @@ _HOST_IO_SIGS = {
     "mesh_download_indexed_attributes": (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(C.c_uint32), _P]),
     "mesh_write_ply_indexed": (C.c_int, [_P, C.c_char_p, _P]),
     "mesh_write_obj_indexed": (C.c_int, [_P, C.c_char_p, _P]),
+    # colour maps of the display path (product only: host loops in the reference, Engine/ITMVisualisationEngine.cpp:7-107)
+    "depth_to_uchar4": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
+    "weight_to_uchar4": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
+    "normal_to_uchar4": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
 }
 
 
@@ -794,6 +798,20 @@ class VisualisationEngine:
 
     def FindSurface(self, pose_M, intrinsics, renderState, stream=None):
         self._pose_call("find_surface", pose_M, intrinsics, renderState, stream)
+
+    # the static colour maps of IITMVisualisationEngine (Engine/ITMVisualisationEngine.cpp:19-107) on device images:
+    # dst uchar4[h*w], src float[h*w] (float4[h*w] for the normals), imgSize = (w, h)
+    def _image_map(self, name, dst: DevBuffer, src: DevBuffer, imgSize, stream):
+        self.s.be.check(self.s.be.fn[name](_P(src.ptr), _P(dst.ptr), int(imgSize[0]), int(imgSize[1]), _P(stream)), name)
+
+    def DepthToUchar4(self, dst: DevBuffer, src: DevBuffer, imgSize, stream=None):
+        self._image_map("depth_to_uchar4", dst, src, imgSize, stream)
+
+    def WeightToUchar4(self, dst: DevBuffer, src: DevBuffer, imgSize, stream=None):
+        self._image_map("weight_to_uchar4", dst, src, imgSize, stream)
+
+    def NormalToUchar4(self, dst: DevBuffer, src: DevBuffer, imgSize, stream=None):
+        self._image_map("normal_to_uchar4", dst, src, imgSize, stream)
 
     def CreatePointCloud(self, view: View, renderState, locations: DevBuffer, colours: DevBuffer, skipPoints=False, stream=None):
         vs = view.struct()

@@ -33,6 +33,19 @@ __device__ inline int wave_inclusive_scan(int v) {
 // sum over the wave, the same value in every lane
 __device__ inline int wave_reduce_sum(int v) { return __builtin_amdgcn_readlane(wave_inclusive_scan(v), kWave - 1); }
 
+// maximum of one unsigned per lane over the wave, the same value in every lane.  The steps of the scan with max for +: a lane
+// without a source reads 0, the identity of an unsigned maximum.
+__device__ inline unsigned wave_reduce_umax(unsigned v) {
+  auto step = [](unsigned a, int b) { return a > (unsigned)b ? a : (unsigned)b; };
+  v = step(v, dpp_int<0x111, 0xf, true>((int)v));
+  v = step(v, dpp_int<0x112, 0xf, true>((int)v));
+  v = step(v, dpp_int<0x114, 0xf, true>((int)v));
+  v = step(v, dpp_int<0x118, 0xf, true>((int)v));      // lane 15 of every row holds the row's maximum
+  v = step(v, dpp_int<0x142, 0xa, false>((int)v));
+  v = step(v, dpp_int<0x143, 0xc, false>((int)v));     // lane 63 holds the wave's
+  return (unsigned)__builtin_amdgcn_readlane((int)v, kWave - 1);
+}
+
 // Exclusive scan of one int per thread over a workgroup of NW waves (blockDim.x == NW*64).
 // `lds` needs NW+1 ints.  Returns the exclusive prefix; *total receives the workgroup sum.
 template <int NW>
