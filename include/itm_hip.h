@@ -698,6 +698,38 @@ int ITM_FN(global_cache_get)(const itm_scene* scene, int entry, void* dst_host, 
 /* hasStoredData[noTotalEntries] as bytes */
 int ITM_FN(global_cache_flags)(const itm_scene* scene, uint8_t* dst_host, size_t bytes);
 
+/* ---- scene merge: fuses scene `src` into scene `dst` on the same GPU (the shared-map merger the exchange above gathers for) ----------
+ * Not a reference operation: assembled from the reference's two-phase block allocation (with src's block positions in the place of
+ * ray steps) and its CombineVoxelInformation (src in the role of the stored block).  Requirements, else ITM_ERR_INVALID with the
+ * reason in itm_last_error and dst untouched: dst != src, same device, same voxelType and indexType, bit-equal voxelSize (mu and maxW
+ * may differ: dst's maxW is used); dense scenes: equal denseSize / denseOffset and srcSlots_dev == NULL.  Recorded calls of both
+ * scenes are launched first.  srcSlots_dev: NULL = every table slot of src, else a DEVICE list of n slots of src's table in any order
+ * (duplicates count once, an id outside the table is ITM_ERR_INVALID) -- a render state's visible list, a gathered exchange record.
+ *
+ * Hash index, sequential definition (the kernels reproduce it bit for bit):
+ *  1. Participants: the selected entries of src with ptr >= 0, in ascending src slot order.  Selected entries with ptr == -1 count in
+ *     srcWithoutBlock; empty slots are ignored.
+ *  2. Rounds.  Request: every participant whose position is not in dst (a matching entry has ptr >= -1; walk from hashIndex(pos) along
+ *     the offset chain) places a request -- ORDERED on the head if the head is empty (ptr < -1), else EXCESS on the chain's tail.
+ *     Requests on one target overwrite each other, the highest src slot wins, the others ask again next round.  Sweep over dst's slots
+ *     ascending: an ordered request is served iff lastFreeBlockId >= 0, an excess request iff also lastFreeExcessListId >= 0; a served
+ *     request takes allocList[lastFreeBlockId--] (and excessList[lastFreeExcessListId--]) and writes {pos, offset 0, ptr} (the tail's
+ *     offset = entry + 1) as AllocateSceneFromDepth does.  Unlike the frame sweep, a request that is not served consumes nothing and
+ *     moves no counter; a counter below -1 counts as empty and stays.  Rounds end after the first round without a request, or the
+ *     first that serves none: the participants still without a place then count in `unserved` (pool exhaustion is not an error).
+ *     considered = participants, alreadyPresent = those found in round 1, allocated = requests served, rounds = rounds run.
+ *  3. Combine: for every participant whose position is now in dst with ptr >= 0, all 512 voxels: dst = CombineVoxelInformation(src,
+ *     dst, dst's maxW); counted in `combined`.  Those found with ptr == -1 (swapped out of dst) count in dstSwappedOut and are left.
+ *  4. The occupancy bits, the directories and the sdf mirror of dst are what itm_upload of the same table and voxels would rebuild;
+ *     the request keys are zero again.  dst's render states, visible lists and swap states are not touched (new entries are not
+ *     visible until a frame sees them); src is never written.
+ * Dense index: every voxel of dst is combined with the voxel of src at the same index; considered = combined = 1.
+ * Synchronises `stream` once per round (the round's counts); the combine itself is enqueued.  `stats` (host) may be NULL. */
+typedef struct itm_merge_stats {
+  int32_t rounds, considered, alreadyPresent, allocated, combined, unserved, srcWithoutBlock, dstSwappedOut;
+} itm_merge_stats;
+int ITM_FN(scene_merge)(itm_scene* dst, const itm_scene* src, const int32_t* srcSlots_dev, int n, itm_merge_stats* stats, itm_stream stream);
+
 /* The acceleration structures a hash scene carries beside the reference's table (none of them part of the reference's state, all
  * derived from it): a block directory and a slot directory over a cube of 512^3 blocks, an sdf mirror over 256^3 blocks for the
  * short voxel types.  The cubes are NOT tied to the world origin: the first frame places them around its camera (the reference's

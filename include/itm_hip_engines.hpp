@@ -277,6 +277,28 @@ class ITMSwappingEngine_HIP {
   }
 };
 
+// Scene merge (itm_scene_merge; no reference class): fuses `src` into `dst` on the GPU -- the blocks src has are allocated in dst by the
+// reference's two-phase allocation, then every voxel is combined as the swapping engine combines a stored block (src in that role).
+// Same voxel type, index type and voxelSize; both scenes on one device.  srcVisible: a render state of src whose visible list selects
+// the blocks (nullptr: every block of src).  dst's render states are not touched; new blocks become visible when a frame sees them.
+template <class TVoxel, class TIndex>
+class ITMSceneMergeEngine_HIP {
+ public:
+  itm_stream stream = nullptr;
+  void MergeScene(ITMScene<TVoxel, TIndex>* dst, const ITMScene<TVoxel, TIndex>* src, const ITMRenderState* srcVisible = nullptr, itm_merge_stats* stats = nullptr) {
+    const int32_t* slots = nullptr;
+    int n = 0;
+    if (srcVisible) {
+      itm_counters c;
+      check(itm_get_counters(src->handle, srcVisible->handle, &c, stream), "MergeScene (visible list)");
+      slots = (const int32_t*)itm_buffer_ptr(src->handle, srcVisible->handle, ITM_BUF_VISIBLE_IDS);
+      n = c.noVisibleEntries;
+      if (!slots) throw std::runtime_error("MergeScene: the render state has no visible list");
+    }
+    check(itm_scene_merge(dst->handle, src->handle, slots, n, stats, stream), "MergeScene");
+  }
+};
+
 template <class TVoxel, class TIndex>
 class ITMDenseMapper_HIP {
   ITMSceneReconstructionEngine_HIP<TVoxel, TIndex> reco;
@@ -678,6 +700,11 @@ class ITMMainEngine_HIP {
   ITMView* GetView() { return &view; }
   ITMTrackingState* GetTrackingState() { return &trackingState; }
   ITMScene<TVoxel, TIndex>* GetScene() { return &scene; }
+  // Fuses the whole scene of `other` (same GPU, same voxel size) into this engine's scene (itm_scene_merge).  Tracking state, render
+  // states and `other` stay as they are: the merged blocks are seen by the next ProcessFrame whose view holds them.
+  void MergeSceneFrom(const ITMMainEngine_HIP& other, itm_merge_stats* stats = nullptr) {
+    ITMSceneMergeEngine_HIP<TVoxel, TIndex>().MergeScene(&scene, &other.scene, nullptr, stats);
+  }
   ITMRenderState* GetRenderState() { return renderState_live; }
   const ITMVisualisationEngine_HIP<TVoxel, TIndex>* GetVisualisationEngine() const { return &visualisationEngine; }
   const ITMViewBuilder_HIP* GetViewBuilder() const { return viewBuilder; }

@@ -157,6 +157,15 @@ class AccelInfo(C.Structure):
                 ("mirror_pages", C.c_int32), ("mirror_pages_mapped", C.c_int32)]
 
 
+class MergeStats(C.Structure):
+    """itm_merge_stats (include/itm_hip.h, itm_scene_merge)."""
+    _fields_ = [(n, C.c_int32) for n in ("rounds", "considered", "alreadyPresent", "allocated", "combined", "unserved",
+                                         "srcWithoutBlock", "dstSwappedOut")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class ItmError(RuntimeError):
     pass
 
@@ -313,6 +322,8 @@ _HOST_IO_SIGS = {
     "depth_to_uchar4": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     "weight_to_uchar4": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     "normal_to_uchar4": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
+    # scene merge (product only: no reference engine merges scenes)
+    "scene_merge": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(MergeStats), _P]),
 }
 
 
@@ -562,6 +573,26 @@ class Scene:
         has = C.c_int()
         self.be.check(self.be.fn["global_cache_get"](_P(self.h), int(entry), out.ctypes.data_as(_P), C.byref(has)), "global_cache_get")
         return out if has.value else None
+
+    def merge_from(self, src: "Scene", slots=None, stream=None) -> dict:
+        """itm_scene_merge: fuses `src` into this scene on the GPU and returns the statistics.  slots: None (every slot of src's
+        table), a DevBuffer of int32 table slots of src, or a numpy array of them (uploaded first)."""
+        keep = None
+        if slots is None:
+            ptr, n = None, 0
+        elif isinstance(slots, DevBuffer):
+            ptr, n = slots.ptr, slots.nbytes // 4
+        else:
+            arr = np.ascontiguousarray(np.asarray(slots, np.int32).reshape(-1))
+            keep = self.be.to_backend(arr, stream)
+            ptr, n = keep.ptr, len(arr)
+        st = MergeStats()
+        rc = self.be.fn["scene_merge"](_P(self.h), _P(src.h), _P(ptr), n, C.byref(st), _P(stream))
+        if keep is not None:
+            self.be.sync(stream)
+            keep.close()
+        self.be.check(rc, "scene_merge")
+        return st.as_dict()
 
     def accel_info(self) -> dict:
         """Sizes, placement and move count of the directory / mirror cubes (product library only)."""

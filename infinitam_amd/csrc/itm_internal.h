@@ -117,6 +117,9 @@ struct itm_scene {
   // the scene fails with ITM_ERR_DEVICE instead of going on with a state the reference can never be in.  Cleared by ResetScene.
   volatile int32_t* fatalHost = nullptr;   // hipHostMalloc (mapped)
   int32_t* fatalDev = nullptr;             // the same word as the device sees it
+  // itm_scene_merge with this scene as destination (merge.hip): per-call scratch, kept between calls
+  void* mergeScratch = nullptr;
+  size_t mergeScratchBytes = 0;
 };
 
 struct itm_render_state {

@@ -412,6 +412,7 @@ static void free_scene(itm_scene* s) {
   (void)hipFree(s->hash); (void)hipFree(s->excessList); (void)hipFree(s->vba); (void)hipFree(s->allocList);
   (void)hipFree(s->counters); (void)hipFree(s->headBits); (void)hipFree(s->allocKey); (void)hipFree(s->chunkReq); (void)hipFree(s->chunkVis); (void)hipFree(s->chunkGran); (void)hipFree(s->chunkSweepDone); (void)hipFree(s->chunkKeptGran);
   (void)hipFree(s->dirPtr); (void)hipFree(s->dirSlot); (void)hipFree(s->sdfMirror); (void)hipFree(s->org.mTable); (void)hipFree(s->org.mPages); (void)hipFree(s->depthTiles);
+  (void)hipFree(s->mergeScratch);
   delete s;
 }
 static void free_rs(itm_render_state* r) {
