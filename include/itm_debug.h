@@ -58,6 +58,30 @@ int ITM_FN(debug_div32767)(const float* in, float* out, int n, itm_stream stream
 int ITM_FN(debug_divide)(int mode, const float* a, const float* b, const float* r, float* out, int n, itm_stream stream);
 
 
+/* Read-only probes of the acceleration cubes of a hash scene (block directory, slot directory, sdf mirror: itm_types.h).  Both launch
+ * the scene's recorded, unflushed engine calls first, as a download does, and only read; a scene without directories, without a mirror
+ * or with a dense index reports "nothing" (no cube covers anything, every count is 0).  All pointers are HOST memory.
+ * itm_debug_accel_probe: for each of the n block positions (int32[n][3]) cells[i] = {the directory cube covers it, its dirPtr cell, its
+ * dirSlot cell (-1 where not covered), the mirror cube covers it, its page-table entry (paged form; -1 otherwise), the block has NO place
+ * in the mirror (outside the cube, page unmapped or unmappable, no mirror)} and values[i] = the 512 mirror values of the block in the
+ * block's own voxel order x + 8 y + 64 z as stored: int16 for the short voxel types, uint32 for the float types ("absent" -- -32768 /
+ * 0xffffffff -- where the block has no place). */
+#define ITM_ACCEL_PROBE_CELLS 6
+int ITM_FN(debug_accel_probe)(const itm_scene* scene, const int32_t* positions, int n, int32_t* cells, void* values, itm_stream stream);
+/* itm_debug_accel_census: a full pass over the cubes on the device.  mirror_blocks counts the blocks with at least one cell that is not
+ * "absent": over the whole cube (dense form) or over every page of the pool, mapped or not (paged form).  pageTable (may be null)
+ * receives the 4096 entries of the page table (-1 everywhere unless the mirror is paged); page_counter is the pool's raw counter. */
+typedef struct itm_accel_census {
+  int64_t directory_cells;       /* dirPtr cells != -1 */
+  int64_t slot_directory_cells;  /* dirSlot cells != -1 */
+  int64_t mirror_blocks;
+  int32_t page_counter;
+  int32_t mirror_form;           /* 0 none, 1 dense, 2 paged */
+  int32_t has_directory;
+  int32_t reserved;
+} itm_accel_census;
+int ITM_FN(debug_accel_census)(const itm_scene* scene, itm_accel_census* out, int32_t* pageTable, itm_stream stream);
+
 /* Test hook (host only, no device work): the tracker's host-side iteration (level schedule, accept / reject damping, SE(3)
  * update) driven by a caller-supplied evaluator of cost / gradient / Hessian, so that it can be checked on a machine without
  * a GPU against ITMDepthTracker::TrackCamera with the same evaluator.  `evaluate` returns 0 on success. */

@@ -157,6 +157,12 @@ class AccelInfo(C.Structure):
                 ("mirror_pages", C.c_int32), ("mirror_pages_mapped", C.c_int32)]
 
 
+class AccelCensus(C.Structure):
+    """itm_accel_census (include/itm_debug.h)."""
+    _fields_ = [("directory_cells", C.c_int64), ("slot_directory_cells", C.c_int64), ("mirror_blocks", C.c_int64),
+                ("page_counter", C.c_int32), ("mirror_form", C.c_int32), ("has_directory", C.c_int32), ("reserved", C.c_int32)]
+
+
 class MergeStats(C.Structure):
     """itm_merge_stats (include/itm_hip.h, itm_scene_merge)."""
     _fields_ = [(n, C.c_int32) for n in ("rounds", "considered", "alreadyPresent", "allocated", "combined", "unserved",
@@ -262,6 +268,9 @@ _HOST_IO_SIGS = {
     "debug_dense_classify_check": (C.c_int, [C.POINTER(C.c_int32), C.c_int]),
     "scene_accel_info": (C.c_int, [_P, C.POINTER(AccelInfo)]),
     "scene_set_deferred_fusion": (C.c_int, [_P, C.c_int]),
+    # read-only probes of the acceleration cubes (test hooks, product only)
+    "debug_accel_probe": (C.c_int, [_P, _P, C.c_int, _P, _P, _P]),
+    "debug_accel_census": (C.c_int, [_P, C.POINTER(AccelCensus), _P, _P]),
     "swap_integrate_global_into_local": (C.c_int, [_P, _P, _P]),
     "swap_save_to_global_memory": (C.c_int, [_P, _P, _P]),
     "global_cache_get": (C.c_int, [_P, C.c_int, _P, C.POINTER(C.c_int)]),
@@ -600,6 +609,30 @@ class Scene:
         self.be.check(self.be.fn["scene_accel_info"](_P(self.h), C.byref(a)), "scene_accel_info")
         return {"directory_bytes": a.directory_bytes, "slot_directory_bytes": a.slot_directory_bytes, "mirror_bytes": a.mirror_bytes,
                 "mirror_pages": a.mirror_pages, "mirror_pages_mapped": a.mirror_pages_mapped, "origin_directory": list(a.origin_directory), "origin_mirror": list(a.origin_mirror), "placed": bool(a.placed), "moves": a.moves}
+
+    def accel_probe(self, positions, stream=None) -> dict:
+        """itm_debug_accel_probe: what the directory cubes and the sdf mirror hold at the block positions (int32[n][3]).  Arrays over
+        the positions: dir_covered, dir_ptr, dir_slot, mirror_covered, page (the page-table entry, paged form), no_place, and
+        values[n][512] -- the mirror's raw bits in the block's own voxel order (int16 for the short voxel types, uint32 for the float
+        ones)."""
+        pos = np.ascontiguousarray(np.asarray(positions, np.int32).reshape(-1, 3))
+        n = len(pos)
+        cells = np.zeros((n, 6), np.int32)
+        values = np.zeros((n, 512), np.int16 if self.cfg.voxelType in (VOXEL_S, VOXEL_S_RGB) else np.uint32)
+        self.be.check(self.be.fn["debug_accel_probe"](_P(self.h), pos.ctypes.data_as(_P), n, cells.ctypes.data_as(_P), values.ctypes.data_as(_P), _P(stream)),
+                      "debug_accel_probe")
+        return {"dir_covered": cells[:, 0] != 0, "dir_ptr": cells[:, 1].copy(), "dir_slot": cells[:, 2].copy(), "mirror_covered": cells[:, 3] != 0,
+                "page": cells[:, 4].copy(), "no_place": cells[:, 5] != 0, "values": values}
+
+    def accel_census(self, stream=None) -> dict:
+        """itm_debug_accel_census: non-empty cells of the two directories, mirror blocks with a cell that is not "absent" (over the
+        whole dense cube / over every page of the pool), the 4096-entry page table and the pool's raw page counter."""
+        c = AccelCensus()
+        table = np.zeros(4096, np.int32)
+        self.be.check(self.be.fn["debug_accel_census"](_P(self.h), C.byref(c), table.ctypes.data_as(_P), _P(stream)), "debug_accel_census")
+        return {"directory_cells": int(c.directory_cells), "slot_directory_cells": int(c.slot_directory_cells), "mirror_blocks": int(c.mirror_blocks),
+                "page_counter": int(c.page_counter), "mirror_form": ("none", "dense", "paged")[c.mirror_form], "has_directory": bool(c.has_directory),
+                "page_table": table}
 
     def process_frame(self, view: View, rs: "RenderState", points: DevBuffer, normals: DevBuffer, stream=None):
         """ITMDenseMapper::ProcessFrame + ITMTrackingController::Prepare (Engine/ITMMainEngine.cpp:123-126)."""
