@@ -582,6 +582,25 @@ typedef struct itm_mesh itm_mesh;
 int ITM_FN(mesh_create)(const itm_scene* scene, uint32_t max_triangles, itm_mesh** out);
 int ITM_FN(mesh_destroy)(itm_mesh* mesh);
 int ITM_FN(mesh_scene)(const itm_scene* scene, itm_mesh* mesh, itm_stream stream);
+/* The mesh of the scene's volume whatever its index (the reference has no dense mesher; this one is defined by its per-cell function).
+ * Hash scenes: exactly itm_mesh_scene.  Dense scenes (ITMPlainVoxelArray: denseSize (sx, sy, sz), denseOffset, voxel (x, y, z) at
+ * x + y * sx + z * sx * sy):
+ *   bricks  the array is cut into bricks of 8^3 voxels by array index: brick (bx, by, bz) holds voxels 8b .. 8b + 7 clipped to the
+ *           array, nb = ceil(s / 8) per axis; sizes need not be multiples of 8.
+ *   order   bricks in ascending bx + by * nbx + bz * nbx * nby; inside a brick `for z for y for x` over the voxels it holds (the loop of
+ *           ITMMeshingEngine_CPU.cpp:39 on one block).
+ *   cell    buildVertList (DeviceAgnostic/ITMMeshingEngine.h:204-232) at the integer location L = (x, y, z) + denseOffset, the eight
+ *           corners read through the dense readVoxel (ITMRepresentationAccess.h:129-142): a corner outside the array is not found; a
+ *           corner that is not found or whose SDF_valueToFloat(sdf) == 1.0f kills the cell; corner positions are L + corner offset as
+ *           floats; sdfInterp with its three `< 0.00001f` early returns; triangles in the case table's order; every vertex times
+ *           voxelSize last.
+ *   buffer  as itm_mesh_scene: cleared first, the count stops at noMaxTriangles - 1, the last slot holds the last triangle generated.
+ * So a hash scene whose blocks hold the same voxels at the same global positions (default voxels where a brick sticks out of the array)
+ * gives the same triangles, block run for block run.  Like itm_mesh_scene the call replaces the mesh, makes attributes and index stale,
+ * and launches recorded engine calls first; itm_mesh_attributes, itm_mesh_index, itm_mesh_indexed_attributes, the downloads and the
+ * writers serve the result.  The per-brick buffers belong to the mesh and are allocated by the first call on a dense scene.  Three
+ * launches, no host round trip.  itm_mesh_scene itself stays empty for dense scenes, as in the reference. */
+int ITM_FN(mesh_volume)(const itm_scene* scene, itm_mesh* mesh, itm_stream stream);
 /* mesh->noTotalTriangles / noMaxTriangles / the triangle buffer; synchronises `stream`.  Any output pointer may be NULL. */
 int ITM_FN(mesh_info)(const itm_mesh* mesh, uint32_t* noTotalTriangles, uint32_t* noMaxTriangles,
                       const float** triangles, itm_stream stream);
@@ -599,8 +618,9 @@ int ITM_FN(mesh_write_stl)(const itm_mesh* mesh, const char* path, itm_stream st
  *   ITM_MESH_COLOURS  readFromSDF_color4u_interpolated(p) (:187-222) converted as drawPixelColour does
  *                     (DeviceAgnostic/ITMVisualisationEngine.h:270-279): (uchar)(c * 255.0f) per channel, alpha 255.  Scenes whose
  *                     voxel type stores no colour: ITM_ERR_INVALID.
- * `what` is one of them or both (further calls add to what is current).  itm_mesh_scene makes the attributes stale; their buffers
- * are allocated by the first call that needs them.  Dense scenes: an empty mesh, empty attributes. */
+ * `what` is one of them or both (further calls add to what is current).  itm_mesh_scene / itm_mesh_volume make the attributes stale; their
+ * buffers are allocated by the first call that needs them.  A dense scene after itm_mesh_scene: an empty mesh, empty attributes; after
+ * itm_mesh_volume: the attributes of its triangles, read through the voxel array. */
 #define ITM_MESH_NORMALS 1
 #define ITM_MESH_COLOURS 2
 int ITM_FN(mesh_attributes)(const itm_scene* scene, itm_mesh* mesh, int what, itm_stream stream);

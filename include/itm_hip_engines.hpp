@@ -841,6 +841,13 @@ class ITMMainEngine_HIP {
     MeshForExport(0);
     check(itm_mesh_write_stl(exportMesh, fileName, nullptr), "WriteSTL");
   }
+  // SaveSceneToMesh through itm_mesh_volume: also a dense scene (ITMPlainVoxelArray) gives its surface, meshed brick by brick;
+  // a hash scene gives the file SaveSceneToMesh writes
+  void SaveVolumeToMesh(const char* fileName) {
+    if (!exportMesh) check(itm_mesh_create(scene.handle, 0, &exportMesh), "itm_mesh_create");
+    check(itm_mesh_volume(scene.handle, exportMesh, nullptr), "MeshVolume");
+    check(itm_mesh_write_stl(exportMesh, fileName, nullptr), "WriteSTL");
+  }
   // the same mesh as a binary PLY with per-vertex normals and, for the voxel types that store colour, colours (itm_mesh_attributes)
   void SaveSceneToPLY(const char* fileName) {
     const bool colour = TVoxel::kType == ITM_VOXEL_S_RGB || TVoxel::kType == ITM_VOXEL_F_RGB;
@@ -912,6 +919,11 @@ class ITMMeshingEngine_HIP {
   itm_stream stream = nullptr;
   void MeshScene(ITMMesh* mesh, const ITMScene<TVoxel, TIndex>* scene) {
     check(itm_mesh_scene(scene->handle, mesh->handle, stream), "MeshScene");
+    check(itm_mesh_info(mesh->handle, &mesh->noTotalTriangles, nullptr, nullptr, stream), "itm_mesh_info");
+  }
+  // beyond the reference (its dense MeshScene is empty): itm_mesh_volume -- MeshScene for a hash scene, a dense scene brick by brick
+  void MeshVolume(ITMMesh* mesh, const ITMScene<TVoxel, TIndex>* scene) {
+    check(itm_mesh_volume(scene->handle, mesh->handle, stream), "MeshVolume");
     check(itm_mesh_info(mesh->handle, &mesh->noTotalTriangles, nullptr, nullptr, stream), "itm_mesh_info");
   }
 };

@@ -327,6 +327,8 @@ _HOST_IO_SIGS = {
     "mesh_download_indexed_attributes": (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(C.c_uint32), _P]),
     "mesh_write_ply_indexed": (C.c_int, [_P, C.c_char_p, _P]),
     "mesh_write_obj_indexed": (C.c_int, [_P, C.c_char_p, _P]),
+    # the mesh of either index type: dense volumes brick by brick (product only: the reference's dense MeshScene is empty)
+    "mesh_volume": (C.c_int, [_P, _P, _P]),
     # colour maps of the display path (product only: host loops in the reference, Engine/ITMVisualisationEngine.cpp:7-107)
     "depth_to_uchar4": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     "weight_to_uchar4": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
@@ -683,6 +685,10 @@ class Mesh:
 
     def MeshScene(self, stream=None):
         self.scene.be.check(self.scene.be.fn["mesh_scene"](_P(self.scene.h), _P(self.h), _P(stream)), "mesh_scene")
+
+    def MeshVolume(self, stream=None):
+        """itm_mesh_volume: MeshScene for a hash scene; a dense scene is meshed brick by brick (MeshScene leaves it empty)."""
+        self.scene.be.check(self.scene.be.fn["mesh_volume"](_P(self.scene.h), _P(self.h), _P(stream)), "mesh_volume")
 
     def info(self, stream=None):
         n, cap = C.c_uint32(), C.c_uint32()

@@ -87,27 +87,29 @@ __device__ inline uchar4 colour_bytes(float4 c) {   // drawPixelColour
   return make_uchar4((unsigned char)(c.x * 255.0f), (unsigned char)(c.y * 255.0f), (unsigned char)(c.z * 255.0f), 255);
 }
 
-// the attributes of vertex v through the hash (directory / mirror where they cover): the reference's functions as the renders use them
-template <class VX>
+// the attributes of vertex v through the hash (directory / mirror where they cover) or, DENSE, the voxel array: the reference's
+// functions as the renders use them
+template <class VX, bool DENSE = false>
 __device__ inline void vertex_global(const VolumeView& vol, size_t v, float px, float py, float pz, uint32_t what,
                                      float* __restrict__ normals, uchar4* __restrict__ colours) {
   if (what & ITM_MESH_NORMALS) {
     float gx, gy, gz;
-    sdf_gradient<VX, false>(vol, px, py, pz, gx, gy, gz);
+    sdf_gradient<VX, DENSE>(vol, px, py, pz, gx, gy, gz);
     store_normal(normals + 3 * v, gx, gy, gz);
   }
   if constexpr (VX::kColor) {
-    if (what & ITM_MESH_COLOURS) colours[v] = colour_bytes(colour_at<VX, false>(vol, px, py, pz));
+    if (what & ITM_MESH_COLOURS) colours[v] = colour_bytes(colour_at<VX, DENSE>(vol, px, py, pz));
   }
 }
 
-template <class VX>
-__global__ void __launch_bounds__(256) mesh_attr_vertex_kernel(VolumeView vol, const float* __restrict__ triangles, const uint32_t* __restrict__ totals,
+// one lane per vertex: the soup's (totals: three per triangle in the buffer) or, totals == nullptr, `nFixed` unique vertices
+template <class VX, bool DENSE>
+__global__ void __launch_bounds__(256) mesh_attr_vertex_kernel(VolumeView vol, const float* __restrict__ triangles, const uint32_t* __restrict__ totals, uint32_t nFixed,
                                                                float voxelSize, uint32_t what, float* __restrict__ normals, uchar4* __restrict__ colours) {
-  const size_t nVertices = (size_t)totals[1] * 3;
+  const size_t nVertices = totals ? (size_t)totals[1] * 3 : (size_t)nFixed;
   for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < nVertices; v += (size_t)gridDim.x * 256) {
     const float* p = triangles + 3 * v;
-    vertex_global<VX>(vol, v, p[0] / voxelSize, p[1] / voxelSize, p[2] / voxelSize, what, normals, colours);
+    vertex_global<VX, DENSE>(vol, v, p[0] / voxelSize, p[1] / voxelSize, p[2] / voxelSize, what, normals, colours);
   }
 }
 
@@ -209,7 +211,8 @@ int itm_mesh_attributes(const itm_scene* s, itm_mesh* m, int what, itm_stream st
     return set_error(ITM_ERR_INVALID, "the scene's voxel type stores no colour: the mesh has no colour attribute");
   { const int rc = enter_scene(s, nullptr); if (rc) return rc; }
   hipStream_t st = as_stream(stream);
-  if (s->cfg.indexType != ITM_INDEX_HASH) { m->attrCurrent |= (uint32_t)what; return ITM_OK; }   // dense scenes: an empty mesh, empty attributes
+  const bool dense = s->cfg.indexType != ITM_INDEX_HASH;
+  if (dense && !m->fromVolume) { m->attrCurrent |= (uint32_t)what; return ITM_OK; }   // a dense scene that itm_mesh_volume has not meshed: nothing meshed, empty attributes
   if ((what & ITM_MESH_NORMALS) && !m->normals) {
     const hipError_t e = hipMalloc((void**)&m->normals, (size_t)m->maxTriangles * 36);
     if (e != hipSuccess) { m->normals = nullptr; return hip_fail(e, "mesh normals", __FILE__, __LINE__); }
@@ -222,8 +225,10 @@ int itm_mesh_attributes(const itm_scene* s, itm_mesh* m, int what, itm_stream st
   const int grid = 256 * 8;
   const int rc = dispatch_voxel(s->cfg.voxelType, [&](auto vx) {
     using VX = decltype(vx);
-    if (g_debug_mesh_attr_per_vertex)
-      mesh_attr_vertex_kernel<VX><<<grid, 256, 0, st>>>(vol, m->triangles, m->totals, s->prm.voxelSize, (uint32_t)what, m->normals, m->colours);
+    if (dense)                                   // the mesh of itm_mesh_volume: every vertex through the voxel array
+      mesh_attr_vertex_kernel<VX, true><<<grid, 256, 0, st>>>(vol, m->triangles, m->totals, 0u, s->prm.voxelSize, (uint32_t)what, m->normals, m->colours);
+    else if (g_debug_mesh_attr_per_vertex)
+      mesh_attr_vertex_kernel<VX, false><<<grid, 256, 0, st>>>(vol, m->triangles, m->totals, 0u, s->prm.voxelSize, (uint32_t)what, m->normals, m->colours);
     else
       mesh_attr_block_kernel<VX, false><<<grid, 256, 0, st>>>(vol, m->slots, m->listCounters, m->blockTriangles, m->triangles, m->totals, m->capBlocks, s->prm.voxelSize,
                                                       (uint32_t)what, m->normals, m->colours);
@@ -277,8 +282,11 @@ int itm_mesh_indexed_attributes(const itm_scene* s, itm_mesh* m, int what, itm_s
   const int grid = 256 * 8;
   rc = dispatch_voxel(s->cfg.voxelType, [&](auto vx) {
     using VX = decltype(vx);
-    mesh_attr_block_kernel<VX, true><<<grid, 256, 0, st>>>(vol, m->slots, m->listCounters, m->blockVertex, m->vertices, m->totals, m->capBlocks, s->prm.voxelSize,
-                                                          (uint32_t)what, m->vertexNormals, m->vertexColours);
+    if (s->cfg.indexType != ITM_INDEX_HASH)      // the mesh of itm_mesh_volume on a dense scene: one lane per unique vertex
+      mesh_attr_vertex_kernel<VX, true><<<grid, 256, 0, st>>>(vol, m->vertices, nullptr, m->noVertices, s->prm.voxelSize, (uint32_t)what, m->vertexNormals, m->vertexColours);
+    else
+      mesh_attr_block_kernel<VX, true><<<grid, 256, 0, st>>>(vol, m->slots, m->listCounters, m->blockVertex, m->vertices, m->totals, m->capBlocks, s->prm.voxelSize,
+                                                            (uint32_t)what, m->vertexNormals, m->vertexColours);
     return ITM_OK;
   });
   if (rc) return rc;

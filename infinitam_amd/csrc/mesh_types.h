@@ -2,7 +2,10 @@
 // mesh_index.hip (the indexed form: shared vertices and faces).
 #pragma once
 
+#include <mutex>
+
 #include "itm_internal.h"
+#include "mc_tables.h"
 #include "shading_device.h"
 
 struct itm_mesh {
@@ -16,6 +19,12 @@ struct itm_mesh {
   itm::RenderCounters* listCounters = nullptr;   // noVisibleEntries = number of listed blocks
   uint32_t* totals = nullptr;        // [0] triangles generated, [1] noTotalTriangles (after the cap)
   int capBlocks = 0;
+  // itm_mesh_volume on a dense scene (mesh_dense.hip); allocated by the first such call
+  int32_t* brickCount = nullptr;     // per 8^3 brick of the array: triangle count
+  unsigned long long* brickBase = nullptr;   // per brick: triangles generated before it
+  int32_t* brickList = nullptr;      // the bricks that have triangles, ascending
+  int32_t* brickCounters = nullptr;  // [0] number of listed bricks; [2..3] triangles generated (64 bits)
+  bool fromVolume = false;           // the buffer holds the mesh itm_mesh_volume made of a dense scene; itm_mesh_scene clears it
   // vertex attributes of the triangles the last itm_mesh_scene left in the buffer (mesh_attributes.hip); allocated on first use
   float* normals = nullptr;          // 3 floats per vertex, 3 vertices per triangle, buffer order
   uchar4* colours = nullptr;         // one per vertex
@@ -40,6 +49,8 @@ struct itm_mesh {
 
 namespace itm {
 
+int launch_mesh_volume_dense(const itm_scene* s, itm_mesh* m, hipStream_t st);   // mesh_dense.hip
+
 // (re)allocates *p for `need` elements of `elem` bytes when the present capacity is smaller; the old contents are not kept
 inline int grow_device(void** p, size_t* cap, size_t need, size_t elem, const char* what) {
   if (need <= *cap) return ITM_OK;
@@ -48,6 +59,45 @@ inline int grow_device(void** p, size_t* cap, size_t need, size_t elem, const ch
   const hipError_t e = hipMalloc(p, need * elem);
   if (e != hipSuccess) { *p = nullptr; return hip_fail(e, what, __FILE__, __LINE__); }
   *cap = need;
+  return ITM_OK;
+}
+
+// ---- the per-cell pieces the hash mesher (meshing.hip) and the dense mesher (mesh_dense.hip) share: one copy, so the two cannot drift ----
+
+// which of the 12 edges a sign configuration crosses: an edge is crossed when its two corners have different signs
+__device__ inline uint32_t crossed_edges(uint32_t cube) {
+  uint32_t mask = 0;
+#pragma unroll
+  for (int e = 0; e < 12; ++e)
+    if (((cube >> kCubeEdge[e][0]) ^ (cube >> kCubeEdge[e][1])) & 1u) mask |= 1u << e;
+  return mask;
+}
+
+// sdfInterp (DeviceAgnostic/ITMMeshingEngine.h:194-201), per component; p1/p2 are integer-valued voxel coordinates
+__device__ inline void edge_vertex(const float* p1, const float* p2, float v1, float v2, float* out) {
+  if (fabsf(0.0f - v1) < 0.00001f) { out[0] = p1[0]; out[1] = p1[1]; out[2] = p1[2]; return; }
+  if (fabsf(0.0f - v2) < 0.00001f) { out[0] = p2[0]; out[1] = p2[1]; out[2] = p2[2]; return; }
+  if (fabsf(v1 - v2) < 0.00001f) { out[0] = p1[0]; out[1] = p1[1]; out[2] = p1[2]; return; }
+  const float t = (0.0f - v1) / (v2 - v1);
+  out[0] = p1[0] + t * (p2[0] - p1[0]);
+  out[1] = p1[1] + t * (p2[1] - p1[1]);
+  out[2] = p1[2] + t * (p2[2] - p1[2]);
+}
+
+// kTriangleCases into a translation unit's constant-memory table (a constant symbol belongs to its code object, so each mesher has
+// its own; TAG keeps their "done" flags apart): once per device, also when several host threads create meshes at the same time
+template <class TAG>
+inline int upload_case_table(const void* symbol) {
+  static std::mutex guard;
+  static bool done[64] = {};
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (dev < 0 || dev >= 64) dev = 0;
+  std::lock_guard<std::mutex> lock(guard);
+  if (!done[dev]) {
+    ITM_HIP(hipMemcpyToSymbol(symbol, kTriangleCases, sizeof(kTriangleCases)));
+    done[dev] = true;
+  }
   return ITM_OK;
 }
 

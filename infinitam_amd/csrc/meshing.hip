@@ -35,15 +35,6 @@ namespace itm {
 
 __device__ __constant__ uint64_t d_triangleCases[256];
 
-// which of the 12 edges a sign configuration crosses: an edge is crossed when its two corners have different signs
-__device__ inline uint32_t crossed_edges(uint32_t cube) {
-  uint32_t mask = 0;
-#pragma unroll
-  for (int e = 0; e < 12; ++e)
-    if (((cube >> kCubeEdge[e][0]) ^ (cube >> kCubeEdge[e][1])) & 1u) mask |= 1u << e;
-  return mask;
-}
-
 __global__ void __launch_bounds__(256) mesh_flag_kernel(const uint4* __restrict__ hash, int nEntries, uint8_t* __restrict__ flags, int32_t* __restrict__ chunkCount) {
   __shared__ int lds[4];
   const int chunk = blockIdx.x, tid = threadIdx.x;
@@ -58,17 +49,6 @@ __global__ void __launch_bounds__(256) mesh_flag_kernel(const uint4* __restrict_
   }
   const int sum = block_reduce_sum<4>(n, lds);
   if (tid == 0) chunkCount[chunk] = sum;
-}
-
-// sdfInterp (DeviceAgnostic/ITMMeshingEngine.h:194-201), per component; p1/p2 are integer-valued voxel coordinates
-__device__ inline void edge_vertex(const float* p1, const float* p2, float v1, float v2, float* out) {
-  if (fabsf(0.0f - v1) < 0.00001f) { out[0] = p1[0]; out[1] = p1[1]; out[2] = p1[2]; return; }
-  if (fabsf(0.0f - v2) < 0.00001f) { out[0] = p2[0]; out[1] = p2[1]; out[2] = p2[2]; return; }
-  if (fabsf(v1 - v2) < 0.00001f) { out[0] = p1[0]; out[1] = p1[1]; out[2] = p1[2]; return; }
-  const float t = (0.0f - v1) / (v2 - v1);
-  out[0] = p1[0] + t * (p2[0] - p1[0]);
-  out[1] = p1[1] + t * (p2[1] - p1[1]);
-  out[2] = p1[2] + t * (p2[2] - p1[2]);
 }
 
 template <class VX, bool WRITE>
@@ -189,25 +169,13 @@ static void free_mesh(itm_mesh* m) {
   (void)hipFree(m->triangles); (void)hipFree(m->slots); (void)hipFree(m->blockTriangles); (void)hipFree(m->flags);
   (void)hipFree(m->chunkCount); (void)hipFree(m->listCounters); (void)hipFree(m->totals);
   (void)hipFree(m->normals); (void)hipFree(m->colours);
+  (void)hipFree(m->brickCount); (void)hipFree(m->brickBase); (void)hipFree(m->brickList); (void)hipFree(m->brickCounters);
   (void)hipFree(m->vertices); (void)hipFree(m->faces); (void)hipFree(m->first); (void)hipFree(m->rep); (void)hipFree(m->indexTable);
   (void)hipFree(m->indexChunks); (void)hipFree(m->blockVertex); (void)hipFree(m->vertexNormals); (void)hipFree(m->vertexColours);
   delete m;
 }
 
-static int upload_tables() {
-  // once per device, also when several host threads create meshes at the same time
-  static std::mutex guard;
-  static bool done[64] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64) dev = 0;
-  std::lock_guard<std::mutex> lock(guard);
-  if (!done[dev]) {
-    ITM_HIP(hipMemcpyToSymbol(HIP_SYMBOL(d_triangleCases), kTriangleCases, sizeof(kTriangleCases)));
-    done[dev] = true;
-  }
-  return ITM_OK;
-}
+static int upload_tables() { return upload_case_table<struct HashMesherTable>(HIP_SYMBOL(d_triangleCases)); }
 
 }  // namespace itm
 
@@ -247,6 +215,7 @@ int itm_mesh_scene(const itm_scene* s, itm_mesh* m, itm_stream stream) {
   hipStream_t st = as_stream(stream);
   m->attrCurrent = 0;                                          // vertex attributes belong to the mesh that is being replaced
   m->indexCurrent = false; m->indexedAttrCurrent = 0;          // and so does the indexed form
+  m->fromVolume = false;
   // mesh->triangles->Clear()
   ITM_HIP(hipMemsetAsync(m->triangles, 0, (size_t)m->maxTriangles * 36, st));
   ITM_HIP(hipMemsetAsync(m->totals, 0, 8, st));
@@ -266,6 +235,18 @@ int itm_mesh_scene(const itm_scene* s, itm_mesh* m, itm_stream stream) {
   });
   if (rc) return rc;
   ITM_LAUNCH_CHECK();
+  return ITM_OK;
+}
+
+// The mesh of the scene's volume whatever its index: a hash scene as itm_mesh_scene, a dense scene brick by brick (mesh_dense.hip)
+int itm_mesh_volume(const itm_scene* s, itm_mesh* m, itm_stream stream) {
+  if (!s || !m) return set_error(ITM_ERR_INVALID, "null argument");
+  if (s->cfg.indexType == ITM_INDEX_HASH) return itm_mesh_scene(s, m, stream);
+  const int rc = itm_mesh_scene(s, m, stream);                 // checks, recorded calls, stale marks, cleared buffer and totals
+  if (rc) return rc;
+  const int rv = launch_mesh_volume_dense(s, m, as_stream(stream));
+  if (rv) return rv;
+  m->fromVolume = true;
   return ITM_OK;
 }
 

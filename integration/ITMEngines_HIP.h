@@ -468,14 +468,20 @@ class ITMMeshingEngine_HIP : public ITMMeshingEngine<TVoxel, TIndex> {
   const void* owner = nullptr;
  public:
   ~ITMMeshingEngine_HIP() { itm_mesh_destroy(dev); }
-  void MeshScene(ITMMesh* mesh, const ITMScene<TVoxel, TIndex>* scene) {
+  void MeshScene(ITMMesh* mesh, const ITMScene<TVoxel, TIndex>* scene) { Mesh(mesh, scene, false); }
+  // beyond the reference: itm_mesh_volume -- MeshScene for a hash scene, and the surface of a dense scene (ITMPlainVoxelArray),
+  // which MeshScene leaves empty as the reference does, meshed brick by brick
+  void MeshVolume(ITMMesh* mesh, const ITMScene<TVoxel, TIndex>* scene) { Mesh(mesh, scene, true); }
+ private:
+  void Mesh(ITMMesh* mesh, const ITMScene<TVoxel, TIndex>* scene, bool volume) {
     itm_scene* sc = HipSceneOf(scene);
     if (!dev || owner != scene) {
       itm_mesh_destroy(dev); dev = nullptr;
       HipCheck(itm_mesh_create(sc, ITMMesh::noMaxTriangles, &dev), "itm_mesh_create");
       owner = scene;
     }
-    HipCheck(itm_mesh_scene(sc, dev, 0), "itm_mesh_scene");
+    if (volume) HipCheck(itm_mesh_volume(sc, dev, 0), "itm_mesh_volume");
+    else HipCheck(itm_mesh_scene(sc, dev, 0), "itm_mesh_scene");
     uint32_t n = 0;
     mesh->triangles->Clear();
     HipCheck(itm_mesh_download(dev, (float*)mesh->triangles->GetData(MEMORYDEVICE_CPU), ITMMesh::noMaxTriangles, &n, 0), "itm_mesh_download");
