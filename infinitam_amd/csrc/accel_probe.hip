@@ -1,8 +1,10 @@
 // accel_probe.hip -- read-only test hooks over the acceleration cubes of a hash scene (include/itm_debug.h): what the block directory,
 // the slot directory and the sdf mirror hold at given block positions, and a census of everything they hold.  The invariant these
-// structures obey (itm_types.h, scene.hip) is kept by eight writers with their own copies of the bookkeeping; tests/accel_terms.py
-// restates it on the downloaded table and compares it with what these hooks read.  Nothing here writes scene memory, no product path
-// calls it, and a scene without directories / mirror (or a dense-indexed one) reports "nothing".
+// structures obey (accel_device.h, scene.hip) is kept by eight writers, all through AccelWriter; tests/accel_terms.py restates it on
+// the downloaded table and compares it with what these hooks read.  This file is the auditor: it keeps its own address arithmetic, its
+// own "absent" values and its own float predicate, and takes from accel_device.h only the constants and cell orders it checks against.
+// Nothing here writes scene memory, no product path calls it, and a scene without directories / mirror (or a dense-indexed one)
+// reports "nothing".
 #include <cstring>
 
 #include "itm_internal.h"

@@ -85,8 +85,7 @@ template <bool ACROSS>
 __device__ inline void sweep_chunk(const int chunk, int* lds, uint32_t* __restrict__ allocKey, const int2* __restrict__ chunkReq,
                                    int2* __restrict__ chunkReqNext, int numChunks, uint4* __restrict__ hash,
                                    const int32_t* __restrict__ excessList, const int32_t* __restrict__ allocList,
-                                   uint8_t* __restrict__ visT, const SceneCounters* __restrict__ counters,
-                                   uint32_t* __restrict__ headBits, int32_t* __restrict__ dirPtr, int32_t* __restrict__ dirSlot, void* __restrict__ sdfMirror,
+                                   uint8_t* __restrict__ visT, const SceneCounters* __restrict__ counters, const AccelWriter& aw,
                                    const float* __restrict__ depth, int lazy, const AllocParams& p) {
 
   const int tid = threadIdx.x;
@@ -161,17 +160,14 @@ __device__ inline void sweep_chunk(const int chunk, int* lds, uint32_t* __restri
         hash[p.bucketNum + off] = pack_entry(bx, by, bz, 0, ptr);
         if (ACROSS) __hip_atomic_store(&visT[p.bucketNum + off], (uint8_t)(lazy ? 0x81 : 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         else visT[p.bucketNum + off] = lazy ? 0x81 : 1;
-        directory_insert(dirPtr, dirSlot, p.org, bx, by, bz, ptr, p.bucketNum + off);
-        mirror_init_block(sdfMirror, p.mirrorFloat != 0, p.org, bx, by, bz);
+        aw.block_allocated_excess(p.bucketNum + off, bx, by, bz, ptr);
       }
     } else if (vbaIdx[k] >= 0) {
       int bx, by, bz;
       replay_block_pos(keys[k], depthOfKey[k], p, bx, by, bz);
       const int ptr = ptrNew[k];
       hash[slot] = pack_entry(bx, by, bz, 0, ptr);
-      atomicOr(&headBits[slot >> 5], 1u << (slot & 31));
-      directory_insert(dirPtr, dirSlot, p.org, bx, by, bz, ptr, slot);
-      mirror_init_block(sdfMirror, p.mirrorFloat != 0, p.org, bx, by, bz);
+      aw.block_allocated_head(slot, bx, by, bz, ptr);
     }
     allocKey[slot] = 0u;
   }
@@ -270,15 +266,14 @@ __device__ inline void share_excess_retests(int chunk, int numChunks, uint8_t* _
 __global__ void __launch_bounds__(256) allocate_sweep_kernel(uint32_t* __restrict__ allocKey, const int2* __restrict__ chunkReq,
                                                              int2* __restrict__ chunkReqNext, int numChunks, uint4* __restrict__ hash,
                                                              const int32_t* __restrict__ excessList, const int32_t* __restrict__ allocList,
-                                                             uint8_t* __restrict__ visT, const SceneCounters* __restrict__ counters,
-                                                             uint32_t* __restrict__ headBits, int32_t* __restrict__ dirPtr, int32_t* __restrict__ dirSlot, void* __restrict__ sdfMirror,
+                                                             uint8_t* __restrict__ visT, const SceneCounters* __restrict__ counters, AccelWriter aw,
                                                              const float* __restrict__ depth, int lazy, AllocParams p) {
   __shared__ int lds[8];
   // (The excess region's re-tests are NOT shared here although the idle workgroups are the same: with the count in a later launch the
   // verdicts would have to travel in the type bytes, and after ResetScene the render state's stale types sit on EMPTY slots -- slots
   // that this very launch may fill and mark "new", racing with the verdict's store.  Built, measured at +1 % for two or three scenes
   // per process, and caught by the second-life test one run in twelve; removed.)
-  sweep_chunk<false>((int)blockIdx.x, lds, allocKey, chunkReq, chunkReqNext, numChunks, hash, excessList, allocList, visT, counters, headBits, dirPtr, dirSlot, sdfMirror, depth, lazy, p);
+  sweep_chunk<false>((int)blockIdx.x, lds, allocKey, chunkReq, chunkReqNext, numChunks, hash, excessList, allocList, visT, counters, aw, depth, lazy, p);
 }
 
 // checkBlockVisibility<true> (DeviceAgnostic/ITMSceneReconstructionEngine.h:243-342): a corner outside the image but inside the image
@@ -406,8 +401,8 @@ __global__ void __launch_bounds__(256) visible_compact_kernel(const uint8_t* __r
 // excess requests -- almost all of them -- nobody waits.  The pool counters, which every sweep reads, are committed by the LAST
 // chunk after its look-back (all granules in = all sweeps done) instead of by chunk 0.
 struct SweepArgs {
-  uint32_t* allocKey; int2* chunkReqNext; const int32_t* excessList; const int32_t* allocList; uint32_t* headBits;
-  int32_t* dirPtr; int32_t* dirSlot; void* sdfMirror; const float* depth; int lazy;
+  uint32_t* allocKey; int2* chunkReqNext; const int32_t* excessList; const int32_t* allocList; AccelWriter aw;
+  const float* depth; int lazy;
   uint32_t* sweepDone;     // per chunk: the epoch of the launch whose sweep has placed the chunk's excess allocations
   unsigned long long* keptGran;      // per 32 slots of the excess region: {epoch, "kept" bits} of the shared re-tests
   int32_t* fatalDev;       // the scene's host-visible status word (alloc_device.h: raise_fatal)
@@ -509,8 +504,8 @@ __global__ void __launch_bounds__(256) visible_list_kernel(uint8_t* __restrict__
     }
   }
   if constexpr (SWEEP) {
-    sweep_chunk<true>(chunk, sweepLds, sw.allocKey, chunkReq, sw.chunkReqNext, numChunks, hash, sw.excessList, sw.allocList, visT, counters, sw.headBits,
-                      sw.dirPtr, sw.dirSlot, sw.sdfMirror, sw.depth, sw.lazy, p);
+    sweep_chunk<true>(chunk, sweepLds, sw.allocKey, chunkReq, sw.chunkReqNext, numChunks, hash, sw.excessList, sw.allocList, visT, counters, sw.aw,
+                      sw.depth, sw.lazy, p);
     if (chunkReq[chunk].y > 0) stamp_sweep(chunk);           // (uniform) only excess allocations are read by other workgroups of this launch
     if (excessRegion) {
       // every chunk that had excess requests (any index: no sweep waits for anything, so this cannot cycle) must be through
@@ -702,7 +697,6 @@ static int fill_params(const itm_scene* s, const float* M, const float* intr, in
   p.bucketNum = s->cfg.bucketNum;
   p.noTotalEntries = s->noTotalEntries;
   p.capIds = capIds;
-  p.mirrorFloat = (s->cfg.voxelType == ITM_VOXEL_F || s->cfg.voxelType == ITM_VOXEL_F_RGB) ? 1 : 0;
   p.org = s->org;
   p.useSwapping = s->cfg.useSwapping;
   int pixBits = 1;
@@ -814,14 +808,14 @@ int launch_sweep_stage(itm_scene* s, const itm_view* v, itm_render_state* rs, bo
     if (!fusedSweep) {
       KernelTimer ts(s, ITM_TK_ALLOC_SWEEP, st);
       allocate_sweep_kernel<<<nChunks, 256, 0, st>>>(s->allocKey, reqCur, reqNext, nChunks, s->hash, s->excessList, s->allocList,
-                                                     rs->visibleType, s->counters, s->headBits, s->dirPtr, s->dirSlot, s->sdfMirror, v->depth, lazy ? 1 : 0, p);
+                                                     rs->visibleType, s->counters, accel_writer(s), v->depth, lazy ? 1 : 0, p);
     }
     s->frameParity++;
   }
   KernelTimer tv(s, ITM_TK_VISIBLE_LIST, st);
   if (onePass) {
     const uint32_t epoch = ++s->listEpoch;
-    const SweepArgs sw{s->allocKey, reqNext, s->excessList, s->allocList, s->headBits, s->dirPtr, s->dirSlot, s->sdfMirror, v->depth, lazy ? 1 : 0, s->chunkSweepDone, s->chunkKeptGran,
+    const SweepArgs sw{s->allocKey, reqNext, s->excessList, s->allocList, accel_writer(s), v->depth, lazy ? 1 : 0, s->chunkSweepDone, s->chunkKeptGran,
                        s->fatalDev, fusedSweep ? g_debug_force_list_stuck - 1 : -1};
 #define ITM_VL(CM, LZ, SW) visible_list_kernel<CM, LZ, SW><<<nChunks, 256, 0, st>>>(rs->visibleType, s->hash, s->chunkGran, epoch, reqCur, nChunks, s->counters, rs->visibleIds, rs->capIds, rs->counters, p, sw)
     if (onlyVisible) { if (lazy) ITM_VL(false, true, false); else ITM_VL(false, false, false); }

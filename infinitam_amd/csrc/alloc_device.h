@@ -18,8 +18,7 @@ struct AllocParams {
   int noTotalEntries;
   int stepBits;
   int capIds;
-  int mirrorFloat;   // the sdf mirror holds floats (ITMVoxel_f / _f_rgb) rather than shorts
-  AccelOrigin org;   // where the block directory / slot directory / sdf mirror cubes lie (itm_types.h)
+  AccelOrigin org;   // where the slot directory's cube lies: read by the request stage only (the sweep's writer carries its own, accel_device.h)
   int useSwapping;   // scenes with a global cache: enlarged frustum for the re-test of the previous list (checkBlockVisibility<true>)
 };
 

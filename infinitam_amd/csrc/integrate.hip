@@ -9,7 +9,7 @@
 //
 // MI355X design: the hash kernel gives (block, 4 z-slices) to ONE WAVE -- four contiguous 64-voxel runs in flight together, then
 // four depth gathers together -- with 2 048 workgroups of 8 waves striding over the device-resident visible list, so no count is
-// read back; voxels of the short types are mirrored into the position-addressed sdf copy the ray caster reads (itm_types.h).
+// read back; voxels of the short types are mirrored into the position-addressed sdf copy the ray caster reads (accel_device.h).
 // The dense kernel streams the volume with 16-byte accesses (4 ITMVoxel_s per lane), culls whole columns of groups against the
 // frustum with two integer comparisons and writes only 128-bit groups that changed.  The depth map is small (1.2 MB) and stays in L2.
 #include <cmath>
@@ -266,14 +266,16 @@ __device__ inline void integrate_item(const HashEntry& he, int z0, int lane, typ
   const size_t vi = (size_t)(present ? he.ptr : 0) * kBlockVoxels + (size_t)z0 * 64 + lane;
   const float mx = (float)(he.px * kBlockSide + x) * p.voxelSize;
   const float my = (float)(he.py * kBlockSide + y) * p.voxelSize;
-  using MC = MirrorCodec<VX::kShort>;
+  // (a MIRROR-ONLY writer: the integration stores mirror values and nothing else, and the mirror's origin travels in FuseParams.  Only
+  // block_base_wave_uniform and store_sdf may be called on it -- no bitmap, no directories, and mirrorFloat is not consulted by either)
+  const AccelWriter aw{nullptr, nullptr, nullptr, sdfMirror, 0, p.org};
   size_t mbase = 0;
-  typename MC::T* mirror = nullptr;
+  bool mirror = false;
   // (the block's page was mapped when the block was allocated; the table entry is requested here, beside the voxels, and used at the end.
   // The float voxel types carry no mirror unless built with ITM_MIRROR_FLOAT_TYPES: their kernels do not carry its code either -- two
   // registers more and ITMVoxel_f_rgb drops from six waves per SIMD to five, 180 -> 203 us on BASELINE configs[4])
   if constexpr (VX::kShort || ITM_MIRROR_FLOAT_TYPES) {
-    if (sdfMirror && mirror_block_base<false>(p.org, he.px, he.py, he.pz, mbase)) mirror = (typename MC::T*)sdfMirror;
+    mirror = aw.block_base_wave_uniform<false>(he.px, he.py, he.pz, mbase);      // (one block per wave)
   }
   // stage 1: project every slice's voxel; stage 2: all depth pixels together; stage 3: update (+ colour), store what changed.
   // Stages 1 and 2 do not look at the voxels: the item's runs (requested by the caller) are still on their way while the wave projects
@@ -307,7 +309,7 @@ __device__ inline void integrate_item(const HashEntry& he, int z0, int lane, typ
     }
     if (touched) {
       VX::store(vba, vi + 64 * k, r[k]);
-      if (mirror) mirror[mbase + mirror_block_voxel((uint32_t)x, (uint32_t)y, (uint32_t)(z0 + k))] = MC::of(VX::raw_sdf(r[k]));     // sdf mirror (itm_types.h)
+      if (mirror) aw.store_sdf<VX>(mbase, mirror_block_voxel((uint32_t)x, (uint32_t)y, (uint32_t)(z0 + k)), VX::raw_sdf(r[k]));
     }
   }
 }
@@ -950,7 +952,7 @@ static bool make_column_cull(const FuseParams& p, const int* size, const int* of
 // fits four times in LDS; the caller checked can_fuse_projection and launches range_reduce afterwards).
 // what an integration of view `v` would be refused for (checked at once by the entry point that records the call, pending.hip)
 int validate_integrate(const itm_scene* s, const itm_view* v) {
-  const bool colour = (s->cfg.voxelType == ITM_VOXEL_S_RGB || s->cfg.voxelType == ITM_VOXEL_F_RGB);
+  const bool colour = voxel_has_colour(s->cfg.voxelType);
   if (colour && (!v->rgb || v->w_rgb <= 0 || v->h_rgb <= 0)) return set_error(ITM_ERR_INVALID, "colour voxels need an rgb image");
   return ITM_OK;
 }

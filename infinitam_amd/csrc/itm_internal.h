@@ -9,6 +9,7 @@
 #include "../../include/itm_hip.h"
 #include "../../include/itm_debug.h"      // the library implements the test hooks; hosts never see them
 #include "itm_types.h"
+#include "accel_device.h"
 
 namespace itm {
 
@@ -78,11 +79,11 @@ struct itm_scene {
   // proves that no block hashing to bucket b is allocated (excess entries hang off occupied heads),
   // which lets the ray caster skip empty space without touching the 16-byte entries.
   uint32_t* headBits = nullptr;   // uint32[bucketNum / 32]
-  // Block directory (itm_types.h): dirPtr[cell] = voxel-block index of the block at that position or -1, cells in brick-major
+  // Block directory (accel_device.h): dirPtr[cell] = voxel-block index of the block at that position or -1, cells in brick-major
   // order.  Maintained by the allocation sweep, rebuilt after uploads; an exact mirror of the table entries with ptr >= 0.
   int32_t* dirPtr = nullptr;      // int32[kDirCells]  (512 MB)
   int32_t* dirSlot = nullptr;     // int32[kDirCells]  (512 MB): table slot of the block at that position or -1 (request kernel)
-  void* sdfMirror = nullptr;      // the mirror's page pool: int16 / uint32 [mirrorPages * 64 * 512] (512 MB; hash scenes, itm_types.h) or nullptr;
+  void* sdfMirror = nullptr;      // the mirror's page pool: int16 / uint32 [mirrorPages * 64 * 512] (512 MB; hash scenes, accel_device.h) or nullptr;
                                   // its page table and page counter travel to the kernels inside `org` (AccelOrigin::mTable / mPages / mMaxPages)
   int mirrorPages = 0;
   // Where the two cubes lie (scene.hip, accel_place): re-placed around the camera when the view leaves them.  Invariant: the only
@@ -207,6 +208,8 @@ inline int dispatch_voxel(int voxelType, F&& f) {
   }
   return set_error(ITM_ERR_INVALID, "unknown voxel type");
 }
+inline bool voxel_is_float(int voxelType) { return voxelType == ITM_VOXEL_F || voxelType == ITM_VOXEL_F_RGB; }
+inline bool voxel_has_colour(int voxelType) { return voxelType == ITM_VOXEL_S_RGB || voxelType == ITM_VOXEL_F_RGB; }
 
 // ---- pending work of the entry points (pending.hip) --------------------------------------------------------------------------------
 // Launches, unfused and in call order, what the render state has recorded (no-op when nothing is).
@@ -247,7 +250,8 @@ int live_hash_scenes(int device);                                     // hash sc
 int accel_unfill(itm_scene* s, hipStream_t st);                      // empties the cubes through the table that filled them
 int accel_place(itm_scene* s, const float* invM, hipStream_t st);    // (re-)places the cubes around a view
 extern int g_debug_no_fused_projection;
-int rebuild_head_bits(itm_scene* s, hipStream_t st);   // occupancy bitmap AND block directory, from the table
+int accel_rebuild(itm_scene* s, hipStream_t st);       // occupancy bitmap, both directories and the sdf mirror, from the table
+AccelWriter accel_writer(const itm_scene* s);          // the scene's derived structures as kernels write them (accel_device.h)
 extern int g_debug_no_directory;
 int launch_request_stage(itm_scene* s, const itm_view* v, itm_render_state* rs, bool onlyVisible, bool fuseRangeInit, hipStream_t st);
 int launch_sweep_stage(itm_scene* s, const itm_view* v, itm_render_state* rs, bool onlyVisible, hipStream_t st);

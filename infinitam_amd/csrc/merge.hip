@@ -112,7 +112,7 @@ constexpr int kMergeSlotsPerThread = kSweepChunk / 256;  // 8
 // r < voxel blocks available -- it then takes allocList[last - r] and excessList[lastExcess - e].
 __global__ void __launch_bounds__(256) merge_sweep_kernel(uint32_t* __restrict__ allocKey, const int2* __restrict__ chunkCnt, uint4* __restrict__ hash, int noTotalEntries, int bucketNum,
                                                           const int32_t* __restrict__ excessList, const int32_t* __restrict__ allocList, const SceneCounters* __restrict__ counters,
-                                                          uint32_t* __restrict__ headBits, int32_t* __restrict__ dirPtr, int32_t* __restrict__ dirSlot, AccelOrigin org,
+                                                          AccelWriter aw,
                                                           const uint4* __restrict__ srcHash, int32_t* __restrict__ where, int32_t* __restrict__ stats) {
   __shared__ int lds[16];
   const int chunk = blockIdx.x, tid = threadIdx.x;
@@ -159,15 +159,16 @@ __global__ void __launch_bounds__(256) merge_sweep_kernel(uint32_t* __restrict__
     const HashEntry se = unpack_entry(srcHash[srcSlot]);
     const int ptr = allocList[lastFreeVBA - rank];
     int newSlot = slot;
-    if (excessBits & (1u << k)) {
+    const bool isHead = !(excessBits & (1u << k));
+    if (!isHead) {
       const int off = excessList[lastFreeExc - excRank[k]];
       if (off < 0 || bucketNum + off >= noTotalEntries) continue;        // (an uploaded excess list may hold anything)
       ((uint32_t*)&hash[slot])[2] = (uint32_t)(off + 1);                 // connect the chain tail to the child
       newSlot = bucketNum + off;
       ++servedExcess;
-    } else atomicOr(&headBits[slot >> 5], 1u << (slot & 31));
+    }
     hash[newSlot] = pack_entry(se.px, se.py, se.pz, 0, ptr);
-    directory_insert(dirPtr, dirSlot, org, se.px, se.py, se.pz, ptr, newSlot);
+    aw.block_listed(newSlot, isHead, se.px, se.py, se.pz, ptr);      // (the combine below stores the block's mirror values)
     where[srcSlot] = newSlot;
     ++servedBlocks;
   }
@@ -199,21 +200,16 @@ __global__ void __launch_bounds__(256) merge_list_kernel(const uint4* __restrict
 template <class VX>
 __global__ void __launch_bounds__(512) merge_combine_kernel(const int32_t* __restrict__ list, const uint4* __restrict__ srcHash, const void* __restrict__ srcVba,
                                                             const int32_t* __restrict__ where, const uint4* __restrict__ dstHash, void* __restrict__ dstVba, int maxW,
-                                                            void* __restrict__ mirror, AccelOrigin org) {
+                                                            AccelWriter aw) {
   const int srcSlot = list[blockIdx.x], t = threadIdx.x;
   const int sp = (int)srcHash[srcSlot].w;
   const HashEntry de = unpack_entry(dstHash[where[srcSlot]]);
-  // the block's place in the sdf mirror: one thread asks (and maps the page of a block allocated by this call), the workgroup hears
-  __shared__ size_t baseShared; __shared__ int okShared;
-  if (t == 0) { size_t b0 = 0; okShared = (mirror && mirror_block_base<true>(org, de.px, de.py, de.pz, b0)) ? 1 : 0; baseShared = b0; }
   const size_t vi = (size_t)de.ptr * kBlockVoxels + t;
   const typename VX::Reg r = combine_voxel<VX>(VX::load(srcVba, (size_t)sp * kBlockVoxels + t), VX::load(dstVba, vi), maxW);
   VX::store(dstVba, vi, r);
-  __syncthreads();
-  if (okShared) {
-    using MC = MirrorCodec<VX::kShort>;
-    ((typename MC::T*)mirror)[baseShared + mirror_block_lin((uint32_t)t)] = MC::of(VX::raw_sdf(r));
-  }
+  // the block's place in the sdf mirror (the page of a block allocated by this call is mapped here)
+  size_t mbase;
+  if (aw.block_base_workgroup<true>(de.px, de.py, de.pz, mbase)) aw.store_sdf<VX>(mbase, (uint32_t)t, VX::raw_sdf(r));
 }
 
 // dense index: voxel i of dst with voxel i of src
@@ -309,7 +305,7 @@ int itm_scene_merge(itm_scene* dst, const itm_scene* src, const int32_t* srcSlot
     else merge_request_kernel<false><<<reqGrid, 256, 0, st>>>(src->hash, src->noTotalEntries, sel, where, table, dst->allocKey, chunkCnt, dStats);
     ITM_LAUNCH_CHECK();
     merge_sweep_kernel<<<dst->numChunks, 256, 0, st>>>(dst->allocKey, chunkCnt, dst->hash, dst->noTotalEntries, dst->cfg.bucketNum, dst->excessList, dst->allocList, dst->counters,
-                                                       dst->headBits, dst->dirPtr, dst->dirSlot, dst->org, src->hash, where, dStats);
+                                                       accel_writer(dst), src->hash, where, dStats);
     ITM_LAUNCH_CHECK();
     merge_commit_kernel<<<1, 1, 0, st>>>(dst->counters, dStats);
     ITM_LAUNCH_CHECK();
@@ -328,7 +324,7 @@ int itm_scene_merge(itm_scene* dst, const itm_scene* src, const int32_t* srcSlot
     const int count = h[kMsListCount];
     const int rc = dispatch_voxel(dst->cfg.voxelType, [&](auto vx) {
       using VX = decltype(vx);
-      merge_combine_kernel<VX><<<count, 512, 0, st>>>(list, src->hash, src->vba, where, dst->hash, dst->vba, dst->prm.maxW, dst->sdfMirror, dst->org);
+      merge_combine_kernel<VX><<<count, 512, 0, st>>>(list, src->hash, src->vba, where, dst->hash, dst->vba, dst->prm.maxW, accel_writer(dst));
       return ITM_OK;
     });
     if (rc) return rc;

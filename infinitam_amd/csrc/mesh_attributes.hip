@@ -195,8 +195,6 @@ __global__ void __launch_bounds__(256) mesh_attr_block_kernel(VolumeView vol, co
   }
 }
 
-static bool voxel_has_colour(int voxelType) { return voxelType == ITM_VOXEL_S_RGB || voxelType == ITM_VOXEL_F_RGB; }
-
 }  // namespace itm
 
 using namespace itm;

@@ -7,6 +7,7 @@
 #pragma once
 
 #include "itm_types.h"
+#include "accel_device.h"
 #include <type_traits>
 
 #ifndef ITM_EXP_WAVE_TIMING
@@ -57,8 +58,8 @@ struct VolumeView {
   const uint32_t* headBits;  // occupancy bitmap of the ordered buckets (hash index only)
   uint32_t mask;       // bucketNum - 1
   int bucketNum;
-  const int32_t* dirPtr;    // block directory (itm_types.h); nullptr = walk the table (hash index only)
-  const void* sdfMirror;    // sdf by position (itm_types.h); nullptr = none (hash index only)
+  const int32_t* dirPtr;    // block directory (accel_device.h); nullptr = walk the table (hash index only)
+  const void* sdfMirror;    // sdf by position (accel_device.h); nullptr = none (hash index only)
   const int32_t* pageTable; // the mirror's page table as THIS kernel reads it: the scene's (memory) or the workgroup's copy in LDS (raycast_kernel)
   AccelOrigin org;          // where the directory / mirror cubes lie
   int sx, sy, sz;      // dense size
@@ -67,7 +68,7 @@ struct VolumeView {
   // (both forms compiled in: the free-view and helper kernels), see VolumeViewM
   static constexpr int kMirror = -1;
 };
-// The same view for a kernel that is compiled for ONE form of the mirror (0 none, 1 dense cube, 2 paged: itm_types.h): the ray-cast
+// The same view for a kernel that is compiled for ONE form of the mirror (0 none, 1 dense cube, 2 paged: accel_device.h): the ray-cast
 // kernel needs every tile of the image resident at once -- 4 800 waves, five per SIMD, at most 96 vector registers -- and with both
 // forms' address arithmetic alive it takes 104.  Every function below takes the view as a template parameter and folds the other form away.
 template <int M> struct VolumeViewM : VolumeView {
@@ -81,7 +82,7 @@ template <class VOL> __device__ inline bool mirror_is_paged(const VOL& vol) { re
 struct BlockCache {
   int bx, by, bz;
   int base;
-  // the mirror page the ray was last in (itm_types.h): table index and entry -- a page is 32 voxels wide, a step at most 8, so most
+  // the mirror page the ray was last in (accel_device.h): table index and entry -- a page is 32 voxels wide, a step at most 8, so most
   // steps find their page here and go straight to the one load that follows from the position
   uint32_t pageIdx;
   int page;
@@ -177,7 +178,7 @@ __device__ inline float read_raw_sdf(const VOL& vol, int px, int py, int pz, boo
     // exactly the voxels of the allocated blocks inside its cube)
     using MC = MirrorCodec<VX::kShort>;
     if (vol.sdfMirror && mirror_is_dense(vol)) {
-      // DENSE cube (itm_types.h): the load is unconditional (cell 0 for a lane outside the cube) and the general path below is skipped by
+      // DENSE cube (accel_device.h): the load is unconditional (cell 0 for a lane outside the cube) and the general path below is skipped by
       // a UNIFORM branch when every lane was served: no exec-mask bracket around the common case (ray cast 42.1 -> 41.7 us)
       const uint32_t ux = (uint32_t)((px >> 3) - vol.org.mx), uy = (uint32_t)((py >> 3) - vol.org.my), uz = (uint32_t)((pz >> 3) - vol.org.mz);
       const int mbits = mirror_dense_bits(vol.org);
@@ -196,7 +197,7 @@ __device__ inline float read_raw_sdf(const VOL& vol, int px, int py, int pz, boo
       // the page answers: with a value, or -- no block was ever allocated in it -- with "no block" and no further load
       const bool covered = inCube && page != kPageUnmappable;
       const bool mapped = covered && page >= 0;
-      typename MC::T v = VX::kShort ? (typename MC::T)-32768 : (typename MC::T)0xffffffffu;
+      typename MC::T v = MC::kAbsent;
       if (__any(mapped)) {
         const size_t mi = mapped ? mirror_element(page, mirror_in_page(vx, vy, vz)) : (size_t)0;
         const typename MC::T got = ((const typename MC::T*)vol.sdfMirror)[mi];
@@ -303,7 +304,7 @@ struct Corners {
           const uint32_t vx = (uint32_t)(ix - (vol.org.mx << 3)), vy = (uint32_t)(iy - (vol.org.my << 3)), vz = (uint32_t)(iz - (vol.org.mz << 3));
           const bool inCube = mirror_covers_voxel(vx, vy, vz) && mirror_covers_voxel(vx + 1u, vy + 1u, vz + 1u);
           const bool onePage = ((vx & kPageVoxMask) != kPageVoxMask) && ((vy & kPageVoxMask) != kPageVoxMask) && ((vz & kPageVoxMask) != kPageVoxMask);
-          const typename MC::T none = VX::kShort ? (typename MC::T)-32768 : (typename MC::T)0xffffffffu;
+          const typename MC::T none = MC::kAbsent;
           if (__all(inCube && onePage)) {
             const int page = mirror_page_of(vol, inCube, mirror_table_index_voxel(vx, vy, vz), cache);
             if (__all(page != kPageUnmappable)) {

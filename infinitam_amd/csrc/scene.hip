@@ -109,13 +109,13 @@ __global__ void __launch_bounds__(256) reset_voxels_s_x4_kernel(uint4* vba, size
 }
 
 __global__ void __launch_bounds__(256) reset_hash_kernel(uint4* hash, int nEntries, int32_t* excessList, int nExcess,
-                                                         int32_t* allocList, int nBlocks, uint32_t* allocKey, uint32_t* headBits, int nHeadWords,
+                                                         int32_t* allocList, int nBlocks, uint32_t* allocKey, AccelWriter aw, int nHeadWords,
                                                          int32_t* chunkReq, int nChunkReq, SceneCounters* counters) {
   int stride = gridDim.x * blockDim.x;
   int i0 = blockIdx.x * blockDim.x + threadIdx.x;
   const uint4 empty = pack_entry(0, 0, 0, 0, -2);
   for (int i = i0; i < nEntries; i += stride) { hash[i] = empty; allocKey[i] = 0u; }
-  for (int i = i0; i < nHeadWords; i += stride) headBits[i] = 0u;
+  for (int i = i0; i < nHeadWords; i += stride) aw.store_head_word(i, 0u);
   for (int i = i0; i < nExcess; i += stride) excessList[i] = i;
   for (int i = i0; i < nBlocks; i += stride) allocList[i] = i;
   for (int i = i0; i < nChunkReq; i += stride) chunkReq[i] = 0;
@@ -128,7 +128,7 @@ __global__ void __launch_bounds__(256) reset_hash_kernel(uint4* hash, int nEntri
 }
 
 // rebuilds the occupancy bitmap from the table (after an upload of hash entries)
-__global__ void __launch_bounds__(256) head_bits_kernel(const uint4* __restrict__ hash, uint32_t* __restrict__ headBits, int nWords, int bucketNum) {
+__global__ void __launch_bounds__(256) head_bits_kernel(const uint4* __restrict__ hash, AccelWriter aw, int nWords, int bucketNum) {
   const int w = blockIdx.x * blockDim.x + threadIdx.x;
   if (w >= nWords) return;
   uint32_t bits = 0;
@@ -136,46 +136,38 @@ __global__ void __launch_bounds__(256) head_bits_kernel(const uint4* __restrict_
     const int slot = w * 32 + k;
     if (slot < bucketNum && (int)hash[slot].w >= -1) bits |= 1u << k;      // -1: swapped out, its chain may still hold resident blocks
   }
-  headBits[w] = bits;
+  aw.store_head_word(w, bits);
 }
 
-// ---- the acceleration cubes (block directory, slot directory, sdf mirror; itm_types.h) -------------------------------------------
+// ---- the acceleration cubes (block directory, slot directory, sdf mirror; accel_device.h) ---------------------------------------
 // Invariant: the only non-empty cells are those of table entries with ptr >= 0, at the scene's current origin.  So the cubes are
 // emptied by visiting exactly those entries (unfill) -- before the table is reset or replaced, or before the origin moves -- and
 // filled again from the table afterwards: O(allocated blocks) instead of an 18 GB memset per ResetScene / upload / move.
 
 // FILL: records every entry with ptr >= 0 in the directory cubes; !FILL: empties those cells
 template <bool FILL>
-__global__ void __launch_bounds__(256) directory_fill_kernel(const uint4* __restrict__ hash, int nEntries, int32_t* __restrict__ dirPtr, int32_t* __restrict__ dirSlot, AccelOrigin org) {
+__global__ void __launch_bounds__(256) directory_fill_kernel(const uint4* __restrict__ hash, int nEntries, AccelWriter aw) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nEntries) return;
   const HashEntry e = unpack_entry(hash[i]);
   if (e.ptr < 0) return;
-  directory_insert(dirPtr, dirSlot, org, e.px, e.py, e.pz, FILL ? e.ptr : -1, FILL ? i : -1);
+  if (FILL) aw.directory_cells(i, e.px, e.py, e.pz, e.ptr);      // (the occupancy bits: head_bits_kernel; the mirror values: mirror_fill_kernel)
+  else aw.block_released(e.px, e.py, e.pz);
 }
 
 // FILL: the 512 sdf values of every allocated block inside the mirror cube, from the pool; !FILL: "no block here" in those cells.
 // One workgroup per entry.
 template <class VX, bool FILL>
-__global__ void __launch_bounds__(256) mirror_fill_kernel(const uint4* __restrict__ hash, int nEntries, const void* __restrict__ vba, void* __restrict__ mirror, AccelOrigin org, size_t numVoxels) {
-  using MC = MirrorCodec<VX::kShort>;
+__global__ void __launch_bounds__(256) mirror_fill_kernel(const uint4* __restrict__ hash, int nEntries, const void* __restrict__ vba, AccelWriter aw, size_t numVoxels) {
   for (int i = blockIdx.x; i < nEntries; i += gridDim.x) {
     const HashEntry e = unpack_entry(hash[i]);
     if (e.ptr < 0) continue;
     if (FILL && (size_t)e.ptr * kBlockVoxels + kBlockVoxels > numVoxels) continue;      // an uploaded table may hold anything
-    // (FILL maps the block's page if need be: one thread asks, the workgroup hears the answer)
-    __shared__ size_t baseShared; __shared__ int okShared;
-    __syncthreads();
-    if (threadIdx.x == 0) { size_t b0 = 0; okShared = mirror_block_base<FILL>(org, e.px, e.py, e.pz, b0) ? 1 : 0; baseShared = b0; }
-    __syncthreads();
-    if (!okShared) continue;
-    const size_t base = baseShared;
+    size_t base;
+    if (!aw.block_base_workgroup<FILL>(e.px, e.py, e.pz, base)) continue;      // (FILL maps the block's page if need be)
     for (int t = threadIdx.x; t < kBlockVoxels; t += 256) {
-      typename MC::T v;
-      if constexpr (FILL) v = MC::of(VX::load_raw_sdf(vba, (size_t)e.ptr * kBlockVoxels + t));
-      else if constexpr (VX::kShort) v = (typename MC::T)-32768;
-      else v = (typename MC::T)0xffffffffu;
-      ((typename MC::T*)mirror)[base + mirror_block_lin((uint32_t)t)] = v;
+      if constexpr (FILL) aw.store_sdf<VX>(base, (uint32_t)t, VX::load_raw_sdf(vba, (size_t)e.ptr * kBlockVoxels + t));
+      else aw.store_absent<VX>(base, (uint32_t)t);
     }
   }
 }
@@ -183,13 +175,21 @@ __global__ void __launch_bounds__(256) mirror_fill_kernel(const uint4* __restric
 #ifndef ITM_MIRROR_FLOAT_TYPES
 #define ITM_MIRROR_FLOAT_TYPES 0
 #endif
-static bool mirror_is_float(const itm_scene* s) { return s->cfg.voxelType == ITM_VOXEL_F || s->cfg.voxelType == ITM_VOXEL_F_RGB; }
-// side of the mirror's cube in blocks, and half of it: the DENSE form's is chosen per scene (itm_types.h, mirror_dense_bits)
+static bool mirror_is_float(const itm_scene* s) { return voxel_is_float(s->cfg.voxelType); }
+// side of the mirror's cube in blocks, and half of it: the DENSE form's is chosen per scene (accel_device.h, mirror_dense_bits)
 static int mirror_side(const itm_scene* s) { return s->org.mMaxPages < 0 ? (1 << mirror_dense_bits(s->org)) : kMirrorSide; }
-static size_t mirror_dense_cells(int bits) { return (size_t)1 << (3 * bits); }
+// voxels the mirror stores, by AccelOrigin::mMaxPages: < 0 the dense cube of 2^-form blocks per side, > 0 a pool of that many pages
+static size_t mirror_voxels(int form) { return (form < 0 ? (size_t)1 << (3 * -form) : (size_t)form * kPageBlocks) * kBlockVoxels; }
+static size_t mirror_voxels(const itm_scene* s) { return mirror_voxels(s->org.mMaxPages); }
+
+// The one place that assembles the writer of a scene's derived structures (accel_device.h).
+AccelWriter accel_writer(const itm_scene* s) {
+  return AccelWriter{s->headBits, s->dirPtr, s->dirSlot, s->sdfMirror, mirror_is_float(s) ? 1 : 0, s->org};
+}
+
 // every voxel of every page of the pool "no block here" (-32768 per short, all ones per float), no page handed out (scene creation only)
 static hipError_t mirror_clear(itm_scene* s, hipStream_t st) {
-  const size_t voxels = s->org.mMaxPages < 0 ? mirror_dense_cells(mirror_dense_bits(s->org)) * 512 : (size_t)s->mirrorPages * kPageBlocks * 512;
+  const size_t voxels = mirror_voxels(s);
   hipError_t e = mirror_is_float(s) ? hipMemsetAsync(s->sdfMirror, 0xff, voxels * 4, st) : hipMemsetD16Async((unsigned short*)s->sdfMirror, (unsigned short)0x8000, voxels, st);
   if (e == hipSuccess && s->org.mTable) e = hipMemsetAsync(s->org.mTable, 0xff, kMirrorTableCells * 4, st);
   if (e == hipSuccess && s->org.mPages) e = hipMemsetAsync(s->org.mPages, 0, 4, st);
@@ -201,13 +201,13 @@ static int mirror_pass(itm_scene* s, hipStream_t st) {
   if (!s->sdfMirror) return ITM_OK;
   int rc = dispatch_voxel(s->cfg.voxelType, [&](auto vx) {
     using VX = decltype(vx);
-    mirror_fill_kernel<VX, FILL><<<4096, 256, 0, st>>>(s->hash, s->noTotalEntries, s->vba, s->sdfMirror, s->org, s->numVoxels);
+    mirror_fill_kernel<VX, FILL><<<4096, 256, 0, st>>>(s->hash, s->noTotalEntries, s->vba, accel_writer(s), s->numVoxels);
     return ITM_OK;
   });
   if (rc) return rc;
   ITM_LAUNCH_CHECK();
   if (!FILL && s->org.mTable) {
-    // every mapped page is all "absent" again (the invariant of itm_types.h): the pool is as good as new
+    // every mapped page is all "absent" again (the invariant of accel_device.h): the pool is as good as new
     ITM_HIP(hipMemsetAsync(s->org.mTable, 0xff, kMirrorTableCells * 4, st));
     ITM_HIP(hipMemsetAsync(s->org.mPages, 0, 4, st));
   }
@@ -216,7 +216,7 @@ static int mirror_pass(itm_scene* s, hipStream_t st) {
 template <bool FILL>
 static int directory_pass(itm_scene* s, hipStream_t st) {
   if (!s->dirPtr) return ITM_OK;
-  directory_fill_kernel<FILL><<<(s->noTotalEntries + 255) / 256, 256, 0, st>>>(s->hash, s->noTotalEntries, s->dirPtr, s->dirSlot, s->org);
+  directory_fill_kernel<FILL><<<(s->noTotalEntries + 255) / 256, 256, 0, st>>>(s->hash, s->noTotalEntries, accel_writer(s));
   ITM_LAUNCH_CHECK();
   return ITM_OK;
 }
@@ -232,10 +232,10 @@ int accel_unfill(itm_scene* s, hipStream_t st) {
 }
 
 // occupancy bitmap AND both cubes, from the table (after the table was replaced: accel_unfill ran before the replacement)
-int rebuild_head_bits(itm_scene* s, hipStream_t st) {
+int accel_rebuild(itm_scene* s, hipStream_t st) {
   if (!s->headBits) return ITM_OK;
   const int nWords = (s->cfg.bucketNum + 31) / 32;
-  head_bits_kernel<<<(nWords + 255) / 256, 256, 0, st>>>(s->hash, s->headBits, nWords, s->cfg.bucketNum);
+  head_bits_kernel<<<(nWords + 255) / 256, 256, 0, st>>>(s->hash, accel_writer(s), nWords, s->cfg.bucketNum);
   ITM_LAUNCH_CHECK();
   int rc = directory_pass<true>(s, st);
   if (rc) return rc;
@@ -565,7 +565,7 @@ int itm_scene_create(const itm_scene_config* cfg_in, const itm_scene_params* prm
     if (hipMalloc((void**)&s->dirPtr, kDirCells * 4) != hipSuccess) { s->dirPtr = nullptr; (void)hipGetLastError(); }
     else if (hipMalloc((void**)&s->dirSlot, kDirCells * 4) != hipSuccess) { (void)hipFree(s->dirPtr); s->dirPtr = nullptr; s->dirSlot = nullptr; (void)hipGetLastError(); }
   }
-  // The sdf mirror is an accelerator, in one of two forms (itm_types.h): DENSE -- the whole cube of 256^3 blocks, 17 GB, the faster one
+  // The sdf mirror is an accelerator, in one of two forms (accel_device.h): DENSE -- the whole cube of 256^3 blocks, 17 GB, the faster one
   // (ray cast 38.3 us against 42.8-43.4 on BASELINE configs[1]) -- while the device has three times that to spare, i.e. for the first
   // handful of scenes of a 288 GB device; PAGED -- a 768 MB pool of 4 MB pages behind a 16 KB table, O(touched pages) -- for every
   // scene after that, and whenever ITM_MIRROR=paged is in the environment (ITM_MIRROR=dense insists on the cube, =off on none;
@@ -586,7 +586,7 @@ int itm_scene_create(const itm_scene_config* cfg_in, const itm_scene_params* prm
       while (denseBits < kMirrorBits && (double)(1 << denseBits) < 1.25 * reach) ++denseBits;
       if (const char* e = getenv("ITM_MIRROR_BITS")) { const int v = atoi(e); if (v >= 5 && v <= kMirrorBits) denseBits = v; }
     }
-    const size_t pageBytes = (size_t)kPageBlocks * 512 * voxBytes, denseBytes = mirror_dense_cells(denseBits) * 512 * voxBytes;
+    const size_t pageBytes = mirror_voxels(1) * voxBytes, denseBytes = mirror_voxels(-denseBits) * voxBytes;
     int pages = (int)(((size_t)768 << 20) / pageBytes);
     if (const char* e = getenv("ITM_MIRROR_PAGES")) { const int v = atoi(e); if (v > 0) pages = v; }
     size_t freeB = 0, totalB = 0;
@@ -659,8 +659,7 @@ int itm_scene_accel_info(const itm_scene* s, itm_accel_info* out) {
   memset(out, 0, sizeof *out);
   out->directory_bytes = s->dirPtr ? (int64_t)(kDirCells * 4) : 0;
   out->slot_directory_bytes = s->dirSlot ? (int64_t)(kDirCells * 4) : 0;
-  out->mirror_bytes = !s->sdfMirror ? 0 : s->org.mMaxPages < 0 ? (int64_t)(mirror_dense_cells(mirror_dense_bits(s->org)) * 512 * (mirror_is_float(s) ? 4 : 2))
-                                                                  : (int64_t)((size_t)s->mirrorPages * kPageBlocks * 512 * (mirror_is_float(s) ? 4 : 2) + kMirrorTableCells * 4);
+  out->mirror_bytes = !s->sdfMirror ? 0 : (int64_t)(mirror_voxels(s) * (mirror_is_float(s) ? 4 : 2) + (s->org.mMaxPages > 0 ? kMirrorTableCells * 4 : 0));
   out->mirror_pages = s->mirrorPages;          // 0 for the dense form
   out->mirror_pages_mapped = 0;
   if (s->sdfMirror && s->org.mPages) { int n = 0; if (hipMemcpy(&n, s->org.mPages, 4, hipMemcpyDeviceToHost) == hipSuccess) out->mirror_pages_mapped = n < s->mirrorPages ? n : s->mirrorPages; else (void)hipGetLastError(); }
@@ -704,7 +703,7 @@ int itm_reset_scene(itm_scene* s, itm_stream stream) {
     s->orgPlaced = false;
     ++s->tableEpoch;
     reset_hash_kernel<<<1024, 256, 0, st>>>(s->hash, s->noTotalEntries, s->excessList, s->cfg.excessNum, s->allocList,
-                                            s->cfg.localBlockNum, s->allocKey, s->headBits, (s->cfg.bucketNum + 31) / 32, s->chunkReq, s->numChunks * 4, s->counters);
+                                            s->cfg.localBlockNum, s->allocKey, accel_writer(s), (s->cfg.bucketNum + 31) / 32, s->chunkReq, s->numChunks * 4, s->counters);
   } else {
     reset_dense_kernel<<<1, 1, 0, st>>>(s->allocList, s->counters);
   }
@@ -904,7 +903,7 @@ int itm_upload(itm_scene* s, itm_render_state* rs, int which, const void* src, s
       ITM_HIP(hipStreamSynchronize(st));
       accel_place_for_table(s, all.data(), all.size());
     } else accel_place_for_table(s, (const HashEntry*)src, bytes / sizeof(HashEntry));
-    int rc = rebuild_head_bits(s, st); if (rc) return rc;
+    int rc = accel_rebuild(s, st); if (rc) return rc;
   }
   if (which == ITM_BUF_VOXEL_BLOCKS) { int rc = rebuild_sdf_mirror(s, st); if (rc) return rc; }   // the table is the same, the values are new
   if (rs && (which == ITM_BUF_VISIBLE_IDS || which == ITM_BUF_VISIBLE_TYPE)) rs->listCoherent = false;

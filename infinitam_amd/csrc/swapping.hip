@@ -69,8 +69,7 @@ __global__ void __launch_bounds__(kSelThreads) swap_select_kernel(const uint8_t*
 // table order, from the free list -- and a cell in the directories / the mirror.  One workgroup.
 __global__ void __launch_bounds__(kSelThreads) swap_after_allocation_kernel(uint8_t* __restrict__ states, uint4* __restrict__ hash, const uint8_t* __restrict__ visT,
                                                                             int nEntries, const int32_t* __restrict__ allocList, SceneCounters* __restrict__ counters,
-                                                                            int32_t* __restrict__ dirPtr, int32_t* __restrict__ dirSlot, void* __restrict__ mirror,
-                                                                            int mirrorFloat, AccelOrigin org) {
+                                                                            AccelWriter aw) {
   __shared__ int lds[kSelThreads / 64 + 1];
   const int per = (nEntries + kSelThreads - 1) / kSelThreads;
   const int lo = min((int)threadIdx.x * per, nEntries), hi = min(lo + per, nEntries);
@@ -94,8 +93,7 @@ __global__ void __launch_bounds__(kSelThreads) swap_after_allocation_kernel(uint
       raw.w = (uint32_t)ptr;
       hash[e] = raw;
       const HashEntry he = unpack_entry(raw);
-      directory_insert(dirPtr, dirSlot, org, he.px, he.py, he.pz, ptr, e);
-      mirror_init_block(mirror, mirrorFloat != 0, org, he.px, he.py, he.pz);     // the block was reset when it was swapped out
+      aw.block_allocated_excess(e, he.px, he.py, he.pz, ptr);     // (the entry and its occupancy bit stayed; the block was reset when it was swapped out)
     }
   }
   __syncthreads();
@@ -108,16 +106,15 @@ __global__ void __launch_bounds__(kSelThreads) swap_after_allocation_kernel(uint
 template <class VX>
 __global__ void __launch_bounds__(512) swap_combine_kernel(const int32_t* __restrict__ ids, const uint8_t* __restrict__ flags, const void* __restrict__ xfer,
                                                            const uint4* __restrict__ hash, void* __restrict__ vba, uint8_t* __restrict__ states, int maxW,
-                                                           void* __restrict__ mirror, AccelOrigin org) {
+                                                           AccelWriter aw) {
   const int i = blockIdx.x, id = ids[i], t = threadIdx.x;
   const HashEntry he = unpack_entry(hash[id]);
   if (flags[i] && he.ptr >= 0) {        // (the reference dereferences ptr unchecked; a state-1 entry without a block cannot be combined)
     const size_t vi = (size_t)he.ptr * kBlockVoxels + t;
     const typename VX::Reg r = combine_voxel<VX>(VX::load(xfer, (size_t)i * kBlockVoxels + t), VX::load(vba, vi), maxW);
     VX::store(vba, vi, r);
-    using MC = MirrorCodec<VX::kShort>;
     size_t mbase;
-    if (mirror && mirror_block_base<false>(org, he.px, he.py, he.pz, mbase)) ((typename MC::T*)mirror)[mbase + mirror_block_lin((uint32_t)t)] = MC::of(VX::raw_sdf(r));
+    if (aw.block_base_wave_uniform<false>(he.px, he.py, he.pz, mbase)) aw.store_sdf<VX>(mbase, (uint32_t)t, VX::raw_sdf(r));      // (one block per workgroup)
   }
   if (t == 0) states[id] = 2;
 }
@@ -129,7 +126,7 @@ __global__ void __launch_bounds__(512) swap_combine_kernel(const int32_t* __rest
 template <class VX>
 __global__ void __launch_bounds__(512) swap_out_kernel(const int32_t* __restrict__ ids, void* __restrict__ xfer, uint4* hash, void* __restrict__ vba,
                                                        uint8_t* __restrict__ states, int32_t* __restrict__ allocList, const SceneCounters* __restrict__ counters,
-                                                       int bucketNum, int localBlockNum, int32_t* __restrict__ dirPtr, int32_t* __restrict__ dirSlot, void* __restrict__ mirror, AccelOrigin org) {
+                                                       int bucketNum, int localBlockNum, AccelWriter aw) {
   const int i = blockIdx.x, id = ids[i], t = threadIdx.x;
   // the entry is read by ONE thread and handed to the others through LDS: thread 0 rewrites hash[id] below, and nothing else would
   // order that store after a late wave's load of the same entry
@@ -151,17 +148,15 @@ __global__ void __launch_bounds__(512) swap_out_kernel(const int32_t* __restrict
   const bool release = vbaIdx < bucketNum - 1 && vbaIdx + 1 < localBlockNum;
   if (release) {
     VX::store(vba, vi, VX::init());
-    using MC = MirrorCodec<VX::kShort>;
     size_t mbase;
-    if (mirror && mirror_block_base<false>(org, he.px, he.py, he.pz, mbase))
-      ((typename MC::T*)mirror)[mbase + mirror_block_lin((uint32_t)t)] = VX::kShort ? (typename MC::T)-32768 : (typename MC::T)0xffffffffu;
+    if (aw.block_base_wave_uniform<false>(he.px, he.py, he.pz, mbase)) aw.store_absent<VX>(mbase, (uint32_t)t);
   }
   if (t == 0) {
     states[id] = 0;
     if (release) {
       allocList[vbaIdx + 1] = he.ptr;
       hash[id] = make_uint4(raw.x, raw.y, raw.z, (uint32_t)-1);
-      directory_insert(dirPtr, dirSlot, org, he.px, he.py, he.pz, -1, -1);
+      aw.block_released(he.px, he.py, he.pz);
     }
   }
 }
@@ -206,9 +201,7 @@ void free_swap_state(itm_scene* s) {
 }
 
 int launch_swap_after_allocation(itm_scene* s, itm_render_state* rs, hipStream_t st) {
-  const int mirrorFloat = (s->cfg.voxelType == ITM_VOXEL_F || s->cfg.voxelType == ITM_VOXEL_F_RGB) ? 1 : 0;
-  swap_after_allocation_kernel<<<1, kSelThreads, 0, st>>>(s->swapStates, s->hash, rs->visibleType, s->noTotalEntries, s->allocList, s->counters,
-                                                          s->dirPtr, s->dirSlot, s->sdfMirror, mirrorFloat, s->org);
+  swap_after_allocation_kernel<<<1, kSelThreads, 0, st>>>(s->swapStates, s->hash, rs->visibleType, s->noTotalEntries, s->allocList, s->counters, accel_writer(s));
   ITM_LAUNCH_CHECK();
   return ITM_OK;
 }
@@ -243,7 +236,7 @@ int itm_swap_integrate_global_into_local(itm_scene* s, itm_render_state* rs, itm
   if (any) ITM_HIP(hipMemcpyAsync(h->xferBlocksDev, h->xferBlocksHost, (size_t)n * blockBytes, hipMemcpyHostToDevice, st));
   int rc = dispatch_voxel(s->cfg.voxelType, [&](auto vx) {
     using VX = decltype(vx);
-    swap_combine_kernel<VX><<<n, 512, 0, st>>>(h->xferIdsDev, h->xferFlagsDev, h->xferBlocksDev, s->hash, s->vba, s->swapStates, s->prm.maxW, s->sdfMirror, s->org);
+    swap_combine_kernel<VX><<<n, 512, 0, st>>>(h->xferIdsDev, h->xferFlagsDev, h->xferBlocksDev, s->hash, s->vba, s->swapStates, s->prm.maxW, accel_writer(s));
     return ITM_OK;
   });
   if (rc) return rc;
@@ -268,7 +261,7 @@ int itm_swap_save_to_global_memory(itm_scene* s, itm_render_state* rs, itm_strea
   int rc = dispatch_voxel(s->cfg.voxelType, [&](auto vx) {
     using VX = decltype(vx);
     swap_out_kernel<VX><<<n, 512, 0, st>>>(h->xferIdsDev, h->xferBlocksDev, s->hash, s->vba, s->swapStates, s->allocList, s->counters, s->cfg.bucketNum, s->cfg.localBlockNum,
-                                           s->dirPtr, s->dirSlot, s->sdfMirror, s->org);
+                                           accel_writer(s));
     return ITM_OK;
   });
   if (rc) return rc;

@@ -618,7 +618,7 @@ int launch_render_image(const itm_scene* s, const float* M, const float* intr, i
   const VolumeView vol = make_volume(s);
   const dim3 grid((rs->w + 15) / 16, (rs->h + 15) / 16);
   const bool dense = s->cfg.indexType == ITM_INDEX_DENSE;
-  const bool colour = (s->cfg.voxelType == ITM_VOXEL_S_RGB || s->cfg.voxelType == ITM_VOXEL_F_RGB);
+  const bool colour = voxel_has_colour(s->cfg.voxelType);
   if (type == ITM_RENDER_COLOUR_FROM_VOLUME && !colour) type = ITM_RENDER_SHADED_GREYSCALE;  // _CPU.cpp:205-206
   if (type != ITM_RENDER_COLOUR_FROM_VOLUME && type != ITM_RENDER_COLOUR_FROM_NORMAL) type = ITM_RENDER_SHADED_GREYSCALE;
   rc = dispatch_voxel(s->cfg.voxelType, [&](auto vx) {

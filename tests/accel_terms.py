@@ -1,4 +1,4 @@
-"""The invariant of the acceleration cubes (infinitam_amd/csrc/itm_types.h, scene.hip), restated in numpy on DOWNLOADED buffers -- the
+"""The invariant of the acceleration cubes (infinitam_amd/csrc/accel_device.h, scene.hip), restated in numpy on DOWNLOADED buffers -- the
 hash table, the voxel pool and accel_info() -- and compared with what the read-only probe and census of include/itm_debug.h find in
 device memory:
 

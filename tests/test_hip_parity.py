@@ -303,7 +303,7 @@ def test_fast_divisions_are_ieee(hip):
     assert np.array_equal(_divide(hip, 2, c, ww).view(np.uint32), (c / ww).view(np.uint32))
 
 
-# ---- block directory (dense mirror of the hash table, infinitam_amd/csrc/itm_types.h) ------------------------------------
+# ---- block directory (dense mirror of the hash table, infinitam_amd/csrc/accel_device.h) ----------------------------------
 DIRECTORY_CASES = [
     SCENARIOS[0],
     Scenario(name="hash_s_4mm_bench_traj6", voxelSize=0.004, frames=6, trajectory="bench"),

@@ -1,4 +1,4 @@
-"""The sdf mirror is PAGED (infinitam_amd/csrc/itm_types.h): a 16 KB table over the mirror's cube of 256^3 blocks says which
+"""The sdf mirror is PAGED (infinitam_amd/csrc/accel_device.h): a 16 KB table over the mirror's cube of 256^3 blocks says which
 16 x 16 x 16-block pages hold blocks; pages (4 MB of int16 sdf) come from a pool as blocks are allocated.  The reference's footprint is O(pool)
 (ITMLib/Objects/ITMLocalVBA.h:18-59); the mirror's now is too (rounds 2-3: 17 GB per scene whatever it held).
 
