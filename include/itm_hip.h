@@ -750,6 +750,57 @@ typedef struct itm_merge_stats {
 } itm_merge_stats;
 int ITM_FN(scene_merge)(itm_scene* dst, const itm_scene* src, const int32_t* srcSlots_dev, int n, itm_merge_stats* stats, itm_stream stream);
 
+/* ---- scene queries: the volume asked at caller-supplied points and along caller-supplied rays -------------------------------------
+ * The reference makes these reads only from inside its engines, per pixel; here the work item is the caller's.  Both calls launch the
+ * scene's recorded calls first, read the scene only, take DEVICE pointers and enqueue one launch on `stream` (no synchronisation).
+ *
+ * itm_scene_query_points, sequential definition.  For point i with x = points_dev[3i .. 3i + 2]:
+ *   p = x / voxelSize (three IEEE divisions, as itm_mesh_attributes: a mesh's vertices reproduce its attributes bit for bit) for
+ *   ITM_QUERY_METRES, p = x for ITM_QUERY_VOXELS.  Voxels are read as readVoxel reads them (DeviceAgnostic/ITMRepresentationAccess.h:
+ *   85-142): an absent voxel is TVoxel() -- sdf 1, weight 0, colour 0.  Outputs, each written only where its pointer is not NULL:
+ *     sdf          readFromSDF_float_interpolated(p)                                               :160-185
+ *     sdf_nearest  readFromSDF_float_uninterpolated(p): the voxel at ROUND(p)                      :144-158
+ *     gradient     computeSingleNormalFromSDF(p) as it returns it, not normalised                  :224-337
+ *     normal       gradient * (1 / sqrt(g.g)), (0, 0, 0) where that is not finite (the normal of itm_mesh_attributes)
+ *     colour       readFromSDF_color4u_interpolated(p) (:187-222) as drawPixelColour's bytes (DeviceAgnostic/ITMVisualisationEngine.h:
+ *                  270-279), alpha 255; a scene whose voxel type stores no colour: ITM_ERR_INVALID, as itm_mesh_attributes
+ *     weight       w_depth of the voxel at ROUND(p), 0 if absent
+ *     flags        bit 0: the voxel at ROUND(p) exists; bits 8-15: which corners of the trilinear cell floor(p) + (dx, dy, dz) exist
+ *                  (corner dx + 2 dy + 4 dz); bit 1: all eight do; bit 31 ITM_QUERY_INVALID: a coordinate of p is not finite or
+ *                  !(|c| < 262136) -- then nothing is read at p (floor(p) - 1 .. floor(p) + 2 stays inside the table's short block
+ *                  coordinates for every other p) and the outputs are the defaults: sdf and sdf_nearest 1, the others 0.
+ *   n == 0: success, nothing launched.
+ *
+ * itm_scene_cast_rays, sequential definition.  Ray i is rays_dev[8i .. 8i + 7] = (sx, sy, sz, t0, ex, ey, ez, t1), metres: the segment
+ * to search and the ray parameter at its two ends.  The result is castRay's (DeviceAgnostic/ITMVisualisationEngine.h:92-158) from the
+ * statement that follows its camera preamble, with oneOverVoxelSize = 1.0f / voxelSize and stepScale = mu * oneOverVoxelSize:
+ *   pt_block_s = s * oneOverVoxelSize, pt_block_e = e * oneOverVoxelSize, totalLength = t0 * oneOverVoxelSize, totalLengthMax = t1 *
+ *   oneOverVoxelSize, rayDirection = (pt_block_e - pt_block_s) * (1 / sqrt(d.d)) as :117-121 form it, then the loop :126-156.
+ * A camera ray fed this way -- s, e = invM * pt_camera_f of the range image's minimum / maximum depth, t = length(pt_camera_f) -- goes
+ * through exactly the float operations of castRay.  hits_dev[4i .. 4i + 3] = (x, y, z, w) in voxel units as raycastResult holds them:
+ * w = 1 a hit (feed xyz to itm_scene_query_points with ITM_QUERY_VOXELS for normals and colours), w = 0 a miss with xyz unspecified.
+ * A ray is invalid, takes no step and gives (0, 0, 0, 0) when a value is not finite, when pt_block_s == pt_block_e, when a coordinate
+ * of pt_block_s or pt_block_e has !(|c| < 131072), when !(|totalLength| < 4194304) or !(|totalLengthMax| < 4194304) (voxels: beyond
+ * 2^24 the loop's `totalLength += stepLength` no longer moves and castRay would not end), or when the normalised direction is not
+ * finite.  The limits bound the ray parameter, not the position: a ray whose t1 - t0 far exceeds |e - s| marches on past e, up to
+ * ~8.4 M voxels from s, through space that reads "no block" (8 voxels a step: about a million steps for that lane and the wave it is
+ * in) -- safe, but the caller pays for it; give t1 - t0 = |e - s| unless that is what is wanted.  hits_dev is 16-byte aligned.
+ * n == 0: success, nothing launched. */
+#define ITM_QUERY_METRES 0
+#define ITM_QUERY_VOXELS 1
+#define ITM_QUERY_INVALID 0x80000000u
+typedef struct itm_query_out {      /* device pointers, NULL = not wanted */
+  float* sdf;           /* [n]  */
+  float* sdf_nearest;   /* [n]  */
+  float* gradient;      /* [3n] */
+  float* normal;        /* [3n] */
+  uint8_t* colour;      /* [4n] */
+  uint8_t* weight;      /* [n]  */
+  uint32_t* flags;      /* [n]  */
+} itm_query_out;
+int ITM_FN(scene_query_points)(const itm_scene* scene, const float* points_dev, uint32_t n, int units, const itm_query_out* out, itm_stream stream);
+int ITM_FN(scene_cast_rays)(const itm_scene* scene, const float* rays_dev, uint32_t n, float* hits_dev, itm_stream stream);
+
 /* The acceleration structures a hash scene carries beside the reference's table (none of them part of the reference's state, all
  * derived from it): a block directory and a slot directory over a cube of 512^3 blocks, an sdf mirror over 256^3 blocks for the
  * short voxel types.  The cubes are NOT tied to the world origin: the first frame places them around its camera (the reference's

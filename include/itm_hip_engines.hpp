@@ -299,6 +299,23 @@ class ITMSceneMergeEngine_HIP {
   }
 };
 
+// Scene queries (itm_scene_query_points / itm_scene_cast_rays; the reference makes these reads only per pixel, inside its engines):
+// readFromSDF_float_interpolated, computeSingleNormalFromSDF, readFromSDF_color4u_interpolated at caller-supplied points, castRay along
+// caller-supplied segments.  All pointers are DEVICE memory; one launch on `stream`, nothing is synchronised.
+template <class TVoxel, class TIndex>
+class ITMSceneQueryEngine_HIP {
+ public:
+  itm_stream stream = nullptr;
+  // points: float[3 n] in metres (units = ITM_QUERY_METRES) or voxels; out: the wanted outputs, NULL = not wanted
+  void QueryPoints(const ITMScene<TVoxel, TIndex>* scene, const float* points, uint32_t n, const itm_query_out& out, int units = ITM_QUERY_METRES) const {
+    check(itm_scene_query_points(scene->handle, points, n, units, &out, stream), "QueryPoints");
+  }
+  // rays: float[8 n] = (s, t0, e, t1) in metres; hits: float[4 n] = (x, y, z, w) in voxel units, w = 1 a hit
+  void CastRays(const ITMScene<TVoxel, TIndex>* scene, const float* rays, uint32_t n, float* hits) const {
+    check(itm_scene_cast_rays(scene->handle, rays, n, hits, stream), "CastRays");
+  }
+};
+
 template <class TVoxel, class TIndex>
 class ITMDenseMapper_HIP {
   ITMSceneReconstructionEngine_HIP<TVoxel, TIndex> reco;
@@ -705,6 +722,11 @@ class ITMMainEngine_HIP {
   void MergeSceneFrom(const ITMMainEngine_HIP& other, itm_merge_stats* stats = nullptr) {
     ITMSceneMergeEngine_HIP<TVoxel, TIndex>().MergeScene(&scene, &other.scene, nullptr, stats);
   }
+  // The fused volume asked at the caller's own points / along the caller's own rays (ITMSceneQueryEngine_HIP; device pointers)
+  void QueryPoints(const float* points, uint32_t n, const itm_query_out& out, int units = ITM_QUERY_METRES) const {
+    ITMSceneQueryEngine_HIP<TVoxel, TIndex>().QueryPoints(&scene, points, n, out, units);
+  }
+  void CastRays(const float* rays, uint32_t n, float* hits) const { ITMSceneQueryEngine_HIP<TVoxel, TIndex>().CastRays(&scene, rays, n, hits); }
   ITMRenderState* GetRenderState() { return renderState_live; }
   const ITMVisualisationEngine_HIP<TVoxel, TIndex>* GetVisualisationEngine() const { return &visualisationEngine; }
   const ITMViewBuilder_HIP* GetViewBuilder() const { return viewBuilder; }

@@ -172,6 +172,18 @@ class MergeStats(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class QueryOut(C.Structure):
+    """itm_query_out (include/itm_hip.h, itm_scene_query_points): device pointers, NULL = not wanted."""
+    _fields_ = [(n, C.c_void_p) for n in ("sdf", "sdf_nearest", "gradient", "normal", "colour", "weight", "flags")]
+
+
+QUERY_METRES, QUERY_VOXELS = 0, 1
+QUERY_INVALID = 0x80000000
+# output name -> (dtype, trailing shape)
+QUERY_OUTPUTS = {"sdf": (np.float32, ()), "sdf_nearest": (np.float32, ()), "gradient": (np.float32, (3,)), "normal": (np.float32, (3,)),
+                 "colour": (np.uint8, (4,)), "weight": (np.uint8, ()), "flags": (np.uint32, ())}
+
+
 class ItmError(RuntimeError):
     pass
 
@@ -335,6 +347,9 @@ _HOST_IO_SIGS = {
     "normal_to_uchar4": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     # scene merge (product only: no reference engine merges scenes)
     "scene_merge": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(MergeStats), _P]),
+    # scene queries at caller-supplied points / along caller-supplied rays (product only: the reference reads per pixel, inside its engines)
+    "scene_query_points": (C.c_int, [_P, _P, C.c_uint32, C.c_int, C.POINTER(QueryOut), _P]),
+    "scene_cast_rays": (C.c_int, [_P, _P, C.c_uint32, _P, _P]),
 }
 
 
@@ -604,6 +619,46 @@ class Scene:
             keep.close()
         self.be.check(rc, "scene_merge")
         return st.as_dict()
+
+    def query_points(self, points, units="metres", want=("sdf", "gradient"), stream=None) -> dict:
+        """itm_scene_query_points: the outputs named in `want` (QUERY_OUTPUTS) at float32 points [n, 3] in "metres" or "voxels", as a
+        dict of numpy arrays.  Uploads the points, downloads the outputs and synchronises `stream`."""
+        pts = np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 3))
+        n = len(pts)
+        unknown = [w for w in want if w not in QUERY_OUTPUTS]
+        if unknown:
+            raise ItmError(f"query_points: unknown outputs {unknown}")
+        dev_pts = self.be.to_backend(pts, stream) if n else None
+        bufs = {w: DevBuffer(self.be, n * int(np.prod(QUERY_OUTPUTS[w][1] or (1,))) * np.dtype(QUERY_OUTPUTS[w][0]).itemsize, QUERY_OUTPUTS[w][0],
+                             (n,) + QUERY_OUTPUTS[w][1]) for w in want}
+        out = QueryOut()
+        for w, b in bufs.items():
+            setattr(out, w, b.ptr)
+        rc = self.be.fn["scene_query_points"](_P(self.h), _P(dev_pts.ptr if n else None), n, {"metres": QUERY_METRES, "voxels": QUERY_VOXELS}[units],
+                                              C.byref(out), _P(stream))
+        self.be.sync(stream)
+        res = {w: (b.numpy(stream) if n else np.zeros((0,) + QUERY_OUTPUTS[w][1], QUERY_OUTPUTS[w][0])) for w, b in bufs.items()} if rc == 0 else None
+        for b in list(bufs.values()) + ([dev_pts] if n else []):
+            b.close()
+        self.be.check(rc, "scene_query_points")
+        return res
+
+    def cast_rays(self, rays, stream=None) -> np.ndarray:
+        """itm_scene_cast_rays: float32 rays [n, 8] = (sx, sy, sz, t0, ex, ey, ez, t1) in metres -> float32 [n, 4] = (x, y, z, w) in
+        voxel units, w = 1 a hit.  Uploads, downloads and synchronises `stream`."""
+        r = np.ascontiguousarray(np.asarray(rays, np.float32).reshape(-1, 8))
+        n = len(r)
+        if n == 0:
+            self.be.check(self.be.fn["scene_cast_rays"](_P(self.h), None, 0, None, _P(stream)), "scene_cast_rays")
+            return np.zeros((0, 4), np.float32)
+        dev_rays = self.be.to_backend(r, stream)
+        hits = DevBuffer(self.be, n * 16, np.float32, (n, 4))
+        rc = self.be.fn["scene_cast_rays"](_P(self.h), _P(dev_rays.ptr), n, _P(hits.ptr), _P(stream))
+        self.be.sync(stream)
+        res = hits.numpy(stream) if rc == 0 else None
+        dev_rays.close(); hits.close()
+        self.be.check(rc, "scene_cast_rays")
+        return res
 
     def accel_info(self) -> dict:
         """Sizes, placement and move count of the directory / mirror cubes (product library only)."""

@@ -28,6 +28,7 @@
 
 #include "itm_internal.h"
 #include "mesh_types.h"
+#include "sample_device.h"
 #include "shading_device.h"
 
 namespace itm {
@@ -37,55 +38,6 @@ int g_debug_mesh_attr_per_vertex = 0;
 constexpr int kHaloLow = 2;                       // planes below the block
 constexpr int kHaloSide = kBlockSide + 5;         // -2 .. +10
 constexpr int kHaloCells = kHaloSide * kHaloSide * kHaloSide;
-
-// sdf_gradient (shading_device.h) over any source of raw sdf values: `raw(dx, dy, dz)` is the voxel at floor(p) + (dx, dy, dz).
-// The products and sums are gradient_component's, term for term.
-template <class VX, int AXIS, class S>
-__device__ inline float gradient_axis(S&& raw, float fa, float fu, float fv) {
-  auto sample = [&](int k, int u, int v) {
-    const int dx = (AXIS == 0) ? k : u;
-    const int dy = (AXIS == 1) ? k : (AXIS == 0 ? u : v);
-    const int dz = (AXIS == 2) ? k : v;
-    return raw(dx, dy, dz);
-  };
-  const float gu = 1.0f - fu, gv = 1.0f - fv, ga = 1.0f - fa;
-  float plane[4];
-#pragma unroll
-  for (int k = -1; k <= 2; ++k)
-    plane[k + 1] = sample(k, 0, 0) * gu * gv + sample(k, 1, 0) * fu * gv + sample(k, 0, 1) * gu * fv + sample(k, 1, 1) * fu * fv;
-  const float lower = plane[1] * fa + plane[0] * ga;
-  return VX::to_float(plane[2] * ga + plane[3] * fa - lower);
-}
-
-// colour_at (shading_device.h) over any source of packed colours (r | g << 8 | b << 16; 0 where no voxel is stored)
-template <class C>
-__device__ inline float4 colour_from(C&& packed, float cx, float cy, float cz) {
-  float r[3] = {0.0f, 0.0f, 0.0f};
-  auto add = [&](int dx, int dy, int dz, float wgt) {
-    const uint32_t c = packed(dx, dy, dz);
-    r[0] += wgt * (float)(int)(c & 0xffu); r[1] += wgt * (float)(int)((c >> 8) & 0xffu); r[2] += wgt * (float)(int)((c >> 16) & 0xffu);
-  };
-  add(0, 0, 0, (1.0f - cx) * (1.0f - cy) * (1.0f - cz));
-  add(1, 0, 0, (cx) * (1.0f - cy) * (1.0f - cz));
-  add(0, 1, 0, (1.0f - cx) * (cy) * (1.0f - cz));
-  add(1, 1, 0, (cx) * (cy) * (1.0f - cz));
-  add(0, 0, 1, (1.0f - cx) * (1.0f - cy) * cz);
-  add(1, 0, 1, (cx) * (1.0f - cy) * cz);
-  add(0, 1, 1, (1.0f - cx) * (cy)*cz);
-  add(1, 1, 1, (cx) * (cy)*cz);
-  return make_float4(r[0] / 255.0f, r[1] / 255.0f, r[2] / 255.0f, 255.0f / 255.0f);
-}
-
-__device__ inline void store_normal(float* __restrict__ o, float gx, float gy, float gz) {
-  const float sc = 1.0f / sqrtf(gx * gx + gy * gy + gz * gz);
-  float nx = gx * sc, ny = gy * sc, nz = gz * sc;
-  if (!(__builtin_isfinite(nx) && __builtin_isfinite(ny) && __builtin_isfinite(nz))) nx = ny = nz = 0.0f;   // zero or overflowing length
-  o[0] = nx; o[1] = ny; o[2] = nz;
-}
-
-__device__ inline uchar4 colour_bytes(float4 c) {   // drawPixelColour
-  return make_uchar4((unsigned char)(c.x * 255.0f), (unsigned char)(c.y * 255.0f), (unsigned char)(c.z * 255.0f), 255);
-}
 
 // the attributes of vertex v through the hash (directory / mirror where they cover) or, DENSE, the voxel array: the reference's
 // functions as the renders use them

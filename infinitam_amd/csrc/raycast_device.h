@@ -549,6 +549,8 @@ struct RayResume { float px, py, pz, total; };
 //   PARK: the ray stops (parked = true, returns its position and length in xyz / w) once it has taken kParkStreak
 //     "not found" steps in a row; the caller appends it to the queue of the second pass.
 // Per ray the sequence of positions, reads and float operations is that of the reference, whatever the pass structure.
+// (march_segment, at the end of this file, is the twin of march_ray<VX, DENSE, 0, false> for rays that are not pixels: a change to the
+// step, the band or the refinement here has to be made there too.)
 template <class VX, bool DENSE, int LOOKAHEAD, bool PARK, class VOL = VolumeView>
 __device__ inline float4 march_ray(int x, int y, const VOL& vol, const RayParams& p, float2 mm, const RayResume* resume, bool& parked) {
   // MARCH: next read is a single voxel; TRI: a single-voxel read found the band, the trilinear read of the same position is
@@ -734,6 +736,61 @@ template <class VX, bool DENSE, class VOL = VolumeView>
 __device__ inline float4 cast_ray(int x, int y, const VOL& vol, const RayParams& p, float2 mm) {
   bool parked;
   return march_ray<VX, DENSE, 0, false>(x, y, vol, p, mm, nullptr, parked);
+}
+
+// castRay from a GIVEN set-up, for rays that are not pixels of a frame (query.hip): what march_ray<VX, DENSE, 0, false> does after its
+// ray_setup -- the same two nested loops, the same reads and float operations per ray -- without anything collective over the wave
+// (look-ahead, parking, the dense "every lane has left the volume" exit): neighbouring lanes are unrelated rays.  A function of its own
+// rather than a split of march_ray: with the split the frame ray-cast kernels kept their registers, scratch and occupancy but came out
+// with their instructions in another order (a few s_waitcnt / s_nop more or fewer), and those kernels are tuned to the microsecond.
+template <class VX, bool DENSE, class VOL = VolumeView>
+__device__ inline float4 march_segment(const RaySetup& r, float stepScale, const VOL& vol) {
+  enum : int { MARCH = 0, TRI = 1, REFINE = 2, DONE = 4 };
+  float px = r.px, py = r.py, pz = r.pz, total = r.total;
+  const float dx = r.dx, dy = r.dy, dz = r.dz, totalMax = r.totalMax;
+  BlockCache cache;
+  bool found;
+  float w = 0.0f;
+  int st = (total < totalMax) ? MARCH : DONE;
+  while (st != DONE) {
+    // ---- cheap phase: at most kMarchBurst single-voxel steps (march_ray's step, as selects) ----
+    int budget = kMarchBurst;
+    while (st == MARCH && budget > 0) {
+      --budget;
+      const float sdf = sdf_nearest<VX, DENSE>(vol, px, py, pz, found, cache);
+      const bool band = found && (sdf <= 0.1f) && (sdf >= -0.5f);       // the position is kept for the trilinear read
+      const bool crossed = found && (sdf <= 0.0f);                      // (below the band) first refinement move, no length update
+      const float s = sdf * stepScale;
+      const float fwd = (s < 1.0f) ? 1.0f : s;
+      const float step = found ? (crossed ? s : fwd) : (float)kBlockSide;
+      const float nx = px + step * dx, ny = py + step * dy, nz = pz + step * dz, nt = total + step;
+      px = band ? px : nx; py = band ? py : ny; pz = band ? pz : nz;
+      total = (band || crossed) ? total : nt;
+      st = band ? TRI : crossed ? REFINE : (total < totalMax) ? MARCH : DONE;
+    }
+    // ---- expensive phase: one 2x2x2 fetch for every lane that waits for one ----
+    if (st == TRI || st == REFINE) {
+      Corners<VX, DENSE> cn;
+      cn.fetch(vol, px, py, pz, cache);
+      const float sdf = cn.trilinear();
+      if (st == REFINE) {
+        const float step = sdf * stepScale;
+        px += step * dx; py += step * dy; pz += step * dz;
+        w = 1.0f; st = DONE;
+      } else if (sdf <= 0.0f) {                                         // surface crossed: first refinement move, no length update
+        const float step = sdf * stepScale;
+        px += step * dx; py += step * dy; pz += step * dz;
+        st = REFINE;
+      } else {
+        const float s = sdf * stepScale;
+        const float step = (s < 1.0f) ? 1.0f : s;
+        px += step * dx; py += step * dy; pz += step * dz;
+        total += step;
+        st = (total < totalMax) ? MARCH : DONE;
+      }
+    }
+  }
+  return make_float4(px, py, pz, w);
 }
 
 }  // namespace itm
