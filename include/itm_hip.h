@@ -233,7 +233,10 @@ int ITM_FN(flush)(itm_scene* scene, itm_render_state* rs, itm_stream stream);   
 
 /* ITMSceneReconstructionEngine::AllocateSceneFromDepth(scene, view, trackingState, renderState,
  * onlyUpdateVisibleList)                               Engine/ITMSceneReconstructionEngine.h:40
- * (CPU hash :116-291, dense :314-317 no-op) */
+ * (CPU hash :116-291, dense :314-317 no-op)
+ * The render state need not have the view's size, as in the reference: ITMMainEngine allocates from the depth image through the
+ * render state of the TRACKED image, which is the colour camera's for TRACKER_COLOR (Engine/ITMMainEngine.cpp:50-52).  A call whose
+ * sizes differ is always launched at once, never recorded for the fused frame (itm_scene_set_deferred_fusion). */
 int ITM_FN(allocate_scene_from_depth)(itm_scene* scene, const itm_view* view,
                                       itm_render_state* rs, int onlyUpdateVisibleList,
                                       itm_stream stream);
@@ -286,7 +289,10 @@ int ITM_FN(forward_render)(const itm_scene* scene, const itm_view* view, itm_ren
  * 50-65: AllocateSceneFromDepth + IntegrateIntoScene) followed by
  * ITMTrackingController::Prepare with requiresFullRendering (Engine/ITMTrackingController.cpp:
  * 31-35: CreateExpectedDepths + CreateICPMaps).  Results are identical to issuing the four calls
- * one after another; this entry point only removes launch overhead. */
+ * one after another; this entry point only removes launch overhead.  itm_process_frame and
+ * itm_process_frame_ahead require view (and next view) and render state of the SAME size -- the
+ * fused launches index the render state's per-pixel buffers by depth pixel -- and return
+ * ITM_ERR_INVALID otherwise; the four separate calls have no such rule. */
 int ITM_FN(process_frame)(itm_scene* scene, const itm_view* view, itm_render_state* rs,
                           float* points, float* normals, itm_stream stream);
 /* The same frame, for a host that already HAS the next frame (an offline sequence, a buffered sensor): `next` (may be NULL) is the view

@@ -143,8 +143,14 @@ int itm_allocate_scene_from_depth(itm_scene* s, const itm_view* v, itm_render_st
   if (rc) return rc;
   if (s->cfg.indexType == ITM_INDEX_DENSE) return ITM_OK;  // _CPU.cpp:314-317
   if (!v->depth) return set_error(ITM_ERR_INVALID, "null depth image");
-  if (rs->scene != s || v->w != rs->w || v->h != rs->h) return set_error(ITM_ERR_INVALID, "view / render state mismatch");
-  if (onlyUpdateVisibleList || !deferral_enabled(s)) return launch_allocate(s, v, rs, onlyUpdateVisibleList != 0, false, as_stream(stream));
+  if (rs->scene != s) return set_error(ITM_ERR_INVALID, "render state belongs to another scene");
+  // The render state need not have the view's size: ITMMainEngine allocates from the depth image through a render state of the TRACKED
+  // size, which is the colour camera's for TRACKER_COLOR (Engine/ITMMainEngine.cpp:50-52).  The launches of this call index no per-pixel
+  // buffer of the render state (visible types, list and counters only).  The fused frame does -- its request launch initialises the
+  // range image by depth pixel (alloc_device.h, FUSE_RANGE_INIT) -- so such a call is never recorded: it is launched here, and what
+  // follows it finds nothing to complete.
+  const bool sameSize = v->w == rs->w && v->h == rs->h;
+  if (onlyUpdateVisibleList || !sameSize || !deferral_enabled(s)) return launch_allocate(s, v, rs, onlyUpdateVisibleList != 0, false, as_stream(stream));
   if ((rc = validate_allocate(s, v, rs, false))) return rc;
   std::lock_guard<std::recursive_mutex> lock(g_pendingMutex);
   rs->deferred.view = *v;

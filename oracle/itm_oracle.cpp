@@ -1343,7 +1343,7 @@ int itmo_render_state_destroy(itm_render_state* rs) { delete rs; return ITM_OK; 
 int itmo_allocate_scene_from_depth(itm_scene* s, const itm_view* v, itm_render_state* rs, int onlyVis, itm_stream) {
   if (!s || !v || !rs) return fail(ITM_ERR_INVALID, "null argument");
   if (s->cfg.indexType == ITM_INDEX_DENSE) return ITM_OK;
-  if (v->w != rs->w || v->h != rs->h) return fail(ITM_ERR_INVALID, "view / render state size mismatch");
+  // (the render state may have another size than the view, as in the reference: ITMMainEngine's is the tracked image's)
   allocate_hash(s, v, rs, onlyVis != 0);
   return ITM_OK;
 }
@@ -1415,6 +1415,8 @@ int itmo_forward_render(const itm_scene* s, const itm_view* v, itm_render_state*
 
 int itmo_process_frame(itm_scene* s, const itm_view* v, itm_render_state* rs, float* pts, float* nrm, itm_stream st) {
   int r;
+  if (!s || !v || !rs) return fail(ITM_ERR_INVALID, "null argument");
+  if (v->w != rs->w || v->h != rs->h) return fail(ITM_ERR_INVALID, "view / render state size mismatch");      // the product's rule for the fused frame
   if ((r = itmo_allocate_scene_from_depth(s, v, rs, 0, st))) return r;
   if ((r = itmo_integrate_into_scene(s, v, rs, st))) return r;
   if ((r = itmo_create_expected_depths(s, v->M_d, v->intr_d, rs, st))) return r;

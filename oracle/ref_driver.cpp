@@ -666,14 +666,23 @@ uint64_t fnv(const void* p, size_t n, uint64_t h = 1469598103934665603ull) {
 }
 }  // namespace
 
-extern "C" int itmr_debug_main_engine_sequence(itm_scene* s, itm_render_state* r, int w, int h, const float intr[4], int nFrames, const int16_t* raw,
-                                               const float* externalPoses, int trackerType, int useApproximateRaycast, int skipPoints,
-                                               const uint8_t* fusionActive, const uint8_t* mainProcessingActive, const itm_tracker_config* cfg,
-                                               int32_t* age, int32_t* full, float* poses, uint64_t* digest) {
-  const Vector2i sz(w, h);
+// The colour camera: its own size (wc x hc), intrinsics and rigid offset (rgbToDepth / rgbToDepthInv, column-major; NULL = identity), one
+// RGB image per frame (rgbFrames: nFrames x hc x wc uchar4; NULL = the (x, y, x ^ y, 255) pattern every frame).  The render state -- and
+// with it the tracking state's point cloud -- has the TRACKED image's size: the colour camera's for trackerType 0 (Engine/ITMMainEngine.cpp:
+// 50-52), the depth camera's otherwise.
+extern "C" int itmr_debug_main_engine_sequence_rgbd(itm_scene* s, itm_render_state* r, int w, int h, const float intr[4], int wc, int hc, const float intrRgb[4],
+                                                    const float* rgbToDepth, const float* rgbToDepthInv, const uint8_t* rgbFrames, int nFrames, const int16_t* raw,
+                                                    const float* externalPoses, int trackerType, int useApproximateRaycast, int skipPoints,
+                                                    const uint8_t* fusionActive, const uint8_t* mainProcessingActive, const itm_tracker_config* cfg,
+                                                    int32_t* age, int32_t* full, float* poses, uint64_t* digest) {
+  const Vector2i sz(w, h), csz(wc, hc);
+  const Vector2i tracked = trackerType == 0 ? csz : sz;
+  if (r->w != tracked.x || r->h != tracked.y) return fail(ITM_ERR_INVALID, "the render state must have the tracked image's size");
   ITMRGBDCalib& calib = r->calib;
   calib.intrinsics_d.SetFrom(intr[0], intr[1], intr[2], intr[3], (float)w, (float)h);
-  calib.intrinsics_rgb.SetFrom(intr[0], intr[1], intr[2], intr[3], (float)w, (float)h);
+  calib.intrinsics_rgb.SetFrom(intrRgb[0], intrRgb[1], intrRgb[2], intrRgb[3], (float)wc, (float)hc);
+  if (rgbToDepth) set_matrix(calib.trafo_rgb_to_depth.calib, rgbToDepth);
+  if (rgbToDepthInv) set_matrix(calib.trafo_rgb_to_depth.calib_inv, rgbToDepthInv);
   calib.disparityCalib.params = Vector2f(0.001f, 0.0f);
   calib.disparityCalib.type = ITMDisparityCalib::TRAFO_AFFINE;
   ITMViewBuilder_CPU viewBuilder(&calib);
@@ -686,11 +695,12 @@ extern "C" int itmr_debug_main_engine_sequence(itm_scene* s, itm_render_state* r
   }
   ITMTrackingState* ts = r->ts;
   ITMView* view = NULL;
-  ITMUChar4Image rgb(sz, true, false);
-  for (int i = 0; i < w * h; ++i) rgb.GetData(MEMORYDEVICE_CPU)[i] = Vector4u((unsigned char)(i % w), (unsigned char)(i / w), (unsigned char)((i % w) ^ (i / w)), 255);
+  ITMUChar4Image rgb(csz, true, false);
+  for (int i = 0; i < wc * hc; ++i) rgb.GetData(MEMORYDEVICE_CPU)[i] = Vector4u((unsigned char)(i % wc), (unsigned char)(i / wc), (unsigned char)((i % wc) ^ (i / wc)), 255);
   ITMShortImage rawImg(sz, true, false);
   for (int k = 0; k < nFrames; ++k) {
     std::memcpy(rawImg.GetData(MEMORYDEVICE_CPU), raw + (size_t)k * w * h, (size_t)w * h * 2);
+    if (rgbFrames) std::memcpy(rgb.GetData(MEMORYDEVICE_CPU), rgbFrames + (size_t)k * wc * hc * 4, (size_t)wc * hc * 4);
     if (externalPoses) { Matrix4f M; set_matrix(M, externalPoses + 16 * k); ts->pose_d->SetM(M); }     // the pose source of this fork writes it before the frame
     // ---- ITMMainEngine::ProcessFrame
     viewBuilder.UpdateView(&view, &rgb, &rawImg, false, false);
@@ -724,10 +734,10 @@ extern "C" int itmr_debug_main_engine_sequence(itm_scene* s, itm_render_state* r
     }
     age[k] = ts->age_pointCloud; full[k] = ts->requiresFullRendering ? 1 : 0;
     std::memcpy(poses + 16 * k, ts->pose_d->GetM().m, 64);
-    const size_t nPts = trackerType == 0 ? (size_t)ts->pointCloud->noTotalPoints : (size_t)w * h;
+    const size_t nPts = trackerType == 0 ? (size_t)ts->pointCloud->noTotalPoints : (size_t)w * h;      // (locations AND colours of the cloud)
     digest[4 * k + 0] = fnv(ts->pointCloud->locations->GetData(MEMORYDEVICE_CPU), nPts * 16);
     digest[4 * k + 1] = fnv(ts->pointCloud->colours->GetData(MEMORYDEVICE_CPU), nPts * 16);
-    digest[4 * k + 2] = fnv(r->rs->raycastImage->GetData(MEMORYDEVICE_CPU), (size_t)w * h * 4);
+    digest[4 * k + 2] = fnv(r->rs->raycastImage->GetData(MEMORYDEVICE_CPU), (size_t)tracked.x * tracked.y * 4);
     uint64_t dv = nPts;
     if (r->hash) {
       ITMRenderState_VH* vh = (ITMRenderState_VH*)r->rs;
@@ -738,4 +748,12 @@ extern "C" int itmr_debug_main_engine_sequence(itm_scene* s, itm_render_state* r
   delete view;
   delete tracker;
   return ITM_OK;
+}
+
+extern "C" int itmr_debug_main_engine_sequence(itm_scene* s, itm_render_state* r, int w, int h, const float intr[4], int nFrames, const int16_t* raw,
+                                               const float* externalPoses, int trackerType, int useApproximateRaycast, int skipPoints,
+                                               const uint8_t* fusionActive, const uint8_t* mainProcessingActive, const itm_tracker_config* cfg,
+                                               int32_t* age, int32_t* full, float* poses, uint64_t* digest) {
+  return itmr_debug_main_engine_sequence_rgbd(s, r, w, h, intr, w, h, intr, NULL, NULL, NULL, nFrames, raw, externalPoses, trackerType, useApproximateRaycast, skipPoints,
+                                              fusionActive, mainProcessingActive, cfg, age, full, poses, digest);
 }

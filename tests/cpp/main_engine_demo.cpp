@@ -10,8 +10,10 @@
 //   main_engine_demo --bench-map[-host] <frames>   THIS FORK'S DEFAULT pipeline: TRACKER_EXTERNAL (Utils/ITMLibSettings.cpp:44) -- the pose source
 //                                             writes pose_d before every frame (Engine/RosPoseSourceEngine.cpp:112-118), ITMMainEngine::ProcessFrame
 //                                             builds the view from the raw frame, the tracker is a no-op, mapper + Prepare fuse and ray-cast
-// sequence file: int32 {w, h, n, trackerType, useApproximateRaycast, skipPoints, hasPoses}, float intr[4], int16 raw[n*h*w],
-//                float poses[n*16] (if hasPoses), uint8 fusion[n], uint8 mainProcessing[n]
+// sequence file: int32 {w, h, n, trackerType, useApproximateRaycast, skipPoints, flags}, float intr[4],
+//                [flags & 2, a colour camera of its own: int32 {wc, hc, voxelType}, float voxelSize, float intrRgb[4], float rgbToDepth[16],
+//                 float rgbToDepthInv[16]], int16 raw[n*h*w], float poses[n*16] (if flags & 1), uint8 fusion[n], uint8 mainProcessing[n],
+//                [flags & 2: uint8 rgb[n*hc*wc*4], one colour image per frame]
 #include <chrono>
 #include <cmath>
 #include <cstdint>
@@ -88,43 +90,44 @@ static int bench(int frames, bool fromHost, bool externalPoses = false) {
   return 0;
 }
 
-int main(int argc, char** argv) {
-  if (argc >= 3 && !strcmp(argv[1], "--bench")) return bench(atoi(argv[2]), false);
-  if (argc >= 3 && !strcmp(argv[1], "--bench-host")) return bench(atoi(argv[2]), true);
-  if (argc >= 3 && !strcmp(argv[1], "--bench-map")) return bench(atoi(argv[2]), false, true);
-  if (argc >= 3 && !strcmp(argv[1], "--bench-map-host")) return bench(atoi(argv[2]), true, true);
-  if (argc < 2) { fprintf(stderr, "usage: %s <sequence file> | --bench <frames>\n", argv[0]); return 2; }
-  FILE* f = fopen(argv[1], "rb");
-  if (!f) { perror(argv[1]); return 2; }
+struct Sequence {
   int32_t hd[7]; float intr[4];
-  if (!rd(f, hd, 7) || !rd(f, intr, 4)) return 2;
-  const int W = hd[0], H = hd[1], N = hd[2], P = W * H;
-  std::vector<int16_t> raw((size_t)N * P); std::vector<float> poses((size_t)N * 16); std::vector<uint8_t> fusion(N), mainOn(N);
-  if (!rd(f, raw.data(), raw.size()) || (hd[6] && !rd(f, poses.data(), poses.size())) || !rd(f, fusion.data(), (size_t)N) || !rd(f, mainOn.data(), (size_t)N)) return 2;
-  fclose(f);
+  int W = 0, H = 0, N = 0, Wc = 0, Hc = 0, voxelType = ITM_VOXEL_S;
+  bool ownCamera = false;                    // the colour camera has its own size, intrinsics, pose and one image per frame
+  float voxelSize = 0.005f, intrRgb[4], rgbToDepth[16], rgbToDepthInv[16];
+  std::vector<int16_t> raw; std::vector<float> poses; std::vector<uint8_t> fusion, mainOn, rgb;
+};
 
+template <class TV>
+static int parity(const Sequence& q) {
+  const int W = q.W, H = q.H, N = q.N;
+  const int32_t* hd = q.hd;
+  const size_t P = (size_t)W * H, Pc = (size_t)q.Wc * q.Hc;
   ITMLibSettings st = settings_for(hd[3], hd[4] != 0, hd[5] != 0);
-  ITMSceneParams params(0.02f, 100, 0.005f, 0.35f, 3.0f, false);      // ITMLibSettings.cpp:10
+  ITMSceneParams params(0.02f, 100, q.voxelSize, 0.35f, 3.0f, false);      // ITMLibSettings.cpp:10
   ITMRGBDCalib calib;
-  calib.intrinsics_d.SetFrom(intr[0], intr[1], intr[2], intr[3]);
-  calib.intrinsics_rgb = calib.intrinsics_d;
-  ITMMainEngine_HIP<V, I> engine(st, params, calib, Vector2i{W, H}, Vector2i{W, H});
+  calib.intrinsics_d.SetFrom(q.intr[0], q.intr[1], q.intr[2], q.intr[3]);
+  calib.intrinsics_rgb.SetFrom(q.intrRgb[0], q.intrRgb[1], q.intrRgb[2], q.intrRgb[3]);
+  if (q.ownCamera) { memcpy(calib.trafo_rgb_to_depth_calib, q.rgbToDepth, 64); memcpy(calib.trafo_rgb_to_depth_calib_inv, q.rgbToDepthInv, 64); }
+  ITMMainEngine_HIP<TV, I> engine(st, params, calib, Vector2i{q.Wc, q.Hc}, Vector2i{W, H});
+  const size_t PT = hd[3] == 0 ? Pc : P;      // the tracked image: the live render state and the point cloud have its size
   void *dRaw, *dRgb;
-  check(itm_dev_malloc(&dRaw, (size_t)P * 2), "malloc"); check(itm_dev_malloc(&dRgb, (size_t)P * 4), "malloc");
-  std::vector<uint8_t> rgb((size_t)P * 4);
-  for (int i = 0; i < P; ++i) { rgb[4 * i] = (uint8_t)(i % W); rgb[4 * i + 1] = (uint8_t)(i / W); rgb[4 * i + 2] = (uint8_t)((i % W) ^ (i / W)); rgb[4 * i + 3] = 255; }
+  check(itm_dev_malloc(&dRaw, P * 2), "malloc"); check(itm_dev_malloc(&dRgb, Pc * 4), "malloc");
+  std::vector<uint8_t> rgb(Pc * 4);
+  for (size_t i = 0; i < Pc; ++i) { rgb[4 * i] = (uint8_t)(i % q.Wc); rgb[4 * i + 1] = (uint8_t)(i / q.Wc); rgb[4 * i + 2] = (uint8_t)((i % q.Wc) ^ (i / q.Wc)); rgb[4 * i + 3] = 255; }
   check(itm_memcpy_h2d(dRgb, rgb.data(), rgb.size(), nullptr), "h2d");
-  std::vector<float> pts((size_t)P * 4), col((size_t)P * 4); std::vector<uint8_t> img((size_t)P * 4); std::vector<int32_t> ids;
+  std::vector<float> pts(PT * 4), col(PT * 4); std::vector<uint8_t> img(PT * 4); std::vector<int32_t> ids;
   for (int k = 0; k < N; ++k) {
-    check(itm_memcpy_h2d(dRaw, raw.data() + (size_t)k * P, (size_t)P * 2, nullptr), "h2d");
+    check(itm_memcpy_h2d(dRaw, q.raw.data() + (size_t)k * P, P * 2, nullptr), "h2d");
+    if (q.ownCamera) check(itm_memcpy_h2d(dRgb, q.rgb.data() + (size_t)k * Pc * 4, Pc * 4, nullptr), "h2d");
     ITMTrackingState* ts = engine.GetTrackingState();
-    if (hd[6]) ts->pose_d.SetM(poses.data() + 16 * k);            // the pose source of this fork writes it before the frame
-    if (fusion[k]) engine.turnOnIntegration(); else engine.turnOffIntegration();
-    if (mainOn[k]) engine.turnOnMainProcessing(); else engine.turnOffMainProcessing();
+    if (hd[6] & 1) ts->pose_d.SetM(q.poses.data() + 16 * k);            // the pose source of this fork writes it before the frame
+    if (q.fusion[k]) engine.turnOnIntegration(); else engine.turnOffIntegration();
+    if (q.mainOn[k]) engine.turnOnMainProcessing(); else engine.turnOffMainProcessing();
     engine.ProcessFrame((const uint8_t*)dRgb, (const int16_t*)dRaw);
     itm_counters c;
     check(itm_get_counters(engine.GetScene()->handle, engine.GetRenderState()->handle, &c, nullptr), "counters");
-    const size_t nPts = hd[3] == 0 ? (size_t)c.noTotalPoints : (size_t)P;
+    const size_t nPts = hd[3] == 0 ? (size_t)c.noTotalPoints : P;
     check(itm_memcpy_d2h(pts.data(), ts->pointCloud_locations, nPts * 16, nullptr), "d2h");
     check(itm_memcpy_d2h(col.data(), ts->pointCloud_colours, nPts * 16, nullptr), "d2h");
     check(itm_download(engine.GetScene()->handle, engine.GetRenderState()->handle, ITM_BUF_RAYCAST_IMAGE, img.data(), img.size(), nullptr), "download");
@@ -139,4 +142,35 @@ int main(int argc, char** argv) {
   }
   itm_dev_free(dRaw); itm_dev_free(dRgb);
   return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc >= 3 && !strcmp(argv[1], "--bench")) return bench(atoi(argv[2]), false);
+  if (argc >= 3 && !strcmp(argv[1], "--bench-host")) return bench(atoi(argv[2]), true);
+  if (argc >= 3 && !strcmp(argv[1], "--bench-map")) return bench(atoi(argv[2]), false, true);
+  if (argc >= 3 && !strcmp(argv[1], "--bench-map-host")) return bench(atoi(argv[2]), true, true);
+  if (argc < 2) { fprintf(stderr, "usage: %s <sequence file> | --bench <frames>\n", argv[0]); return 2; }
+  FILE* f = fopen(argv[1], "rb");
+  if (!f) { perror(argv[1]); return 2; }
+  Sequence q;
+  if (!rd(f, q.hd, 7) || !rd(f, q.intr, 4)) return 2;
+  q.W = q.hd[0]; q.H = q.hd[1]; q.N = q.hd[2]; q.Wc = q.W; q.Hc = q.H;
+  memcpy(q.intrRgb, q.intr, 16);
+  if (q.hd[6] & 2) {
+    int32_t ext[3];
+    if (!rd(f, ext, 3) || !rd(f, &q.voxelSize, 1) || !rd(f, q.intrRgb, 4) || !rd(f, q.rgbToDepth, 16) || !rd(f, q.rgbToDepthInv, 16)) return 2;
+    q.Wc = ext[0]; q.Hc = ext[1]; q.voxelType = ext[2]; q.ownCamera = true;
+  }
+  const size_t P = (size_t)q.W * q.H, Pc = (size_t)q.Wc * q.Hc;
+  q.raw.resize((size_t)q.N * P); q.poses.resize((size_t)q.N * 16); q.fusion.resize(q.N); q.mainOn.resize(q.N);
+  if (!rd(f, q.raw.data(), q.raw.size()) || ((q.hd[6] & 1) && !rd(f, q.poses.data(), q.poses.size())) || !rd(f, q.fusion.data(), (size_t)q.N) || !rd(f, q.mainOn.data(), (size_t)q.N)) return 2;
+  if (q.ownCamera) { q.rgb.resize((size_t)q.N * Pc * 4); if (!rd(f, q.rgb.data(), q.rgb.size())) return 2; }
+  fclose(f);
+  switch (q.voxelType) {
+    case ITM_VOXEL_S: return parity<ITMVoxel_s>(q);
+    case ITM_VOXEL_S_RGB: return parity<ITMVoxel_s_rgb>(q);
+    case ITM_VOXEL_F_RGB: return parity<ITMVoxel_f_rgb>(q);
+  }
+  fprintf(stderr, "voxel type %d not built into this demo\n", q.voxelType);
+  return 2;
 }

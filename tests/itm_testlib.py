@@ -58,8 +58,9 @@ def reference_backend() -> Optional[Backend]:
     """The reference's own CPU engines behind the same ABI; None where /root/reference is absent
     and no prebuilt oracle/_ref exists."""
     if "ref" not in _cache:
-        if not os.path.exists(REF_LIB) and os.path.isdir(REFERENCE_TREE):
-            subprocess.run(["make", "-C", ORACLE_DIR, "ref"], check=True, capture_output=True)
+        if os.path.isdir(REFERENCE_TREE):
+            # also where a library exists: oracle/Makefile rebuilds one that was made from another oracle/ref_driver.cpp (a no-op otherwise)
+            subprocess.run(["make", "-C", ORACLE_DIR, "_ref/libitm_ref.so"], check=not os.path.exists(REF_LIB), capture_output=True)
         _cache["ref"] = Backend(REF_LIB, "itmr_") if os.path.exists(REF_LIB) else None
     return _cache["ref"]
 
@@ -67,8 +68,8 @@ def reference_backend() -> Optional[Backend]:
 def reference_pool40000_backend() -> Optional[Backend]:
     """The reference's CPU engines compiled with the upstream pool size 0x40000 (oracle/Makefile target ref40000)."""
     if "ref40000" not in _cache:
-        if not os.path.exists(REF_POOL40000_LIB) and os.path.isdir(REFERENCE_TREE):
-            subprocess.run(["make", "-C", ORACLE_DIR, "ref40000"], check=True, capture_output=True)
+        if os.path.isdir(REFERENCE_TREE):
+            subprocess.run(["make", "-C", ORACLE_DIR, "ref40000"], check=not os.path.exists(REF_POOL40000_LIB), capture_output=True)
         _cache["ref40000"] = Backend(REF_POOL40000_LIB, "itmr_") if os.path.exists(REF_POOL40000_LIB) else None
     return _cache["ref40000"]
 

@@ -87,8 +87,12 @@ def test_argument_validation(oracle):
     s = oracle.create_scene(capi.VOXEL_S, capi.INDEX_HASH, capi.default_params())
     rs = s.vis.CreateRenderState((64, 48))
     d = oracle.to_backend(np.ones((48, 32), np.float32))
+    v = capi.View(d, 32, 48)
+    s.reco.AllocateSceneFromDepth(v, rs)                 # a render state of another size than the view is the reference's own use
+    assert s.counters(rs)["noVisibleEntries"] > 0
+    pts, nrm = capi.DevBuffer(oracle, 64 * 48 * 16, np.float32, (48, 64, 4)), capi.DevBuffer(oracle, 64 * 48 * 16, np.float32, (48, 64, 4))
     with pytest.raises(capi.ItmError):
-        s.reco.AllocateSceneFromDepth(capi.View(d, 32, 48), rs)   # view / render state size mismatch
+        s.process_frame(v, rs, pts, nrm)                 # the fused frame keeps the equal-size rule
 
 
 @pytest.mark.gpu
@@ -109,3 +113,9 @@ def test_argument_validation_hip(hip):
     other = hip.create_scene(capi.VOXEL_S, capi.INDEX_HASH, capi.default_params())
     with pytest.raises(capi.ItmError):
         other.reco.AllocateSceneFromDepth(capi.View(d, 64, 48), rs)  # render state of another scene
+    small = capi.View(hip.to_backend(np.ones((48, 32), np.float32)), 32, 48, rgb=hip.to_backend(synth.rgb_frame(32, 48)), w_rgb=32, h_rgb=48)
+    s.reco.AllocateSceneFromDepth(small, rs)             # a render state of another size than the view is accepted ...
+    assert s.counters(rs)["noVisibleEntries"] > 0
+    pts, nrm = capi.DevBuffer(hip, 64 * 48 * 16, np.float32, (48, 64, 4)), capi.DevBuffer(hip, 64 * 48 * 16, np.float32, (48, 64, 4))
+    with pytest.raises(capi.ItmError):
+        s.process_frame(small, rs, pts, nrm)             # ... but not by the fused frame

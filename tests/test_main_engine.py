@@ -8,7 +8,10 @@ Sequences (640x480, 5 mm voxels, useApproximateRaycast = true, a camera that cre
 off for frames 5-8, main processing for frame 10):
   external   poses from outside (this fork's default): every decision, pose and map digest equal, bit for bit
   icp        ITMDepthTracker: the decisions and ages equal, poses within the tracker's tolerance (2e-4: sums in another order)
-  colour     TRACKER_COLOR branch of Prepare with outside poses: expected depths through the rgb camera + CreatePointCloud"""
+  colour     TRACKER_COLOR branch of Prepare with outside poses: expected depths through the rgb camera + CreatePointCloud
+  colour_camera   the same branch with a colour camera of its own (tests/colour_camera_cases.py: 213 x 171 next to 160 x 120 depth, its own
+             intrinsics and rigid offset, one RGB image per frame) on ITMVoxel_s_rgb, 10 mm voxels, 8 frames, fusion off for two: the live
+             render state and the point cloud have the COLOUR camera's size, the allocation reads the depth image through it"""
 import ctypes as C
 import json
 import os
@@ -18,6 +21,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import colour_camera_cases as CCC
 import itm_testlib as T
 from infinitam_amd import capi, synth
 
@@ -26,10 +30,30 @@ GOLDEN = os.path.join(T.GOLDEN_DIR, "g_main_engine.json")
 SRC = os.path.join(T.ROOT, "tests", "cpp", "main_engine_demo.cpp")
 EXE = os.path.join(T.ROOT, "tests", "cpp", "main_engine_demo")
 XS = [0.0, .001, .002, .003, .004, .005, .006, .007, .008, .009, .010, .025, .040, .055, .056, .057]
-TRACKERS = {"colour": 0, "icp": 1, "external": 2}
+TRACKERS = {"colour": 0, "icp": 1, "external": 2, "colour_camera": 0}
+CAMERA = "larger_213x171"
+
+
+def colour_camera_sequence():
+    n = 8
+    w, h = CCC.W, CCC.H
+    wc, hc = CCC.size(CAMERA)
+    intr = np.array(CCC.INTR_D, np.float32)
+    pos = [(0.0137 + 0.0041 * k, -0.0071 + 0.0013 * k, 0.0043 - 0.0009 * k) for k in range(n)]
+    raw = np.stack([synth.raw_depth_mm(w, h, tuple(np.float32(v) for v in p), tuple(intr)) for p in pos]).astype(np.int16)
+    poses = np.stack([synth.pose_matrix_yaw(p, 0.031 - 0.0047 * k) for k, p in enumerate(pos)]).astype(np.float32)
+    base = synth.rgb_frame(wc, hc)
+    rgb = np.stack([np.roll(base, (3 * k, 5 * k), axis=(0, 1)) for k in range(n)])          # another image every frame
+    fusion = np.ones(n, np.uint8); fusion[3] = 0; fusion[6] = 0
+    calib, calib_inv = CCC.extrinsic()
+    return dict(n=n, w=w, h=h, intr=intr, raw=raw, poses=poses, fusion=fusion, main=np.ones(n, np.uint8), tracker=0, approx=1, skip=1,
+                wc=wc, hc=hc, intr_rgb=np.array(CCC.intr_rgb(CAMERA), np.float32), calib=calib, calib_inv=calib_inv, rgb=np.ascontiguousarray(rgb),
+                voxelType=capi.VOXEL_S_RGB, voxelSize=0.01)
 
 
 def sequence(kind):
+    if kind == "colour_camera":
+        return colour_camera_sequence()
     n = len(XS)
     intr = np.array(synth.intrinsics_for(W, H), np.float32)
     # the camera 15 cm beside the sphere's axis: on the axis the roll about the optical axis is unobservable and the ICP tracker's
@@ -39,25 +63,34 @@ def sequence(kind):
     poses = np.stack([synth.pose_matrix((np.float32(x), OFF, np.float32(0))) for x in XS]).astype(np.float32)
     fusion = np.ones(n, np.uint8); fusion[5:9] = 0
     main = np.ones(n, np.uint8); main[10] = 0
-    return dict(n=n, intr=intr, raw=raw, poses=(None if kind == "icp" else poses), fusion=fusion, main=main, tracker=TRACKERS[kind], approx=1, skip=1)
+    return dict(n=n, w=W, h=H, intr=intr, raw=raw, poses=(None if kind == "icp" else poses), fusion=fusion, main=main, tracker=TRACKERS[kind], approx=1, skip=1)
 
 
 def run_reference(ref, kind):
     """The sequence on the reference's objects (oracle/_ref/libitm_ref.so)."""
     q = sequence(kind)
-    s = ref.create_scene(capi.VOXEL_S, capi.INDEX_HASH, capi.default_params(voxelSize=0.005))
+    own = "wc" in q                      # a colour camera of its own: the render state has the tracked (= colour) image's size
+    s = ref.create_scene(q.get("voxelType", capi.VOXEL_S), capi.INDEX_HASH, capi.default_params(voxelSize=q.get("voxelSize", 0.005)))
     s.reco.ResetScene()
-    rs = s.vis.CreateRenderState((W, H))
+    rs = s.vis.CreateRenderState((q["wc"], q["hc"]) if own else (W, H))
     n = q["n"]
     age = np.zeros(n, np.int32); full = np.zeros(n, np.int32); poses = np.zeros((n, 16), np.float32); dig = np.zeros((n, 4), np.uint64)
     cfg = capi.TrackerConfig.default()
-    fn = ref.lib.itmr_debug_main_engine_sequence
-    fn.restype = C.c_int
     P = C.c_void_p
-    fn.argtypes = [P, P, C.c_int, C.c_int, P, C.c_int, P, P, C.c_int, C.c_int, C.c_int, P, P, P, P, P, P, P]
     ptr = lambda a: a.ctypes.data_as(P) if a is not None else None      # noqa: E731
-    rc = fn(s.h, rs.h, W, H, ptr(q["intr"]), n, ptr(q["raw"]), ptr(q["poses"]), q["tracker"], q["approx"], q["skip"], ptr(q["fusion"]), ptr(q["main"]),
-            C.cast(C.byref(cfg), P), ptr(age), ptr(full), ptr(poses), ptr(dig))
+    tail = [q["n"], ptr(q["raw"]), ptr(q["poses"]), q["tracker"], q["approx"], q["skip"], ptr(q["fusion"]), ptr(q["main"]),
+            C.cast(C.byref(cfg), P), ptr(age), ptr(full), ptr(poses), ptr(dig)]
+    tail_types = [C.c_int, P, P, C.c_int, C.c_int, C.c_int, P, P, P, P, P, P, P]
+    if own:
+        fn = ref.lib.itmr_debug_main_engine_sequence_rgbd
+        fn.restype = C.c_int
+        fn.argtypes = [P, P, C.c_int, C.c_int, P, C.c_int, C.c_int, P, P, P, P] + tail_types
+        rc = fn(s.h, rs.h, q["w"], q["h"], ptr(q["intr"]), q["wc"], q["hc"], ptr(q["intr_rgb"]), ptr(q["calib"]), ptr(q["calib_inv"]), ptr(q["rgb"]), *tail)
+    else:
+        fn = ref.lib.itmr_debug_main_engine_sequence
+        fn.restype = C.c_int
+        fn.argtypes = [P, P, C.c_int, C.c_int, P] + tail_types
+        rc = fn(s.h, rs.h, W, H, ptr(q["intr"]), *tail)
     assert rc == 0
     return [{"k": k, "age": int(age[k]), "full": int(full[k]), "pose": [float(v) for v in poses[k]], "digest": ["%016x" % int(d) for d in dig[k]]} for k in range(n)]
 
@@ -76,12 +109,19 @@ def build_demo():
 def run_hip(kind, tmp_path):
     q = sequence(kind)
     path = os.path.join(str(tmp_path), "seq_%s.bin" % kind)
+    own = "wc" in q
     with open(path, "wb") as f:
-        f.write(struct.pack("7i", W, H, q["n"], q["tracker"], q["approx"], q["skip"], 0 if q["poses"] is None else 1))
-        f.write(q["intr"].tobytes()); f.write(q["raw"].tobytes())
+        f.write(struct.pack("7i", q["w"], q["h"], q["n"], q["tracker"], q["approx"], q["skip"], (0 if q["poses"] is None else 1) | (2 if own else 0)))
+        f.write(q["intr"].tobytes())
+        if own:
+            f.write(struct.pack("3if", q["wc"], q["hc"], q["voxelType"], q["voxelSize"]))
+            f.write(q["intr_rgb"].tobytes()); f.write(np.asarray(q["calib"], np.float32).tobytes()); f.write(np.asarray(q["calib_inv"], np.float32).tobytes())
+        f.write(q["raw"].tobytes())
         if q["poses"] is not None:
             f.write(q["poses"].tobytes())
         f.write(q["fusion"].tobytes()); f.write(q["main"].tobytes())
+        if own:
+            f.write(q["rgb"].tobytes())
     out = subprocess.run([build_demo(), path], check=True, capture_output=True, text=True).stdout
     return [json.loads(line) for line in out.strip().splitlines() if line.startswith("{")]
 
@@ -103,10 +143,12 @@ def test_golden_is_what_the_reference_objects_give():
     # the sequence exercises the state machine: full renders at the start, on old age and on a jump; forward renders in between
     assert [e["full"] for e in ext] == [1, 1, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0] or sum(e["full"] for e in ext) >= 4, [e["full"] for e in ext]
     assert max(e["age"] for e in ext) >= 5 and min(e["age"] for e in ext) == -2
+    # the colour camera's sequence produces a cloud on every frame (the digests are of its locations AND colours)
+    assert all(e["age"] == 0 for e in g["colour_camera"]) and len({e["digest"][1] for e in g["colour_camera"]}) >= 6
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("kind", ["external", "colour", "icp"])
+@pytest.mark.parametrize("kind", ["external", "colour", "icp", "colour_camera"])
 def test_main_engine_on_hip_equals_the_reference_objects(kind, tmp_path):
     with open(GOLDEN) as f:
         want = json.load(f)[kind]
