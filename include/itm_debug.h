@@ -95,6 +95,11 @@ int ITM_FN(debug_icp_track)(const itm_tracker_config* cfg, const float M_d[16], 
 int ITM_FN(debug_wicp_track)(const itm_tracker_config* cfg, const float M_d[16], itm_icp_evaluate_fn evaluate,
                              void* user, float M_d_out[16]);
 
+/* Measurement hook of the keyframe relocaliser (tools/reloc_bench.py): enable != 0 brackets the two search launches of every later
+ * itm_reloc_find / itm_reloc_process_frame on this handle with device events (two event records per call; off by default).  *ms, when
+ * not NULL, receives the device time of the last bracketed search, -1 if there is none. */
+int ITM_FN(debug_reloc_search_ms)(struct itm_reloc* reloc, int enable, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -807,6 +807,71 @@ typedef struct itm_query_out {      /* device pointers, NULL = not wanted */
 int ITM_FN(scene_query_points)(const itm_scene* scene, const float* points_dev, uint32_t n, int units, const itm_query_out* out, itm_stream stream);
 int ITM_FN(scene_cast_rays)(const itm_scene* scene, const float* rays_dev, uint32_t n, float* hits_dev, itm_stream stream);
 
+/* ---- keyframe relocaliser: "where have I seen this depth image before?" -------------------------------------------------------------
+ * Randomised ferns over a small, smoothed depth image (Glocker et al., Real-Time RGB-D Camera Relocalization via Randomized Ferns
+ * for Keyframe Encoding): a code of numFerns bytes per frame, a database of keyframe codes (device memory) with their poses (host),
+ * a nearest-code search.  The reference at this revision has none; a host that has lost the pose takes the nearest keyframe's pose,
+ * ray-casts from there and lets a tracker refine (ITMMainEngine_HIP::Relocalise).  The handle touches no scene.
+ *
+ * Sequential definition (the kernels reproduce it bit for bit; every product and sum is rounded separately, division is IEEE).
+ *  1. Image.  I_0 is the float depth image, w x h, metres; a pixel <= 0 is a hole.  For l = 1 .. levels: I_l =
+ *     FilterSubsampleWithHoles(I_{l-1}) (itm_filter_subsample_with_holes), sizes (w >> l, h >> l).  Then, for blurRadius R > 0, a
+ *     hole-aware separable blur with taps t[0 .. R], the pass along x first, then the pass along y on its output.  A pass, for an
+ *     output pixel: s = 0, n = 0; for i = -R .. R ascending, v the input at offset i along the axis: if that position is inside the
+ *     image and v > 0 then s = s + t[|i|] * v, n = n + t[|i|]; the output is n > 0 ? s / n : 0.  R = 0: no blur, S = I_levels.  The
+ *     result S has ws x hs = (w >> levels) x (h >> levels) pixels.
+ *  2. Code.  numFerns F ferns of numDecisions D decisions (1 <= D <= 8, 1 <= F <= ITM_RELOC_MAX_FERNS); decision (f, d) has a pixel
+ *     index pixel[f * D + d] in [0, ws * hs) and a threshold threshold[f * D + d]:
+ *     code[f] = sum_d (S[pixel[f * D + d]] > threshold[f * D + d] ? 1 << d : 0), one byte per fern.
+ *  3. Search.  The database holds `count` rows.  sim_i = #{f < F : row_i[f] == q[f]}.  Rows ordered by sim descending, then i
+ *     ascending; for j < k (1 <= k <= ITM_RELOC_MAX_K): ids[j] the j-th row, dist[j] = (float)(F - sim) / (float)F; for j >= count:
+ *     ids[j] = -1, dist[j] = 1.0f.
+ *  4. Harvest (itm_reloc_process_frame).  The search result is that of the database BEFORE the call.  If harvest != 0 and (count ==
+ *     0 or dist[0] > harvestThreshold) and count < capacity: the code becomes row `count`, M_d its pose, *added = the old count.  If
+ *     only count < capacity fails: *added = -2.  Otherwise *added = -1.
+ *  5. Defaults (host only).  levels: the smallest L with (w >> L) <= 40.  blurRadius 6, blurTaps[i] = (float)exp(-(double)(i * i) /
+ *     (2 * 2.5 * 2.5)).  numFerns 500, numDecisions 4, capacity 65536.  Default ferns from a seed by splitmix64 (x += 0x9E3779B97F4A7C15;
+ *     z = x; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; result z ^ z >> 31): for decision index
+ *     0 .. F * D - 1 in order, pixel = (next() >> 32) % (ws * hs), u = (float)(next() >> 40) * (1.0f / 16777216.0f), threshold =
+ *     lo + (hi - lo) * u in float (the metres a decision compares against: 0.2 and 3.0 span the default view frustum).
+ *
+ * Calls.  encode / find / process_frame enqueue on `stream`; encode never synchronises, find and process_frame synchronise `stream`
+ * exactly once, to read their result.  A handle is used from one host thread at a time; work it has pending on another stream is
+ * waited for first.  The calls without a stream (read, download, upload, save, load) wait for what the handle has pending.
+ *   encode         image and code of depth_dev (device float[h * w]); both stay in the handle
+ *   find           nearest rows of code_host (numFerns bytes), or of the last encoded code when NULL
+ *   process_frame  encode + find + harvest; M_d (world -> camera, as itm_view) may be NULL when harvest == 0
+ *   read           the last encode's small image (float[hs * ws]) and code (numFerns bytes); either may be NULL
+ *   download       codes_host[count * numFerns], poses_host[count * 16]; either may be NULL
+ *   upload         replaces the database by n rows
+ *   save / load    one file, relocaliser.dat, in an existing directory (beside a scene checkpoint): configuration, ferns, codes and
+ *                  poses.  Loading into a handle whose configuration (capacity apart) or ferns differ: ITM_ERR_INVALID.
+ * ITM_ERR_INVALID with the handle untouched: a size that does not survive `levels` halvings, F, D, k or blurRadius (0 .. 8) out of
+ * range, a pixel index outside the small image, an id outside the database, more rows than the capacity. */
+#define ITM_RELOC_MAX_K 8
+#define ITM_RELOC_MAX_FERNS 1024
+typedef struct itm_reloc itm_reloc;
+typedef struct itm_reloc_config {
+  int32_t w, h, levels, blurRadius;
+  float blurTaps[9];
+  int32_t numFerns, numDecisions, capacity;
+} itm_reloc_config;
+int ITM_FN(reloc_default_config)(int w, int h, itm_reloc_config* cfg);
+int ITM_FN(reloc_default_ferns)(const itm_reloc_config* cfg, uint64_t seed, float lo, float hi, int32_t* pixel, float* threshold);
+int ITM_FN(reloc_create)(const itm_reloc_config* cfg, const int32_t* pixel_host, const float* threshold_host, itm_reloc** out);
+int ITM_FN(reloc_destroy)(itm_reloc* reloc);
+int ITM_FN(reloc_encode)(itm_reloc* reloc, const float* depth_dev, itm_stream stream);
+int ITM_FN(reloc_find)(itm_reloc* reloc, const uint8_t* code_host, int k, int32_t* ids_host, float* dist_host, itm_stream stream);
+int ITM_FN(reloc_process_frame)(itm_reloc* reloc, const float* depth_dev, const float M_d[16], int harvest, float harvestThreshold, int k,
+                                int32_t* ids_host, float* dist_host, int32_t* added, itm_stream stream);
+int ITM_FN(reloc_info)(const itm_reloc* reloc, int32_t* count, itm_reloc_config* cfg);
+int ITM_FN(reloc_get_pose)(const itm_reloc* reloc, int32_t id, float M[16]);
+int ITM_FN(reloc_read)(itm_reloc* reloc, float* image_host, uint8_t* code_host);
+int ITM_FN(reloc_download)(itm_reloc* reloc, uint8_t* codes_host, float* poses_host);
+int ITM_FN(reloc_upload)(itm_reloc* reloc, int32_t n, const uint8_t* codes_host, const float* poses_host);
+int ITM_FN(reloc_save)(itm_reloc* reloc, const char* dir);
+int ITM_FN(reloc_load)(itm_reloc* reloc, const char* dir);
+
 /* The acceleration structures a hash scene carries beside the reference's table (none of them part of the reference's state, all
  * derived from it): a block directory and a slot directory over a cube of 512^3 blocks, an sdf mirror over 256^3 blocks for the
  * short voxel types.  The cubes are NOT tied to the world origin: the first frame places them around its camera (the reference's

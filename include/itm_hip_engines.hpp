@@ -36,6 +36,7 @@ struct ITMVoxelBlockHash { static constexpr int kType = ITM_INDEX_HASH; };
 struct ITMPlainVoxelArray { static constexpr int kType = ITM_INDEX_DENSE; };
 
 struct Vector2i { int x, y; };
+struct Vector2f { float x, y; };
 struct Vector4u { uint8_t x, y, z, w; };
 
 // ITMUChar4Image (Utils/ITMLibDefines.h, ORUtils/Image.h) as far as ITMMainEngine::GetImage needs it: a host image of Vector4u
@@ -138,6 +139,11 @@ struct ITMLibSettings {
   int noICPRunTillLevel = 0;
   // TRACKER_COLOR: false (default) keeps this fork's behaviour, poses from outside; true builds ITMColorTracker_HIP
   bool useColourTracker = false;
+  // Keyframe relocaliser (ITMRelocaliser_HIP; the reference at this revision has none).  false (default): nothing is created and no
+  // code path changes.  true: ITMMainEngine_HIP harvests keyframes while it fuses and offers Relocalise().
+  bool useRelocalisation = false;
+  float relocHarvestingThreshold = 0.2f;      // a frame becomes a keyframe when its nearest keyframe is further than this
+  int relocCapacity = 65536;                  // rows of the keyframe database
 };
 
 struct ITMSceneParams : itm_scene_params {
@@ -588,6 +594,58 @@ inline void matmul4(const float* lhs, const float* rhs, float* out) {
   }
 }
 
+// Keyframe relocaliser (itm_reloc_*, include/itm_hip.h): fern codes of the depth frames, a database of keyframe codes with their
+// poses, the nearest-code search.  range: the depths in metres the default ferns' thresholds are drawn from.
+class ITMRelocaliser_HIP {
+  itm_reloc* handle = nullptr;
+  float harvestingThreshold;
+
+ public:
+  itm_stream stream = nullptr;
+  ITMRelocaliser_HIP(Vector2i imgSize, Vector2f range, float harvestingThreshold_ = 0.2f, int numFerns = 500, int numDecisions = 4, int capacity = 65536,
+                     uint64_t seed = 1)
+      : harvestingThreshold(harvestingThreshold_) {
+    itm_reloc_config cfg;
+    check(itm_reloc_default_config(imgSize.x, imgSize.y, &cfg), "itm_reloc_default_config");
+    cfg.numFerns = numFerns; cfg.numDecisions = numDecisions; cfg.capacity = capacity;
+    const size_t n = (size_t)(numFerns > 0 ? numFerns : 0) * (size_t)(numDecisions > 0 ? numDecisions : 0);
+    std::vector<int32_t> pixel(n ? n : 1);
+    std::vector<float> threshold(n ? n : 1);
+    check(itm_reloc_default_ferns(&cfg, seed, range.x, range.y, pixel.data(), threshold.data()), "itm_reloc_default_ferns");
+    check(itm_reloc_create(&cfg, pixel.data(), threshold.data(), &handle), "itm_reloc_create");
+  }
+  ~ITMRelocaliser_HIP() { itm_reloc_destroy(handle); }
+  ITMRelocaliser_HIP(const ITMRelocaliser_HIP&) = delete;
+  ITMRelocaliser_HIP& operator=(const ITMRelocaliser_HIP&) = delete;
+
+  // depth: device float image of imgSize.  The k nearest keyframes of the database as it was before the call into nearest[] /
+  // distances[] (-1 / 1.0 where there are fewer); with harvest, the frame becomes a keyframe with `pose` when its nearest one is
+  // further than the harvesting threshold.  Returns the id added, or -1 (also when the database is full).
+  int ProcessFrame(const float* depth, const ITMPose* pose, int k, int nearest[], float distances[], bool harvest) {
+    int32_t ids[ITM_RELOC_MAX_K], added = -1;
+    float dist[ITM_RELOC_MAX_K];
+    check(itm_reloc_process_frame(handle, depth, pose ? pose->GetM() : nullptr, harvest && pose ? 1 : 0, harvestingThreshold, k, ids, dist, &added, stream),
+          "ITMRelocaliser_HIP::ProcessFrame");
+    for (int j = 0; j < k; ++j) { nearest[j] = ids[j]; distances[j] = dist[j]; }
+    return added >= 0 ? added : -1;
+  }
+  ITMPose RetrievePose(int id) const {
+    ITMPose p;
+    float M[16];
+    check(itm_reloc_get_pose(handle, id, M), "ITMRelocaliser_HIP::RetrievePose");
+    p.SetM(M);
+    return p;
+  }
+  int NumKeyframes() const {
+    int32_t n = 0;
+    check(itm_reloc_info(handle, &n, nullptr), "itm_reloc_info");
+    return n;
+  }
+  void SaveToDirectory(const char* dir) { check(itm_reloc_save(handle, dir), "ITMRelocaliser_HIP::SaveToDirectory"); }
+  void LoadFromDirectory(const char* dir) { check(itm_reloc_load(handle, dir), "ITMRelocaliser_HIP::LoadFromDirectory"); }
+  itm_reloc* Handle() { return handle; }
+};
+
 // ITMTrackingController (Engine/ITMTrackingController.cpp:11-46): Track and Prepare, statement for statement
 template <class TVoxel, class TIndex>
 class ITMTrackingController_HIP {
@@ -656,6 +714,8 @@ class ITMMainEngine_HIP {
   itm_mesh* exportMesh = nullptr;      // created by the first SaveSceneTo* call
   ITMRenderState* renderState_freeview = nullptr;      // created by the first free-camera GetImage
   void* depthImageBuf = nullptr;                       // device uchar4 of the depth size: the coloured depth / uncertainty image of GetImage
+  ITMRelocaliser_HIP* relocaliser = nullptr;           // settings.useRelocalisation
+  bool harvestingActive = true;
 
  public:
   // calibType / c0 / c1: ITMDisparityCalib (0 = TRAFO_KINECT, 1 = TRAFO_AFFINE); sizes as ITMMainEngine's imgSize_rgb / imgSize_d
@@ -698,8 +758,12 @@ class ITMMainEngine_HIP {
       tracker = new ITMExternalTracker();          // TRACKER_EXTERNAL, and TRACKER_COLOR with poses from outside (useColourTracker = false)
     }
     trackingController = new ITMTrackingController_HIP<TVoxel, TIndex>(tracker, &visualisationEngine, &settings);
+    if (settings.useRelocalisation)
+      relocaliser = new ITMRelocaliser_HIP(imgSize_d, Vector2f{params.viewFrustum_min, params.viewFrustum_max}, settings.relocHarvestingThreshold, 500, 4,
+                                           settings.relocCapacity);
   }
   ~ITMMainEngine_HIP() {
+    delete relocaliser;
     itm_mesh_destroy(exportMesh);
     delete renderState_freeview; itm_dev_free(depthImageBuf);
     delete renderState_live; delete trackingController; delete tracker; delete depthTracker; delete colourTracker; delete renTracker; delete wicpTracker; delete viewBuilder;
@@ -765,9 +829,48 @@ class ITMMainEngine_HIP {
     if (fusionActive) denseMapper.ProcessFrame(&view, &trackingState, &scene, renderState_live);
     // expected depths + ICP maps (or the forward projection) from the new pose: what the next Track call and the UI read
     trackingController->Prepare(&trackingState, &view, renderState_live);
+    // the frame as a keyframe candidate, under the pose it was fused with
+    if (relocaliser && fusionActive && harvestingActive) {
+      int nearest; float distance;
+      relocaliser->ProcessFrame(view.depth, &trackingState.pose_d, 1, &nearest, &distance, true);
+    }
   }
 
  public:
+  // Keyframe relocaliser (settings.useRelocalisation; nullptr without it).  While fusion is active every frame is offered to it as a
+  // keyframe under its pose; SetKeyframeHarvesting(false) stops that (a host that knows its poses are poor).
+  ITMRelocaliser_HIP* GetRelocaliser() { return relocaliser; }
+  void SetKeyframeHarvesting(bool on) { harvestingActive = on; }
+  // The pose is lost (the host decides when): builds the view from the raw frame as ProcessFrame does and asks for the nearest
+  // keyframe, without harvesting.  None (or no relocaliser): returns -1 and changes nothing else.  Otherwise pose_d becomes the
+  // keyframe's pose, the live visible list is rebuilt for it (FindVisibleBlocks), and Prepare, Track, Prepare run with a full ray
+  // cast: the tracker refines against maps rendered from the keyframe's pose, and the maps the next frame tracks against are
+  // rendered from the refined pose.  Nothing is integrated.  Returns the keyframe's id.
+  int Relocalise(const uint8_t* rgbImage, const int16_t* rawDepthImage) {
+    view.rgb = rgbImage;
+    viewBuilder->UpdateView(&view, rawDepthImage, (float*)depthBuf, (float*)scratchBuf, settings.useBilateralFilter, ModelSensorNoise(),
+                            (float*)normalBuf, (float*)sigmaBuf);
+    view.depthUncertainty = ModelSensorNoise() ? (const float*)sigmaBuf : nullptr;
+    if (!relocaliser) return -1;
+    int nearest = -1; float distance = 1.0f;
+    relocaliser->ProcessFrame(view.depth, nullptr, 1, &nearest, &distance, false);
+    if (nearest < 0) return -1;
+    trackingState.pose_d = relocaliser->RetrievePose(nearest);
+    if (settings.trackerType == ITMLibSettings::TRACKER_COLOR) {      // the live render state is the colour camera's (Prepare)
+      ITMPose pose_rgb;
+      float M[16];
+      matmul4(view.calib.trafo_rgb_to_depth_calib_inv, trackingState.pose_d.GetM(), M);
+      pose_rgb.SetM(M);
+      visualisationEngine.FindVisibleBlocks(&pose_rgb, &view.calib.intrinsics_rgb, renderState_live);
+    } else {
+      visualisationEngine.FindVisibleBlocks(&trackingState.pose_d, &view.calib.intrinsics_d, renderState_live);
+    }
+    trackingState.requiresFullRendering = true;
+    trackingController->Prepare(&trackingState, &view, renderState_live);
+    trackingController->Track(&trackingState, &view);
+    trackingController->Prepare(&trackingState, &view, renderState_live);
+    return nearest;
+  }
   void turnOnIntegration() { fusionActive = true; }
   void turnOffIntegration() { fusionActive = false; }
   void turnOnMainProcessing() { mainProcessingActive = true; }

@@ -10,7 +10,7 @@ import os
 import subprocess
 
 from . import capi, synth  # noqa: F401
-from .capi import (Backend, DevBuffer, ItmError, RenderState, Scene, View,  # noqa: F401
+from .capi import (Backend, DevBuffer, ItmError, Relocaliser, RenderState, Scene, View,  # noqa: F401
                    default_params)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))

@@ -184,6 +184,15 @@ QUERY_OUTPUTS = {"sdf": (np.float32, ()), "sdf_nearest": (np.float32, ()), "grad
                  "colour": (np.uint8, (4,)), "weight": (np.uint8, ()), "flags": (np.uint32, ())}
 
 
+class RelocConfig(C.Structure):
+    """itm_reloc_config (include/itm_hip.h, the keyframe relocaliser)."""
+    _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("levels", C.c_int32), ("blurRadius", C.c_int32), ("blurTaps", C.c_float * 9),
+                ("numFerns", C.c_int32), ("numDecisions", C.c_int32), ("capacity", C.c_int32)]
+
+
+RELOC_MAX_K, RELOC_MAX_FERNS = 8, 1024
+
+
 class ItmError(RuntimeError):
     pass
 
@@ -350,6 +359,22 @@ _HOST_IO_SIGS = {
     # scene queries at caller-supplied points / along caller-supplied rays (product only: the reference reads per pixel, inside its engines)
     "scene_query_points": (C.c_int, [_P, _P, C.c_uint32, C.c_int, C.POINTER(QueryOut), _P]),
     "scene_cast_rays": (C.c_int, [_P, _P, C.c_uint32, _P, _P]),
+    # keyframe relocaliser (product only: the reference at this revision has none); the two defaults are host-only
+    "reloc_default_config": (C.c_int, [C.c_int, C.c_int, C.POINTER(RelocConfig)]),
+    "reloc_default_ferns": (C.c_int, [C.POINTER(RelocConfig), C.c_uint64, C.c_float, C.c_float, _P, _P]),
+    "reloc_create": (C.c_int, [C.POINTER(RelocConfig), _P, _P, C.POINTER(_P)]),
+    "reloc_destroy": (C.c_int, [_P]),
+    "reloc_encode": (C.c_int, [_P, _P, _P]),
+    "reloc_find": (C.c_int, [_P, _P, C.c_int, _P, _P, _P]),
+    "reloc_process_frame": (C.c_int, [_P, _P, C.POINTER(C.c_float), C.c_int, C.c_float, C.c_int, _P, _P, C.POINTER(C.c_int32), _P]),
+    "reloc_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(RelocConfig)]),
+    "reloc_get_pose": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_float)]),
+    "reloc_read": (C.c_int, [_P, _P, _P]),
+    "reloc_download": (C.c_int, [_P, _P, _P]),
+    "reloc_upload": (C.c_int, [_P, C.c_int32, _P, _P]),
+    "reloc_save": (C.c_int, [_P, C.c_char_p]),
+    "reloc_load": (C.c_int, [_P, C.c_char_p]),
+    "debug_reloc_search_ms": (C.c_int, [_P, C.c_int, C.POINTER(C.c_float)]),
 }
 
 
@@ -720,6 +745,127 @@ class Scene:
     def close(self):
         if self.h:
             self.be.fn["scene_destroy"](_P(self.h))
+            self.h = 0
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Relocaliser:
+    """itm_reloc: fern codes of depth frames, the keyframe database and its nearest-code search (include/itm_hip.h).
+
+    Relocaliser(be, w, h) takes every default; numFerns / numDecisions / capacity / levels / blurRadius / blurTaps override the
+    configuration, seed / lo / hi the default ferns, and pixel + threshold (arrays of numFerns * numDecisions) give explicit ferns."""
+
+    def __init__(self, be: Backend, w: int, h: int, numFerns=None, numDecisions=None, capacity=None, levels=None, blurRadius=None,
+                 blurTaps=None, seed=1, lo=0.2, hi=3.0, pixel=None, threshold=None):
+        self.be, self.h = be, 0
+        cfg = self.default_config(be, w, h)
+        for name, v in (("numFerns", numFerns), ("numDecisions", numDecisions), ("capacity", capacity), ("levels", levels), ("blurRadius", blurRadius)):
+            if v is not None:
+                setattr(cfg, name, int(v))
+        if blurTaps is not None:
+            taps = [float(t) for t in blurTaps]
+            cfg.blurTaps[:] = (taps + [0.0] * 9)[:9]
+        if pixel is None:
+            pixel, threshold = self.default_ferns(be, cfg, seed, lo, hi)
+        self.pixel = np.ascontiguousarray(np.asarray(pixel, np.int32).reshape(-1))
+        self.threshold = np.ascontiguousarray(np.asarray(threshold, np.float32).reshape(-1))
+        n = max(int(cfg.numFerns), 0) * max(int(cfg.numDecisions), 0)
+        if len(self.pixel) != n or len(self.threshold) != n:
+            raise ItmError(f"Relocaliser: {n} decisions need {n} pixels and thresholds")
+        p = _P()
+        be.check(be.fn["reloc_create"](C.byref(cfg), self.pixel.ctypes.data_as(_P), self.threshold.ctypes.data_as(_P), C.byref(p)), "reloc_create")
+        self.h, self.cfg = p.value, cfg
+        self.small = (int(cfg.h) >> int(cfg.levels), int(cfg.w) >> int(cfg.levels))      # (hs, ws)
+
+    @staticmethod
+    def default_config(be: Backend, w: int, h: int) -> RelocConfig:
+        cfg = RelocConfig()
+        be.check(be.fn["reloc_default_config"](int(w), int(h), C.byref(cfg)), "reloc_default_config")
+        return cfg
+
+    @staticmethod
+    def default_ferns(be: Backend, cfg: RelocConfig, seed=1, lo=0.2, hi=3.0):
+        n = max(int(cfg.numFerns), 0) * max(int(cfg.numDecisions), 0)
+        pixel, threshold = np.zeros(n, np.int32), np.zeros(n, np.float32)
+        be.check(be.fn["reloc_default_ferns"](C.byref(cfg), int(seed), float(lo), float(hi), pixel.ctypes.data_as(_P), threshold.ctypes.data_as(_P)),
+                 "reloc_default_ferns")
+        return pixel, threshold
+
+    @staticmethod
+    def _dev(depth) -> int:
+        return depth.ptr if isinstance(depth, DevBuffer) else int(depth)
+
+    @property
+    def count(self) -> int:
+        n = C.c_int32()
+        self.be.check(self.be.fn["reloc_info"](_P(self.h), C.byref(n), None), "reloc_info")
+        return n.value
+
+    def encode(self, depth, stream=None):
+        """Enqueues the image and code kernels for a device depth image (DevBuffer or pointer); nothing is waited for."""
+        self.be.check(self.be.fn["reloc_encode"](_P(self.h), _P(self._dev(depth)), _P(stream)), "reloc_encode")
+
+    def read(self):
+        """(small image float32[hs, ws], code uint8[numFerns]) of the last encode."""
+        img, code = np.zeros(self.small, np.float32), np.zeros(int(self.cfg.numFerns), np.uint8)
+        self.be.check(self.be.fn["reloc_read"](_P(self.h), img.ctypes.data_as(_P), code.ctypes.data_as(_P)), "reloc_read")
+        return img, code
+
+    def find(self, code=None, k=1, stream=None):
+        """(ids int32[k], dist float32[k]) of the rows nearest to `code` (uint8[numFerns]; None: the last encoded code)."""
+        kk = max(int(k), 1)
+        ids, dist = np.zeros(kk, np.int32), np.zeros(kk, np.float32)
+        c = None
+        if code is not None:
+            c = np.ascontiguousarray(np.asarray(code, np.uint8).reshape(-1))
+            if len(c) != int(self.cfg.numFerns):
+                raise ItmError("Relocaliser.find: a code has numFerns bytes")
+        self.be.check(self.be.fn["reloc_find"](_P(self.h), c.ctypes.data_as(_P) if c is not None else None, int(k), ids.ctypes.data_as(_P),
+                                               dist.ctypes.data_as(_P), _P(stream)), "reloc_find")
+        return ids, dist
+
+    def process_frame(self, depth, M_d=None, harvest=True, harvestThreshold=0.2, k=1, stream=None):
+        """itm_reloc_process_frame: (ids, dist, added)."""
+        kk = max(int(k), 1)
+        ids, dist, added = np.zeros(kk, np.int32), np.zeros(kk, np.float32), C.c_int32()
+        Mp = _fptr(M_d)[1] if M_d is not None else None
+        self.be.check(self.be.fn["reloc_process_frame"](_P(self.h), _P(self._dev(depth)), Mp, int(bool(harvest)), float(harvestThreshold), int(k),
+                                                        ids.ctypes.data_as(_P), dist.ctypes.data_as(_P), C.byref(added), _P(stream)), "reloc_process_frame")
+        return ids, dist, added.value
+
+    def pose(self, id: int) -> np.ndarray:
+        M = (C.c_float * 16)()
+        self.be.check(self.be.fn["reloc_get_pose"](_P(self.h), int(id), M), "reloc_get_pose")
+        return np.array(M[:], np.float32)
+
+    def codes(self):
+        """(codes uint8[count, numFerns], poses float32[count, 16]) of the database."""
+        n = self.count
+        codes, poses = np.zeros((n, int(self.cfg.numFerns)), np.uint8), np.zeros((n, 16), np.float32)
+        self.be.check(self.be.fn["reloc_download"](_P(self.h), codes.ctypes.data_as(_P), poses.ctypes.data_as(_P)), "reloc_download")
+        return codes, poses
+
+    def upload(self, codes, poses):
+        codes = np.ascontiguousarray(np.asarray(codes, np.uint8).reshape(-1, int(self.cfg.numFerns)))
+        poses = np.ascontiguousarray(np.asarray(poses, np.float32).reshape(-1, 16))
+        if len(codes) != len(poses):
+            raise ItmError("Relocaliser.upload: one pose per code")
+        self.be.check(self.be.fn["reloc_upload"](_P(self.h), len(codes), codes.ctypes.data_as(_P), poses.ctypes.data_as(_P)), "reloc_upload")
+
+    def save(self, directory: str):
+        self.be.check(self.be.fn["reloc_save"](_P(self.h), directory.encode()), "reloc_save")
+
+    def load(self, directory: str):
+        self.be.check(self.be.fn["reloc_load"](_P(self.h), directory.encode()), "reloc_load")
+
+    def close(self):
+        if self.h:
+            self.be.fn["reloc_destroy"](_P(self.h))
             self.h = 0
 
     def __del__(self):
