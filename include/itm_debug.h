@@ -56,6 +56,14 @@ int ITM_FN(debug_div32767)(const float* in, float* out, int n, itm_stream stream
 /* out[i] = a[i] / b[i] through the reduced division sequences of the integration kernel (mode 1: shared
  * refined reciprocal; 2: small-integer divisor; 3: the refined reciprocal of b; 4: reciprocal given in r). */
 int ITM_FN(debug_divide)(int mode, const float* a, const float* b, const float* r, float* out, int n, itm_stream stream);
+/* The ordered compaction behind the visible list, FindVisibleBlocks, the mesher's slot list and the forward projection, in isolation:
+ * the n flags (HOST memory, elemBytes = 1: bytes as the hash callers pass them, n a multiple of 8; elemBytes = 4: int32 as the pixel
+ * callers do, any n) are copied to the device, counted per chunk of 2048 by a kernel of the hook's own and listed by the product
+ * launcher.  ids_host holds cap + ITM_DEBUG_ORDERED_GUARD entries: all of them are uploaded as the device list's contents before the
+ * launch and downloaded after it, so the caller sees every word the launch wrote -- the first min(total, cap) indices of the non-zero
+ * flags, ascending, and its own pattern everywhere else, also in the guard words past cap.  counts = {total, min(total, cap)}. */
+#define ITM_DEBUG_ORDERED_GUARD 8
+int ITM_FN(debug_ordered_compact)(const void* flags_host, int elemBytes, int n, int cap, int32_t* ids_host, int32_t counts[2], itm_stream stream);
 
 
 /* Read-only probes of the acceleration cubes of a hash scene (block directory, slot directory, sdf mirror: itm_types.h).  Both launch

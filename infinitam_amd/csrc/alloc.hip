@@ -25,7 +25,7 @@
 //                              the slot directory and the sdf mirror for the new block.
 //      b. visible list       : frustum re-test of type-3 slots and an ORDERED compaction (ascending
 //                              slot ids); counts travel between workgroups as 8-byte granules.
-//      (allocate_sweep_kernel / visible_count_kernel / visible_compact_kernel: the same steps as
+//      (allocate_sweep_kernel / visible_count_kernel / ordered_compact_kernel: the same steps as
 //      separate launches, kept for FindVisibleBlocks and behind test hooks.)
 // No host synchronisation: all counts stay in HBM.
 #include <cstdlib>
@@ -33,6 +33,7 @@
 
 #include "itm_internal.h"
 #include "alloc_device.h"
+#include "ordered_device.h"
 #include "wave_utils.h"
 
 namespace itm {
@@ -313,14 +314,12 @@ __global__ void __launch_bounds__(256) visible_count_kernel(uint8_t* __restrict_
   const int slot0 = chunk * kSweepChunk + tid * kSlotsPerThread;
   int n = 0;
   if (slot0 < p.noTotalEntries) {  // noTotalEntries is a multiple of 8 (checked on the host)
-    uint2 raw = *(const uint2*)(visT + slot0);
-    if (raw.x | raw.y) {
-      uint32_t w[2] = {raw.x, raw.y};
+    SlotBytes types = SlotBytes::load(visT + slot0);
+    if (types.w[0] | types.w[1]) {
       bool changed = false;
 #pragma unroll
       for (int k = 0; k < kSlotsPerThread; ++k) {
-        uint32_t t = (w[k >> 2] >> ((k & 3) * 8)) & 0xffu;
-        const uint32_t t0 = t;
+        uint32_t t = types.get(k);
         if (LAZY && (t & 0x80u)) {
           t &= 0x7fu;                         // touched this frame: type 1 / 2
         } else if (LAZY ? (t != 0u) : (t == 3u)) {
@@ -330,10 +329,10 @@ __global__ void __launch_bounds__(256) visible_count_kernel(uint8_t* __restrict_
                                           : block_in_frustum(he.px, he.py, he.pz, p.M, p.fx, p.fy, p.cx, p.cy, p.voxelSize, p.W, p.H);
           t = keep ? 3u : 0u;
         }
-        if (t != t0) { w[k >> 2] = (w[k >> 2] & ~(0xffu << ((k & 3) * 8))) | (t << ((k & 3) * 8)); changed = true; }
-        n += (t > 0u);
+        changed |= types.set(k, t);
       }
-      if (changed) *(uint2*)(visT + slot0) = make_uint2(w[0], w[1]);
+      if (changed) types.store(visT + slot0);
+      n = types.count();
     }
   }
   const int sum = block_reduce_sum<4>(n, lds);
@@ -347,40 +346,6 @@ __global__ void __launch_bounds__(256) visible_count_kernel(uint8_t* __restrict_
       counters->lastFreeBlockId -= a;
       counters->lastFreeExcessListId -= b;
       counters->noAllocRequests = a;
-    }
-  }
-}
-
-// Pass 2: ordered compaction of slots flagged in `flags` (non-zero byte) into ascending ids.
-__global__ void __launch_bounds__(256) visible_compact_kernel(const uint8_t* __restrict__ flags, const int32_t* __restrict__ chunkVis,
-                                                              int numChunks, int noTotalEntries, int32_t* __restrict__ ids, int capIds,
-                                                              RenderCounters* __restrict__ rc) {
-  __shared__ int lds[8];
-  const int chunk = blockIdx.x, tid = threadIdx.x;
-  const int mine = chunkVis[chunk];
-  if (chunk != 0 && mine == 0) return;
-  int b = 0, all = 0;
-  for (int j = tid; j < numChunks; j += 256) { int c = chunkVis[j]; all += c; if (j < chunk) b += c; }
-  const int base = block_reduce_sum<4>(b, lds);
-  if (chunk == 0) {
-    const int total = block_reduce_sum<4>(all, lds + 4);
-    if (tid == 0) { rc->rawVisibleCount = total; rc->noVisibleEntries = total < capIds ? total : capIds; }
-    if (mine == 0) return;
-  }
-  const int slot0 = chunk * kSweepChunk + tid * kSlotsPerThread;
-  uint32_t w[2] = {0u, 0u};
-  if (slot0 < noTotalEntries) { uint2 raw = *(const uint2*)(flags + slot0); w[0] = raw.x; w[1] = raw.y; }
-  int n = 0;
-#pragma unroll
-  for (int k = 0; k < kSlotsPerThread; ++k) n += (((w[k >> 2] >> ((k & 3) * 8)) & 0xffu) != 0u);
-  int tot;
-  int pos = base + block_exclusive_scan<4>(n, lds, &tot);
-  if (n == 0) return;
-#pragma unroll
-  for (int k = 0; k < kSlotsPerThread; ++k) {
-    if (((w[k >> 2] >> ((k & 3) * 8)) & 0xffu) != 0u) {
-      if (pos < capIds) ids[pos] = slot0 + k;
-      ++pos;
     }
   }
 }
@@ -643,23 +608,10 @@ __global__ void __launch_bounds__(256) visible_list_kernel(uint8_t* __restrict__
 // FindVisibleBlocks pass 1: flag every allocated slot whose block passes the frustum test.
 __global__ void __launch_bounds__(256) freeview_flag_kernel(const uint4* __restrict__ hash, uint8_t* __restrict__ flags,
                                                             int32_t* __restrict__ chunkVis, AllocParams p) {
-  __shared__ int lds[4];
-  const int chunk = blockIdx.x, tid = threadIdx.x;
-  const int slot0 = chunk * kSweepChunk + tid * kSlotsPerThread;
-  int n = 0;
-  if (slot0 < p.noTotalEntries) {
-    uint32_t w[2] = {0u, 0u};
-#pragma unroll
-    for (int k = 0; k < kSlotsPerThread; ++k) {
-      HashEntry he = unpack_entry(hash[slot0 + k]);
-      bool vis = false;
-      if (he.ptr >= 0) vis = block_in_frustum(he.px, he.py, he.pz, p.M, p.fx, p.fy, p.cx, p.cy, p.voxelSize, p.W, p.H);
-      if (vis) { w[k >> 2] |= 1u << ((k & 3) * 8); ++n; }
-    }
-    *(uint2*)(flags + slot0) = make_uint2(w[0], w[1]);
-  }
-  const int sum = block_reduce_sum<4>(n, lds);
-  if (tid == 0) chunkVis[chunk] = sum;
+  flag_chunk(p.noTotalEntries, flags, chunkVis, [&](int slot) {
+    const HashEntry he = unpack_entry(hash[slot]);
+    return he.ptr >= 0 && block_in_frustum(he.px, he.py, he.pz, p.M, p.fx, p.fy, p.cx, p.cy, p.voxelSize, p.W, p.H);
+  });
 }
 
 // Is this scene alone on its device?  (scene.hip keeps the count of live hash scenes.)
@@ -827,7 +779,9 @@ int launch_sweep_stage(itm_scene* s, const itm_view* v, itm_render_state* rs, bo
     if (onlyVisible) { if (lazy) ITM_CNT(false, true); else ITM_CNT(false, false); }
     else { if (lazy) ITM_CNT(true, true); else ITM_CNT(true, false); }
 #undef ITM_CNT
-    visible_compact_kernel<<<nChunks, 256, 0, st>>>(rs->visibleType, s->chunkVis, nChunks, s->noTotalEntries, rs->visibleIds, rs->capIds, rs->counters);
+    // pass 2: the non-zero types in ascending slot order
+    if ((rc = launch_ordered_compaction(rs->visibleType, s->chunkVis, nChunks, s->noTotalEntries, rs->visibleIds, rs->capIds, &rs->counters->rawVisibleCount,
+                                        &rs->counters->noVisibleEntries, st))) return rc;
   }
   ITM_LAUNCH_CHECK();
   rs->listCoherent = true;   // list == non-zero visible types again
@@ -839,13 +793,6 @@ int launch_allocate(itm_scene* s, const itm_view* v, itm_render_state* rs, bool 
   int rc = launch_request_stage(s, v, rs, onlyVisible, fuseRangeInit, st);
   if (rc) return rc;
   return launch_sweep_stage(s, v, rs, onlyVisible, st);
-}
-
-// ordered compaction of the slots flagged in `flags` (one byte per slot, chunk counts from the flagging pass) into ascending ids
-int launch_ordered_compaction(const uint8_t* flags, const int32_t* chunkCount, int nChunks, int nEntries, int32_t* ids, int cap, RenderCounters* rc, hipStream_t st) {
-  visible_compact_kernel<<<nChunks, 256, 0, st>>>(flags, chunkCount, nChunks, nEntries, ids, cap, rc);
-  ITM_LAUNCH_CHECK();
-  return ITM_OK;
 }
 
 int launch_find_visible(const itm_scene* s, const float* M, const float* intr, itm_render_state* rs, hipStream_t st) {
@@ -860,8 +807,8 @@ int launch_find_visible(const itm_scene* s, const float* M, const float* intr, i
     ITM_HIP(hipMalloc((void**)&rs->viewChunkVis, (size_t)nChunks * 4));
   }
   freeview_flag_kernel<<<nChunks, 256, 0, st>>>(s->hash, rs->viewFlags, rs->viewChunkVis, p);
-  visible_compact_kernel<<<nChunks, 256, 0, st>>>(rs->viewFlags, rs->viewChunkVis, nChunks, s->noTotalEntries, rs->visibleIds, rs->capIds, rs->counters);
-  ITM_LAUNCH_CHECK();
+  if ((rc = launch_ordered_compaction(rs->viewFlags, rs->viewChunkVis, nChunks, s->noTotalEntries, rs->visibleIds, rs->capIds, &rs->counters->rawVisibleCount,
+                                      &rs->counters->noVisibleEntries, st))) return rc;
   rs->listCoherent = false;   // the list no longer mirrors entriesVisibleType
   return ITM_OK;
 }
@@ -890,6 +837,12 @@ int cancel_ahead(itm_scene* s, itm_render_state* rs, hipStream_t st) {
   return ITM_OK;
 }
 
+// itm_debug_ordered_compact: the chunk counts a flagging pass would leave, one lane per element (nothing shared with the compaction)
+__global__ void __launch_bounds__(256) debug_chunk_count_kernel(const void* __restrict__ flags, int elemBytes, int n, int32_t* __restrict__ chunkCount) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n && (elemBytes == 1 ? ((const uint8_t*)flags)[i] != 0 : ((const int32_t*)flags)[i] != 0)) atomicAdd(&chunkCount[i / kSweepChunk], 1);
+}
+
 }  // namespace itm
 
 using namespace itm;
@@ -903,6 +856,35 @@ int itm_find_visible_blocks(const itm_scene* s, const float M[16], const float i
   { const int rc = enter_scene(s, rs); if (rc) return rc; }
   if (refuse_while_ahead(s, rs, "FindVisibleBlocks")) return ITM_ERR_INVALID;
   return launch_find_visible(s, M, intr, rs, as_stream(stream));
+}
+
+int itm_debug_ordered_compact(const void* flags_host, int elemBytes, int n, int cap, int32_t* ids_host, int32_t counts[2], itm_stream stream) {
+  if (!flags_host || !ids_host || !counts || n <= 0 || cap < 0 || (elemBytes != 1 && elemBytes != 4) || (elemBytes == 1 && n % 8 != 0))
+    return set_error(ITM_ERR_INVALID, "bad argument");
+  hipStream_t st = as_stream(stream);
+  // one buffer: the flags (padded to 8 bytes), the list with its guard words -- uploaded from ids_host, so that the caller sees afterwards
+  // whatever the launch wrote there --, the two totals, the chunk counts
+  const size_t flagBytes = ((size_t)n * elemBytes + 7) & ~(size_t)7, nList = (size_t)cap + ITM_DEBUG_ORDERED_GUARD;
+  const int nChunks = (n + kSweepChunk - 1) / kSweepChunk;
+  uint8_t* buf = nullptr;
+  ITM_HIP(hipMalloc((void**)&buf, flagBytes + (nList + 2 + nChunks) * 4));
+  int32_t* ids = (int32_t*)(buf + flagBytes);
+  int32_t* totals = ids + nList;
+  int32_t* chunkCount = totals + 2;
+  int rc = ITM_OK;
+  hipError_t e = hipMemcpyAsync(buf, flags_host, (size_t)n * elemBytes, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(ids, ids_host, nList * 4, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemsetAsync(chunkCount, 0, (size_t)nChunks * 4, st);
+  if (e == hipSuccess) {
+    debug_chunk_count_kernel<<<(n + 255) / 256, 256, 0, st>>>(buf, elemBytes, n, chunkCount);
+    rc = elemBytes == 1 ? launch_ordered_compaction((const uint8_t*)buf, chunkCount, nChunks, n, ids, cap, totals, totals + 1, st)
+                        : launch_ordered_compaction((const int32_t*)buf, chunkCount, nChunks, n, ids, cap, totals, totals + 1, st);
+  }
+  if (e == hipSuccess && !rc) e = hipMemcpyAsync(ids_host, ids, nList * 4, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && !rc) e = hipMemcpyAsync(counts, totals, 8, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && !rc) e = hipStreamSynchronize(st);
+  (void)hipFree(buf);
+  return e != hipSuccess ? hip_fail(e, "itm_debug_ordered_compact", __FILE__, __LINE__) : rc;
 }
 
 }  // extern "C"

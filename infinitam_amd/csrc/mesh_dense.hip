@@ -166,7 +166,7 @@ __global__ void __launch_bounds__(1024) mesh_brick_scan_kernel(const int32_t* __
       nonEmpty += c[k] > 0 ? 1 : 0;
     }
     int total, totalListed;
-    const int ex = block_exclusive_scan<16>(sum, lds, &total);
+    const int ex = block_exclusive_scan<16>(sum, lds, &total);           // (both scans on one array: each begins with a barrier)
     const int exListed = block_exclusive_scan<16>(nonEmpty, lds, &totalListed);
     unsigned long long at = carry + (unsigned long long)ex;
     int slot = carryListed + exListed;
@@ -183,11 +183,9 @@ __global__ void __launch_bounds__(1024) mesh_brick_scan_kernel(const int32_t* __
     __syncthreads();
   }
   if (threadIdx.x == 0) {
-    const unsigned long long g = carry;
     counters[0] = carryListed;
-    *generatedTotal = g;
-    totals[0] = (uint32_t)g;
-    totals[1] = (g < (unsigned long long)maxTriangles - 1ull) ? (uint32_t)g : maxTriangles - 1u;
+    *generatedTotal = carry;
+    store_triangle_totals(totals, carry, maxTriangles);
   }
 }
 

@@ -34,6 +34,7 @@
 
 #include "itm_internal.h"
 #include "mesh_types.h"
+#include "ordered_device.h"
 #include "wave_utils.h"
 
 namespace itm {
@@ -107,22 +108,8 @@ __global__ void __launch_bounds__(256) mesh_index_resolve_kernel(const uint32_t*
 
 // exclusive scan of the chunk counts (in place) by one workgroup; chunks[slotOfTotal] = their sum = nV
 __global__ void __launch_bounds__(1024) mesh_index_scan_kernel(uint32_t* __restrict__ chunks, int nChunks, int slotOfTotal) {
-  __shared__ int lds[17];
-  __shared__ uint32_t carry;
-  if (threadIdx.x == 0) carry = 0u;
-  __syncthreads();
-  for (int base = 0; base < nChunks; base += 1024) {
-    const int i = base + threadIdx.x;
-    const int v = (i < nChunks) ? (int)chunks[i] : 0;
-    int total;
-    const int ex = block_exclusive_scan<16>(v, lds, &total);
-    const uint32_t c = carry;
-    if (i < nChunks) chunks[i] = c + (uint32_t)ex;
-    __syncthreads();
-    if (threadIdx.x == 0) carry = c + (uint32_t)total;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) chunks[slotOfTotal] = carry;
+  const uint32_t nV = carry_scan<16, uint32_t>(nChunks, [&](int i) { return chunks[i]; }, [&](int i, uint32_t before) { chunks[i] = before; });
+  if (threadIdx.x == 0) chunks[slotOfTotal] = nV;
 }
 
 __global__ void __launch_bounds__(256) mesh_index_compact_kernel(const uint32_t* __restrict__ soup, uint32_t nSoup, const uint32_t* __restrict__ rep,

@@ -84,6 +84,13 @@ __device__ inline void edge_vertex(const float* p1, const float* p2, float v1, f
   out[2] = p1[2] + t * (p2[2] - p1[2]);
 }
 
+// what a mesher's scan leaves in itm_mesh::totals: [0] = the triangles generated, [1] = noTotalTriangles -- the reference's count stops at
+// noMaxTriangles - 1 (its last slot keeps being overwritten, _CPU.cpp:48-52)
+__device__ inline void store_triangle_totals(uint32_t* totals, unsigned long long generated, uint32_t maxTriangles) {
+  totals[0] = (uint32_t)generated;
+  totals[1] = (generated < (unsigned long long)maxTriangles - 1ull) ? (uint32_t)generated : maxTriangles - 1u;
+}
+
 // kTriangleCases into a translation unit's constant-memory table (a constant symbol belongs to its code object, so each mesher has
 // its own; TAG keeps their "done" flags apart): once per device, also when several host threads create meshes at the same time
 template <class TAG>

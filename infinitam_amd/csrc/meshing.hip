@@ -29,6 +29,7 @@
 #include "mc_tables.h"
 #include "shading_device.h"
 #include "mesh_types.h"
+#include "ordered_device.h"
 #include "wave_utils.h"
 
 namespace itm {
@@ -36,19 +37,7 @@ namespace itm {
 __device__ __constant__ uint64_t d_triangleCases[256];
 
 __global__ void __launch_bounds__(256) mesh_flag_kernel(const uint4* __restrict__ hash, int nEntries, uint8_t* __restrict__ flags, int32_t* __restrict__ chunkCount) {
-  __shared__ int lds[4];
-  const int chunk = blockIdx.x, tid = threadIdx.x;
-  const int slot0 = chunk * kSweepChunk + tid * 8;
-  int n = 0;
-  if (slot0 < nEntries) {
-    uint32_t w[2] = {0u, 0u};
-#pragma unroll
-    for (int k = 0; k < 8; ++k)
-      if ((int)hash[slot0 + k].w >= 0) { w[k >> 2] |= 1u << ((k & 3) * 8); ++n; }
-    *(uint2*)(flags + slot0) = make_uint2(w[0], w[1]);
-  }
-  const int sum = block_reduce_sum<4>(n, lds);
-  if (tid == 0) chunkCount[chunk] = sum;
+  flag_chunk(nEntries, flags, chunkCount, [&](int slot) { return (int)hash[slot].w >= 0; });
 }
 
 template <class VX, bool WRITE>
@@ -139,30 +128,11 @@ __global__ void __launch_bounds__(512) mesh_cells_kernel(VolumeView vol, const i
 // exclusive scan of the per-block triangle counts (in place) by one workgroup; totals[0] = sum, totals[1] = count after the cap
 __global__ void __launch_bounds__(1024) mesh_scan_kernel(int32_t* __restrict__ blockTriangles, const RenderCounters* __restrict__ lc,
                                                          uint32_t* __restrict__ totals, uint32_t maxTriangles) {
-  __shared__ int lds[17];
-  __shared__ unsigned long long carry;
-  const int n = lc->noVisibleEntries;
-  if (threadIdx.x == 0) carry = 0ull;
-  __syncthreads();
-  for (int base = 0; base < n; base += 1024) {
-    const int i = base + threadIdx.x;
-    const int v = (i < n) ? blockTriangles[i] : 0;
-    int total;
-    const int ex = block_exclusive_scan<16>(v, lds, &total);
-    const unsigned long long c = carry;
-    if (i < n) blockTriangles[i] = (int32_t)(uint32_t)(c + (unsigned long long)ex);   // < 2^32: at most 5 * 512 per block, 2^18 blocks
-    __syncthreads();
-    if (threadIdx.x == 0) carry = c + (unsigned long long)total;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    const unsigned long long g = carry;
-    totals[0] = (uint32_t)g;
-    totals[1] = (g < (unsigned long long)maxTriangles - 1ull) ? (uint32_t)g : maxTriangles - 1u;
-  }
+  // (prefixes < 2^32: at most 5 * 512 triangles per block, 2^18 blocks)
+  const unsigned long long generated = carry_scan<16, unsigned long long>(
+      lc->noVisibleEntries, [&](int i) { return blockTriangles[i]; }, [&](int i, unsigned long long before) { blockTriangles[i] = (int32_t)(uint32_t)before; });
+  if (threadIdx.x == 0) store_triangle_totals(totals, generated, maxTriangles);
 }
-
-int launch_ordered_compaction(const uint8_t* flags, const int32_t* chunkCount, int nChunks, int nEntries, int32_t* ids, int cap, RenderCounters* rc, hipStream_t st);
 
 static void free_mesh(itm_mesh* m) {
   if (!m) return;
@@ -223,7 +193,8 @@ int itm_mesh_scene(const itm_scene* s, itm_mesh* m, itm_stream stream) {
   int rc = upload_tables();
   if (rc) return rc;
   mesh_flag_kernel<<<s->numChunks, 256, 0, st>>>(s->hash, s->noTotalEntries, m->flags, m->chunkCount);
-  if ((rc = launch_ordered_compaction(m->flags, m->chunkCount, s->numChunks, s->noTotalEntries, m->slots, m->capBlocks, m->listCounters, st))) return rc;
+  if ((rc = launch_ordered_compaction(m->flags, m->chunkCount, s->numChunks, s->noTotalEntries, m->slots, m->capBlocks, &m->listCounters->rawVisibleCount,
+                                      &m->listCounters->noVisibleEntries, st))) return rc;
   const VolumeView vol = make_volume(s);
   const int grid = 256 * 4;
   rc = dispatch_voxel(s->cfg.voxelType, [&](auto vx) {

@@ -13,6 +13,7 @@
 // pixel index and lists are produced by ordered (scan-based) compaction, which yields the same
 // results without serialising.
 #include "itm_internal.h"
+#include "ordered_device.h"
 #include "shading_device.h"
 #include "wave_utils.h"
 
@@ -62,28 +63,6 @@ __global__ void __launch_bounds__(256) fwd_gather_flag_kernel(const float4* __re
   if (flag) atomicAdd(&chunkCnt[loc / kSweepChunk], 1);
 }
 
-// ordered compaction of flagged pixel indices (raster order)
-__global__ void __launch_bounds__(256) compact_pixels_kernel(const int32_t* __restrict__ flags, const int32_t* __restrict__ chunkCnt,
-                                                             int nChunks, int n, int32_t* __restrict__ outIdx, int32_t* __restrict__ totalOut) {
-  __shared__ int lds[8];
-  const int chunk = blockIdx.x, tid = threadIdx.x;
-  int b = 0, all = 0;
-  for (int j = tid; j < nChunks; j += 256) { const int c = chunkCnt[j]; all += c; if (j < chunk) b += c; }
-  const int base = block_reduce_sum<4>(b, lds);
-  if (chunk == 0) {
-    const int total = block_reduce_sum<4>(all, lds + 4);
-    if (tid == 0) *totalOut = total;
-  }
-  const int i0 = chunk * kSweepChunk + tid * 8;
-  int f[8], cnt = 0;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) { f[k] = (i0 + k < n) ? flags[i0 + k] : 0; cnt += f[k]; }
-  int tot;
-  int pos = base + block_exclusive_scan<4>(cnt, lds, &tot);
-#pragma unroll
-  for (int k = 0; k < 8; ++k) if (f[k]) outIdx[pos++] = i0 + k;
-}
-
 template <class VX, bool DENSE>
 __global__ void __launch_bounds__(256) fwd_raycast_missing_kernel(VolumeView vol, const int32_t* __restrict__ missing,
                                                                   const RenderCounters* __restrict__ rc, const float2* __restrict__ range,
@@ -121,9 +100,11 @@ int launch_forward_render(const itm_scene* s, const itm_view* v, itm_render_stat
   fwd_clear_kernel<<<blocks, 256, 0, st>>>(rs->pixScratch, rs->pixChunk, P, nChunks);
   fwd_scatter_kernel<<<blocks, 256, 0, st>>>(rs->raycast, rs->pixScratch, fp);
   fwd_gather_flag_kernel<<<blocks, 256, 0, st>>>(rs->raycast, rs->pixScratch, rs->fwdProj, rs->range, v->depth, rs->pixChunk, W, H);
-  compact_pixels_kernel<<<nChunks, 256, 0, st>>>(rs->pixScratch, rs->pixChunk, nChunks, P, rs->missing, &rs->counters->noFwdProjMissingPoints);
+  // the flagged pixel indices in raster order (ordered compaction; the list has room for every pixel)
+  int rc = launch_ordered_compaction(rs->pixScratch, rs->pixChunk, nChunks, P, rs->missing, P, (int32_t*)nullptr, &rs->counters->noFwdProjMissingPoints, st);
+  if (rc) return rc;
   const bool dense = s->cfg.indexType == ITM_INDEX_DENSE;
-  int rc = dispatch_voxel(s->cfg.voxelType, [&](auto vx) {
+  rc = dispatch_voxel(s->cfg.voxelType, [&](auto vx) {
     using VX = decltype(vx);
     if (dense) fwd_raycast_missing_kernel<VX, true><<<1024, 256, 0, st>>>(vol, rs->missing, rs->counters, rs->range, rs->fwdProj, rp);
     else fwd_raycast_missing_kernel<VX, false><<<1024, 256, 0, st>>>(vol, rs->missing, rs->counters, rs->range, rs->fwdProj, rp);
@@ -160,31 +141,16 @@ template <class VX, bool DENSE>
 __global__ void __launch_bounds__(256) pc_write_kernel(VolumeView vol, const float4* __restrict__ rays, const int32_t* __restrict__ flags,
                                                        const int32_t* __restrict__ chunkCnt, int nChunks, float4* __restrict__ locations,
                                                        float4* __restrict__ colours, RenderCounters* __restrict__ rc, RayParams p) {
-  __shared__ int lds[8];
-  const int chunk = blockIdx.x, tid = threadIdx.x;
-  const int n = p.W * p.H;
-  int b = 0, all = 0;
-  for (int j = tid; j < nChunks; j += 256) { const int c = chunkCnt[j]; all += c; if (j < chunk) b += c; }
-  const int base = block_reduce_sum<4>(b, lds);
-  if (chunk == 0) {
-    const int total = block_reduce_sum<4>(all, lds + 4);
-    if (tid == 0) rc->noTotalPoints = total;
-  }
-  const int i0 = chunk * kSweepChunk + tid * 8;
-  int f[8], cnt = 0;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) { f[k] = (i0 + k < n) ? flags[i0 + k] : 0; cnt += f[k]; }
-  int tot;
-  int pos = base + block_exclusive_scan<4>(cnt, lds, &tot);
-  for (int k = 0; k < 8; ++k) {
-    if (!f[k]) continue;
+  __shared__ int lds[kOrderedLds];
+  const int base = chunk_base(chunkCnt, nChunks, blockIdx.x, lds, [&](int total) { rc->noTotalPoints = total; });
+  const int i0 = blockIdx.x * kSweepChunk + threadIdx.x * 8;
+  ordered_scatter(base, flag_mask(flags, i0, p.W * p.H), lds, [&](int k, int pos) {
     const float4 r = rays[i0 + k];
     float4 c = colour_at<VX, DENSE>(vol, r.x, r.y, r.z);
     if (c.w > 0.0f) { c.x /= c.w; c.y /= c.w; c.z /= c.w; c.w = 1.0f; }
     colours[pos] = c;
     locations[pos] = make_float4(r.x * p.voxelSize, r.y * p.voxelSize, r.z * p.voxelSize, 1.0f);
-    ++pos;
-  }
+  });
 }
 
 int launch_point_cloud(const itm_scene* s, const itm_view* v, itm_render_state* rs, bool skip, float4* loc, float4* col, hipStream_t st) {

@@ -1,4 +1,6 @@
-// wave_utils.h -- wave64 / workgroup scan and reduce helpers for 256-thread workgroups.
+// wave_utils.h -- wave64 / workgroup scan and reduce helpers.
+// The workgroup helpers take the number of waves as NW and require blockDim.x == NW * 64, every thread calling, and `lds` of NW + 1
+// ints (block_reduce_sum: NW).  Each begins with a barrier, so back-to-back calls -- of one helper or of both -- may share one `lds`.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -46,8 +48,7 @@ __device__ inline unsigned wave_reduce_umax(unsigned v) {
   return (unsigned)__builtin_amdgcn_readlane((int)v, kWave - 1);
 }
 
-// Exclusive scan of one int per thread over a workgroup of NW waves (blockDim.x == NW*64).
-// `lds` needs NW+1 ints.  Returns the exclusive prefix; *total receives the workgroup sum.
+// Exclusive scan of one int per thread over the workgroup.  Returns the exclusive prefix; *total receives the workgroup sum.
 template <int NW>
 __device__ inline int block_exclusive_scan(int v, int* lds, int* total) {
   int inc = wave_inclusive_scan(v);
