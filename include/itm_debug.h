@@ -38,7 +38,12 @@ extern "C" {
 #define ITM_DEBUG_EXCHANGE_CORRUPT_WORD 25       /* exchanges created while it is >= 0: the self-check behind every collective sees this word of the rank's own block flipped (the check must fire); -1 = off */
 #define ITM_DEBUG_MESH_ATTR_PER_VERTEX 26        /* itm_mesh_attributes: one lane per vertex reading through the hash instead of one workgroup per block reading from LDS */
 #define ITM_DEBUG_MESH_INDEX_WEAK_HASH 27        /* itm_mesh_index: the hash cut to 8 bits (256 start slots spread over the table, the last 64 slots before its end): probe chains hundreds of slots long and the wrap-around on small meshes */
+#define ITM_DEBUG_FAIL_ALLOCATION 28             /* n > 0: the n-th allocation the library attempts from now on (device or pinned memory) fails with out-of-memory before the runtime is called, then the key clears itself; 0 = off */
 int ITM_FN(debug_set)(int key, int value);
+/* Everything the library allocates passes through one pair of functions (csrc/device_memory.h): out = {live allocations, live bytes,
+ * allocations attempted since the library was loaded}, device and pinned memory together, process-wide.  Memory handed out by
+ * itm_dev_malloc / itm_host_malloc is the host's and is not counted.  Host only: touches no GPU state. */
+int ITM_FN(debug_memory)(int64_t out[3]);
 /* A stand-in for a device-side consumer of the exchange's table (tests of itm_exchange_acquire): dst[0] = sum over `rounds` passes of a
  * position-weighted checksum of src[0 .. words), computed by ONE workgroup on `stream` -- slow on purpose, so that collectives of later
  * batches run while it reads. */

@@ -293,6 +293,7 @@ _HOST_IO_SIGS = {
     "debug_accel_probe": (C.c_int, [_P, _P, C.c_int, _P, _P, _P]),
     "debug_accel_census": (C.c_int, [_P, C.POINTER(AccelCensus), _P, _P]),
     "debug_ordered_compact": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "debug_memory": (C.c_int, [_P]),
     "swap_integrate_global_into_local": (C.c_int, [_P, _P, _P]),
     "swap_save_to_global_memory": (C.c_int, [_P, _P, _P]),
     "global_cache_get": (C.c_int, [_P, C.c_int, _P, C.POINTER(C.c_int)]),

@@ -98,20 +98,19 @@ int itm_debug_accel_probe(const itm_scene* s, const int32_t* positions, int n, i
   if (n == 0) return ITM_OK;
   hipStream_t st = as_stream(stream);
   const size_t elem = probe_float(s) ? 4 : 2;
-  int32_t* dPos = nullptr; int32_t* dCells = nullptr; void* dValues = nullptr;
-  hipError_t e = hipMalloc((void**)&dPos, (size_t)n * 12);
-  if (e == hipSuccess) e = hipMalloc((void**)&dCells, (size_t)n * ITM_ACCEL_PROBE_CELLS * 4);
-  if (e == hipSuccess) e = hipMalloc(&dValues, (size_t)n * kBlockVoxels * elem);
+  DeviceBuffer<int32_t> dPos, dCells; DeviceBuffer<void> dValues;      // (freed by their scope)
+  hipError_t e = dPos.alloc((size_t)n * 3);
+  if (e == hipSuccess) e = dCells.alloc((size_t)n * ITM_ACCEL_PROBE_CELLS);
+  if (e == hipSuccess) e = dValues.alloc((size_t)n * kBlockVoxels * elem);
   if (e == hipSuccess) e = hipMemcpyAsync(dPos, positions, (size_t)n * 12, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) {
-    if (probe_float(s)) accel_probe_kernel<false><<<n, 256, 0, st>>>(dPos, n, s->dirPtr, s->dirSlot, s->sdfMirror, s->org, dCells, (uint32_t*)dValues);
-    else accel_probe_kernel<true><<<n, 256, 0, st>>>(dPos, n, s->dirPtr, s->dirSlot, s->sdfMirror, s->org, dCells, (int16_t*)dValues);
+    if (probe_float(s)) accel_probe_kernel<false><<<n, 256, 0, st>>>(dPos, n, s->dirPtr, s->dirSlot, s->sdfMirror, s->org, dCells, (uint32_t*)dValues.get());
+    else accel_probe_kernel<true><<<n, 256, 0, st>>>(dPos, n, s->dirPtr, s->dirSlot, s->sdfMirror, s->org, dCells, (int16_t*)dValues.get());
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpyAsync(cells, dCells, (size_t)n * ITM_ACCEL_PROBE_CELLS * 4, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipMemcpyAsync(values, dValues, (size_t)n * kBlockVoxels * elem, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  (void)hipFree(dPos); (void)hipFree(dCells); (void)hipFree(dValues);
   if (e != hipSuccess) return hip_fail(e, "accel probe", __FILE__, __LINE__);
   return ITM_OK;
 }
@@ -122,10 +121,10 @@ int itm_debug_accel_census(const itm_scene* s, itm_accel_census* out, int32_t* p
   memset(out, 0, sizeof *out);
   if (pageTable) for (size_t i = 0; i < kMirrorTableCells; ++i) pageTable[i] = kPageNone;
   hipStream_t st = as_stream(stream);
-  unsigned long long* dCounts = nullptr;
+  DeviceBuffer<unsigned long long> dCounts;      // (freed by its scope)
   unsigned long long h[kCensusCounts] = {0, 0, 0};
   int32_t pageCounter = 0;
-  hipError_t e = hipMalloc((void**)&dCounts, sizeof h);
+  hipError_t e = dCounts.alloc(kCensusCounts);
   if (e == hipSuccess) e = hipMemsetAsync(dCounts, 0, sizeof h, st);
   if (e == hipSuccess && s->dirPtr) {
     accel_census_directory_kernel<<<4096, 256, 0, st>>>(s->dirPtr, s->dirSlot, kDirCells, dCounts);
@@ -143,7 +142,6 @@ int itm_debug_accel_census(const itm_scene* s, itm_accel_census* out, int32_t* p
   }
   if (e == hipSuccess) e = hipMemcpyAsync(h, dCounts, sizeof h, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  (void)hipFree(dCounts);
   if (e != hipSuccess) return hip_fail(e, "accel census", __FILE__, __LINE__);
   out->directory_cells = (int64_t)h[0]; out->slot_directory_cells = (int64_t)h[1]; out->mirror_blocks = (int64_t)h[2];
   out->page_counter = pageCounter;

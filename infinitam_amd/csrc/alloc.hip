@@ -674,9 +674,9 @@ int prepare_request_stage(itm_scene* s, const itm_view* v, itm_render_state* rs,
   rc = accel_place(s, p.invM.m, st);
   if (rc) return rc;
   p.org = s->org;
-  int2* reqCur = (int2*)s->chunkReq + (size_t)(s->frameParity & 1u) * s->numChunks;
+  int2* reqCur = (int2*)s->chunkReq.get() + (size_t)(s->frameParity & 1u) * s->numChunks;
   lazy = rs->listCoherent && !g_debug_explicit_mark;
-  ra = RequestArgs{v->depth, s->hash, rs->visibleType, s->allocKey, reqCur, s->counters, rs->range, rs->counters, g_debug_no_directory ? nullptr : s->dirSlot, s->fatalDev};
+  ra = RequestArgs{v->depth, s->hash, rs->visibleType, s->allocKey, reqCur, s->counters, rs->range, rs->counters, g_debug_no_directory ? nullptr : s->dirSlot, (int32_t*)s->fatalHost.device()};
   return ITM_OK;
 }
 
@@ -742,8 +742,8 @@ int launch_sweep_stage(itm_scene* s, const itm_view* v, itm_render_state* rs, bo
   int rc = fill_params(s, v->M_d, v->intr_d, v->w, v->h, rs->capIds, p);
   if (rc) return rc;
   const int nChunks = s->numChunks;
-  int2* reqCur = (int2*)s->chunkReq + (size_t)(s->frameParity & 1u) * nChunks;
-  int2* reqNext = (int2*)s->chunkReq + (size_t)((s->frameParity + 1u) & 1u) * nChunks;
+  int2* reqCur = (int2*)s->chunkReq.get() + (size_t)(s->frameParity & 1u) * nChunks;
+  int2* reqNext = (int2*)s->chunkReq.get() + (size_t)((s->frameParity + 1u) & 1u) * nChunks;
   const bool lazy = rs->lazyThisFrame;
   // the sweep rides in the visible-list launch unless a test hook asks for separate launches (or the ordered part of the table
   // does not end on a chunk boundary, which no configuration of the reference produces)
@@ -768,7 +768,7 @@ int launch_sweep_stage(itm_scene* s, const itm_view* v, itm_render_state* rs, bo
   if (onePass) {
     const uint32_t epoch = ++s->listEpoch;
     const SweepArgs sw{s->allocKey, reqNext, s->excessList, s->allocList, accel_writer(s), v->depth, lazy ? 1 : 0, s->chunkSweepDone, s->chunkKeptGran,
-                       s->fatalDev, fusedSweep ? g_debug_force_list_stuck - 1 : -1};
+                       (int32_t*)s->fatalHost.device(), fusedSweep ? g_debug_force_list_stuck - 1 : -1};
 #define ITM_VL(CM, LZ, SW) visible_list_kernel<CM, LZ, SW><<<nChunks, 256, 0, st>>>(rs->visibleType, s->hash, s->chunkGran, epoch, reqCur, nChunks, s->counters, rs->visibleIds, rs->capIds, rs->counters, p, sw)
     if (onlyVisible) { if (lazy) ITM_VL(false, true, false); else ITM_VL(false, false, false); }
     else if (fusedSweep) { if (lazy) ITM_VL(true, true, true); else ITM_VL(true, false, true); }
@@ -780,7 +780,7 @@ int launch_sweep_stage(itm_scene* s, const itm_view* v, itm_render_state* rs, bo
     else { if (lazy) ITM_CNT(true, true); else ITM_CNT(true, false); }
 #undef ITM_CNT
     // pass 2: the non-zero types in ascending slot order
-    if ((rc = launch_ordered_compaction(rs->visibleType, s->chunkVis, nChunks, s->noTotalEntries, rs->visibleIds, rs->capIds, &rs->counters->rawVisibleCount,
+    if ((rc = launch_ordered_compaction(rs->visibleType.get(), s->chunkVis, nChunks, s->noTotalEntries, rs->visibleIds, rs->capIds, &rs->counters->rawVisibleCount,
                                         &rs->counters->noVisibleEntries, st))) return rc;
   }
   ITM_LAUNCH_CHECK();
@@ -802,12 +802,13 @@ int launch_find_visible(const itm_scene* s, const float* M, const float* intr, i
   const int nChunks = s->numChunks;
   // The flags and per-chunk counts of a free-view query live in the RENDER STATE (allocated on first use): the scene is const
   // here and a free-view render on another stream must not touch the allocation scratch a frame may be using.
-  if (!rs->viewFlags) {
-    ITM_HIP(hipMalloc((void**)&rs->viewFlags, (size_t)nChunks * kSweepChunk));
-    ITM_HIP(hipMalloc((void**)&rs->viewChunkVis, (size_t)nChunks * 4));
+  if (!rs->viewFlags || !rs->viewChunkVis) {      // both or neither: a failed call leaves nothing that the next would launch with
+    hipError_t e = rs->viewFlags.alloc((size_t)nChunks * kSweepChunk);
+    if (e == hipSuccess) e = rs->viewChunkVis.alloc((size_t)nChunks);
+    if (e != hipSuccess) { rs->viewFlags.reset(); rs->viewChunkVis.reset(); return hip_fail(e, "free-view flags", __FILE__, __LINE__); }
   }
   freeview_flag_kernel<<<nChunks, 256, 0, st>>>(s->hash, rs->viewFlags, rs->viewChunkVis, p);
-  if ((rc = launch_ordered_compaction(rs->viewFlags, rs->viewChunkVis, nChunks, s->noTotalEntries, rs->visibleIds, rs->capIds, &rs->counters->rawVisibleCount,
+  if ((rc = launch_ordered_compaction(rs->viewFlags.get(), rs->viewChunkVis, nChunks, s->noTotalEntries, rs->visibleIds, rs->capIds, &rs->counters->rawVisibleCount,
                                       &rs->counters->noVisibleEntries, st))) return rc;
   rs->listCoherent = false;   // the list no longer mirrors entriesVisibleType
   return ITM_OK;
@@ -830,7 +831,7 @@ int cancel_ahead(itm_scene* s, itm_render_state* rs, hipStream_t st) {
   cancel_requests_kernel<<<(n / 4 + 255) / 256, 256, 0, st>>>(rs->visibleType, s->allocKey, n);
   mark_previous_kernel<<<64, 256, 0, st>>>(rs->visibleIds, rs->counters, rs->visibleType, s->noTotalEntries, rs->capIds);
   ITM_LAUNCH_CHECK();
-  ITM_HIP(hipMemsetAsync((int2*)s->chunkReq + (size_t)(s->frameParity & 1u) * s->numChunks, 0, (size_t)s->numChunks * sizeof(int2), st));
+  ITM_HIP(hipMemsetAsync((int2*)s->chunkReq.get() + (size_t)(s->frameParity & 1u) * s->numChunks, 0, (size_t)s->numChunks * sizeof(int2), st));
   rs->ahead.valid = false;
   if (s->aheadRs == rs) s->aheadRs = nullptr;
   rs->listCoherent = true;       // list == the non-zero types
@@ -866,8 +867,8 @@ int itm_debug_ordered_compact(const void* flags_host, int elemBytes, int n, int 
   // whatever the launch wrote there --, the two totals, the chunk counts
   const size_t flagBytes = ((size_t)n * elemBytes + 7) & ~(size_t)7, nList = (size_t)cap + ITM_DEBUG_ORDERED_GUARD;
   const int nChunks = (n + kSweepChunk - 1) / kSweepChunk;
-  uint8_t* buf = nullptr;
-  ITM_HIP(hipMalloc((void**)&buf, flagBytes + (nList + 2 + nChunks) * 4));
+  DeviceBuffer<uint8_t> buf;      // (freed by its scope)
+  ITM_HIP(buf.alloc(flagBytes + (nList + 2 + nChunks) * 4));
   int32_t* ids = (int32_t*)(buf + flagBytes);
   int32_t* totals = ids + nList;
   int32_t* chunkCount = totals + 2;
@@ -877,13 +878,12 @@ int itm_debug_ordered_compact(const void* flags_host, int elemBytes, int n, int 
   if (e == hipSuccess) e = hipMemsetAsync(chunkCount, 0, (size_t)nChunks * 4, st);
   if (e == hipSuccess) {
     debug_chunk_count_kernel<<<(n + 255) / 256, 256, 0, st>>>(buf, elemBytes, n, chunkCount);
-    rc = elemBytes == 1 ? launch_ordered_compaction((const uint8_t*)buf, chunkCount, nChunks, n, ids, cap, totals, totals + 1, st)
-                        : launch_ordered_compaction((const int32_t*)buf, chunkCount, nChunks, n, ids, cap, totals, totals + 1, st);
+    rc = elemBytes == 1 ? launch_ordered_compaction((const uint8_t*)buf.get(), chunkCount, nChunks, n, ids, cap, totals, totals + 1, st)
+                        : launch_ordered_compaction((const int32_t*)buf.get(), chunkCount, nChunks, n, ids, cap, totals, totals + 1, st);
   }
   if (e == hipSuccess && !rc) e = hipMemcpyAsync(ids_host, ids, nList * 4, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess && !rc) e = hipMemcpyAsync(counts, totals, 8, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess && !rc) e = hipStreamSynchronize(st);
-  (void)hipFree(buf);
   return e != hipSuccess ? hip_fail(e, "itm_debug_ordered_compact", __FILE__, __LINE__) : rc;
 }
 

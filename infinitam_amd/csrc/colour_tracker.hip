@@ -193,10 +193,10 @@ __global__ void __launch_bounds__(kGHThreads) colour_eval_kernel(const float4* _
 struct itm_colour_tracker {
   mutable std::mutex mu;
   itm::GHChannel ch;
-  void* pyramidMem = nullptr; size_t pyramidBytes = 0;
+  itm::DeviceBuffer<void> pyramidMem;
   itm::ColourPyramid P = {};
   float intr[4] = {0, 0, 0, 0};    // intr_rgb of the last prepare
-  int* totalHost = nullptr;        // pinned: noTotalPoints copied from the render state (track_camera)
+  itm::PinnedBuffer<int> totalHost;   // pinned: noTotalPoints copied from the render state (track_camera)
   int evaluations = 0;
 };
 
@@ -204,9 +204,7 @@ namespace itm {
 
 static void colour_release(itm_colour_tracker* t) {
   t->ch.release();
-  if (t->totalHost) (void)hipHostFree(t->totalHost);
-  (void)hipFree(t->pyramidMem);
-  t->totalHost = nullptr; t->pyramidMem = nullptr; t->pyramidBytes = 0;
+  t->totalHost.reset(); t->pyramidMem.reset();
   t->P = ColourPyramid{};
 }
 
@@ -215,16 +213,11 @@ static int colour_reserve(itm_colour_tracker* t, size_t pyramidBytes) {
   int rc = t->ch.reserve(kGHGroups);
   if (rc) return rc;
   if (!t->totalHost) {
-    const hipError_t e = hipHostMalloc((void**)&t->totalHost, sizeof(int), hipHostMallocMapped | hipHostMallocCoherent);
+    const hipError_t e = t->totalHost.alloc(1, hipHostMallocMapped | hipHostMallocCoherent);
     if (e != hipSuccess) { colour_release(t); return hip_fail(e, "colour tracker buffers", __FILE__, __LINE__); }
   }
-  if (t->pyramidBytes < pyramidBytes) {
-    (void)hipFree(t->pyramidMem);
-    t->pyramidMem = nullptr; t->pyramidBytes = 0;
-    const hipError_t e = hipMalloc(&t->pyramidMem, pyramidBytes);
-    if (e != hipSuccess) return hip_fail(e, "colour tracker pyramid", __FILE__, __LINE__);
-    t->pyramidBytes = pyramidBytes;
-  }
+  const hipError_t e = t->pyramidMem.reserve(pyramidBytes);
+  if (e != hipSuccess) { colour_release(t); return hip_fail(e, "colour tracker pyramid", __FILE__, __LINE__); }
   return ITM_OK;
 }
 
@@ -243,7 +236,7 @@ static int colour_prepare(itm_colour_tracker* t, const itm_view* view, int level
   }
   int rc = colour_reserve(t, bytes);
   if (rc) return rc;
-  char* base = (char*)t->pyramidMem;
+  char* base = (char*)t->pyramidMem.get();
   for (int l = 0; l < levels; ++l) {
     const size_t n = (size_t)P.w[l] * P.h[l];
     P.rgb[l] = (uchar4*)(base + off[l]);
@@ -286,11 +279,11 @@ static int colour_evaluate(itm_colour_tracker* t, int level, const float* locati
   const unsigned int seq = t->ch.begin();
   const dim3 grid(kGHGroups);
   if (np == 3) {
-    if (gh) colour_eval_kernel<3, true><<<grid, kGHThreads, 0, st>>>(loc, col, p, t->ch.recDev, seq);
-    else colour_eval_kernel<3, false><<<grid, kGHThreads, 0, st>>>(loc, col, p, t->ch.recDev, seq);
+    if (gh) colour_eval_kernel<3, true><<<grid, kGHThreads, 0, st>>>(loc, col, p, t->ch.rec.device(), seq);
+    else colour_eval_kernel<3, false><<<grid, kGHThreads, 0, st>>>(loc, col, p, t->ch.rec.device(), seq);
   } else {
-    if (gh) colour_eval_kernel<6, true><<<grid, kGHThreads, 0, st>>>(loc, col, p, t->ch.recDev, seq);
-    else colour_eval_kernel<6, false><<<grid, kGHThreads, 0, st>>>(loc, col, p, t->ch.recDev, seq);
+    if (gh) colour_eval_kernel<6, true><<<grid, kGHThreads, 0, st>>>(loc, col, p, t->ch.rec.device(), seq);
+    else colour_eval_kernel<6, false><<<grid, kGHThreads, 0, st>>>(loc, col, p, t->ch.rec.device(), seq);
   }
   ITM_LAUNCH_CHECK();
   double sums[kGHValues];
@@ -298,7 +291,7 @@ static int colour_evaluate(itm_colour_tracker* t, int level, const float* locati
   const int rc = t->ch.collect(kGHGroups, seq, st, sums, &valid);
   if (rc) return rc;
   // the launch has finished (its records are in): the count it read is in place as well
-  const int total = countDev ? *(volatile int*)t->totalHost : countHost;
+  const int total = countDev ? *(volatile int*)t->totalHost.get() : countHost;
   // F_oneLevel / G_oneLevel scaling (MY_INF is the integer 0x7f800000 converted to float)
   out->noValidPoints = valid;
   out->numPara = np;

@@ -129,8 +129,8 @@ struct itm_exchange {
   size_t words = 0;                       // per record
   ncclComm_t comm = nullptr;              // a communicator for EVERY world size, one rank included; null only behind ITM_EXCHANGE_DEVICE_COPY=1 (debug)
   static constexpr int kRing = 8;
-  int32_t* buffers[kRing] = {};           // batch records each
-  int32_t* gathered[kRing] = {};          // per slot: world x batch records, rank-major, then frame of the batch
+  itm::DeviceBuffer<int32_t> buffers[kRing];         // batch records each
+  itm::DeviceBuffer<int32_t> gathered[kRing];        // per slot: world x batch records, rank-major, then frame of the batch
   hipStream_t side = nullptr;
   hipEvent_t copied[kRing] = {}, released[kRing] = {}, consumed[kRing] = {};
   // (all guarded by m) which batch a slot's table holds (-1: none yet); the slot a consumer holds (-1: none); slots whose last holder
@@ -157,8 +157,7 @@ struct itm_exchange {
   bool stop = false;
   std::atomic<int> issuerFailed{0};
   std::string issuerMessage;
-  itm::SelfCheck* check = nullptr;        // page-locked host memory (mapped); null = self-check off
-  itm::SelfCheck* checkDev = nullptr;
+  itm::PinnedBuffer<itm::SelfCheck> check;   // page-locked host memory (mapped) and its device address; empty = self-check off
   int corruptWord = -1;                   // test hook (debug key ITM_DEBUG_EXCHANGE_CORRUPT_WORD, read when the exchange is created)
 };
 
@@ -174,13 +173,10 @@ static void free_exchange(itm_exchange* x) {
   if (x->side) (void)hipStreamSynchronize(x->side);
   if (x->comm) rccl().CommDestroy(x->comm);
   for (int b = 0; b < itm_exchange::kRing; ++b) {
-    if (x->buffers[b]) (void)hipFree(x->buffers[b]);
-    if (x->gathered[b]) (void)hipFree(x->gathered[b]);
     if (x->copied[b]) (void)hipEventDestroy(x->copied[b]);
     if (x->released[b]) (void)hipEventDestroy(x->released[b]);
     if (x->consumed[b]) (void)hipEventDestroy(x->consumed[b]);
   }
-  if (x->check) (void)hipHostFree(x->check);
   if (x->side) (void)hipStreamDestroy(x->side);
   delete x;
 }
@@ -198,8 +194,8 @@ static int issue_collective(itm_exchange* x, int b) {
   } else {
     ITM_HIP(hipMemcpyAsync(x->gathered[b], x->buffers[b], count * 4, hipMemcpyDeviceToDevice, x->side));
   }
-  if (x->checkDev) {
-    exchange_self_check_kernel<<<(unsigned)((count + 255) / 256), 256, 0, x->side>>>(x->buffers[b], x->gathered[b] + (size_t)x->rank * count, count, x->checkDev, x->corruptWord);
+  if (x->check.device()) {
+    exchange_self_check_kernel<<<(unsigned)((count + 255) / 256), 256, 0, x->side>>>(x->buffers[b], x->gathered[b] + (size_t)x->rank * count, count, x->check.device(), x->corruptWord);
     ITM_LAUNCH_CHECK();
   }
   ITM_HIP(hipEventRecord(x->released[b], x->side));
@@ -267,9 +263,9 @@ int itm_exchange_create(int world, int rank, const unsigned char id[128], int ma
   // (device-scope release: a system-scope one writes back the L2s the next frame's kernels are working in; A/B in DESIGN.md section 6)
   const unsigned evFlags = hipEventDisableTiming | (unsigned)hipEventReleaseToDevice;
   for (int b = 0; b < itm_exchange::kRing && e == hipSuccess; ++b) {
-    e = hipMalloc((void**)&x->buffers[b], batchBytes);
+    e = x->buffers[b].alloc(batchBytes / 4);
     if (e == hipSuccess) e = hipMemset(x->buffers[b], 0xFF, batchBytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&x->gathered[b], batchBytes * (size_t)world);
+    if (e == hipSuccess) e = x->gathered[b].alloc(batchBytes / 4 * (size_t)world);
     if (e == hipSuccess) e = hipMemset(x->gathered[b], 0xFF, batchBytes * (size_t)world);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&x->copied[b], evFlags);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&x->released[b], evFlags);
@@ -294,11 +290,7 @@ int itm_exchange_create(int world, int rank, const unsigned char id[128], int ma
   {
     const char* sc = getenv("ITM_EXCHANGE_SELF_CHECK");
     if (!(sc && sc[0] == '0')) {
-      void* h = nullptr; void* d = nullptr;
-      if (hipHostMalloc(&h, sizeof(SelfCheck), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess && hipHostGetDevicePointer(&d, h, 0) == hipSuccess) {
-        memset(h, 0, sizeof(SelfCheck));
-        x->check = (SelfCheck*)h; x->checkDev = (SelfCheck*)d;
-      } else { if (h) (void)hipHostFree(h); (void)hipGetLastError(); }
+      if (x->check.alloc(1, hipHostMallocMapped | hipHostMallocCoherent, true) != hipSuccess) (void)hipGetLastError();
     }
     x->corruptWord = g_debug_exchange_corrupt_word;
   }

@@ -175,29 +175,21 @@ static inline int collect_records(const GHBlockRecord* rec, size_t blocks, unsig
 // to the polling host without a kernel boundary), the device they live on and the handle's sequence numbers.  One channel per
 // handle, so two handles never share records or sequence numbers.
 struct GHChannel {
-  GHBlockRecord* rec = nullptr;      // pinned host records
-  GHBlockRecord* recDev = nullptr;   // their device address
-  size_t capacity = 0;               // in workgroups
+  PinnedBuffer<GHBlockRecord> rec;   // pinned host records (capacity in workgroups) and their device address
   int device = -1;                   // the device of the last reserve
   unsigned int seq = 0;
 
   // the current device is not the one the records were reserved on: the handle's other buffers are of no use here either
   bool moved() const { int dev = 0; (void)hipGetDevice(&dev); return dev != device; }
-  void release() {
-    if (rec) (void)hipHostFree(rec);
-    rec = nullptr; recDev = nullptr; capacity = 0;
-  }
+  void release() { rec.reset(); }
   // at least `blocks` records on the current device (grows only); on failure the channel holds none
   int reserve(size_t blocks) {
     int dev = 0;
     (void)hipGetDevice(&dev);
-    if (dev == device && capacity >= blocks) return ITM_OK;
-    release();
+    if (dev == device && rec.capacity() >= blocks) return ITM_OK;
     device = dev;
-    hipError_t e = hipHostMalloc((void**)&rec, blocks * sizeof(GHBlockRecord), hipHostMallocMapped | hipHostMallocCoherent);
-    if (e == hipSuccess) { memset(rec, 0, blocks * sizeof(GHBlockRecord)); e = hipHostGetDevicePointer((void**)&recDev, rec, 0); }
-    if (e != hipSuccess) { release(); return hip_fail(e, "tracker records", __FILE__, __LINE__); }
-    capacity = blocks;
+    const hipError_t e = rec.alloc(blocks, hipHostMallocMapped | hipHostMallocCoherent, true);
+    if (e != hipSuccess) return hip_fail(e, "tracker records", __FILE__, __LINE__);
     return ITM_OK;
   }
   unsigned int begin() { return seq = next_seq(seq); }   // the tag of the next evaluation's records

@@ -161,8 +161,9 @@ struct SlotKey {
 struct SlotKeyHash { size_t operator()(const SlotKey& k) const { return std::hash<const void*>()((const void*)k.stream) * 31u + (size_t)k.device; } };
 std::mutex g_slotMutex;
 std::unordered_map<SlotKey, LimitSlot, SlotKeyHash> g_slots;
-struct SlotBlock { int device; ImageLimits* base; int used; };
-std::vector<SlotBlock> g_slotBlocks;
+struct SlotBlock { int device; DeviceBuffer<ImageLimits> base; int used; };
+// lives as long as the process, as the slots always have (never destroyed: no runtime call after the runtime has shut down)
+std::vector<SlotBlock>& g_slotBlocks = *new std::vector<SlotBlock>();
 }  // namespace
 
 // the slot of this call and its epoch; *words / *epoch are valid on ITM_OK
@@ -175,12 +176,12 @@ static int acquire_limits(hipStream_t st, ImageLimits** words, uint32_t* epoch) 
     SlotBlock* blk = nullptr;
     for (auto& b : g_slotBlocks) if (b.device == device && b.used < kSlotsPerBlock) { blk = &b; break; }
     if (!blk) {
-      ImageLimits* base = nullptr;
-      hipError_t e = hipMalloc((void**)&base, sizeof(ImageLimits) * kSlotsPerBlock);
+      DeviceBuffer<ImageLimits> base;
+      hipError_t e = base.alloc(kSlotsPerBlock);
       if (e == hipSuccess) e = hipMemset(base, 0, sizeof(ImageLimits) * kSlotsPerBlock);
       if (e == hipSuccess) e = hipDeviceSynchronize();      // once per block: the zeros are in place before any stream uses a slot
-      if (e != hipSuccess) { if (base) (void)hipFree(base); g_slots.erase(SlotKey{device, st}); return hip_fail(e, "image-map limit slots", __FILE__, __LINE__); }
-      g_slotBlocks.push_back(SlotBlock{device, base, 0});
+      if (e != hipSuccess) { g_slots.erase(SlotKey{device, st}); return hip_fail(e, "image-map limit slots", __FILE__, __LINE__); }
+      g_slotBlocks.push_back(SlotBlock{device, std::move(base), 0});
       blk = &g_slotBlocks.back();
     }
     slot.words = blk->base + blk->used++;

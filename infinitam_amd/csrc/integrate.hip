@@ -1029,26 +1029,21 @@ int launch_integrate(itm_scene* s, const itm_view* v, itm_render_state* rs, hipS
       if (planes && g_debug_dense_classify != 1) {
         // min / max depth tiles of this frame (one small launch), then groups are classified against them
         const TileLevels tl = tile_levels(v->w, v->h);
-        if (s->depthTilesCap < (size_t)tl.total) {
-          if (s->depthTiles) (void)hipFree(s->depthTiles);
-          s->depthTiles = nullptr; s->depthTilesCap = 0;
-          if (hipMalloc((void**)&s->depthTiles, (size_t)tl.total * sizeof(float2)) == hipSuccess) s->depthTilesCap = (size_t)tl.total;
-          else (void)hipGetLastError();
-        }
+        if (s->depthTiles.reserve((size_t)tl.total) != hipSuccess) (void)hipGetLastError();
         if (s->depthTiles && make_group_classify(p, sz, of, s->depthTiles, tl, gc, wantStrips ? 4 : 1)) {
           depth_tiles_kernel<<<dim3((v->w + 63) / 64, (v->h + 63) / 64), 256, 0, st>>>(v->depth, v->w, v->h, s->depthTiles, tl);
           classify = g_debug_dense_classify == 2 ? 2 : g_debug_dense_classify == 3 ? 3 : 1;
         }
       }
       tk.reset(new KernelTimer(s, ITM_TK_INTEGRATE, st));
-#define ITM_DENSE(P2, CU, CL) integrate_dense_s_x4_kernel<P2, CU, CL><<<grid, 256, 0, st>>>((uint4*)s->vba, v->depth, p, sz[0], sz[1], sz[2], of[0], of[1], of[2], lg, cc, gc)
+#define ITM_DENSE(P2, CU, CL) integrate_dense_s_x4_kernel<P2, CU, CL><<<grid, 256, 0, st>>>((uint4*)s->vba.get(), v->depth, p, sz[0], sz[1], sz[2], of[0], of[1], of[2], lg, cc, gc)
       // the strip kernel: volumes whose rows are whole strips of 64 groups (debug key 17 keeps the launch shape of rounds 1-2)
       const bool strips = wantStrips && classify != 0;
       if (strips) {
         // 16 384 waves for the 16 384 items of a 512^3 volume: one item each, dispatched as slots free up (measured, BASELINE configs[2]:
         // 1 024 workgroups 102-110 us, 2 048: 95-104, 3 072: 93-107, 4 096: 91-105)
         const int wgs = g_debug_integrate_wgs > 0 ? g_debug_integrate_wgs : 4096;
-        integrate_dense_strip_kernel<<<wgs, 256, 0, st>>>((uint4*)s->vba, v->depth, p, sz[0], sz[1], sz[2], of[0], of[1], of[2], cc, gc);
+        integrate_dense_strip_kernel<<<wgs, 256, 0, st>>>((uint4*)s->vba.get(), v->depth, p, sz[0], sz[1], sz[2], of[0], of[1], of[2], cc, gc);
       }
       else if (columns && classify == 1) ITM_DENSE(true, 1, 1);
       else if (columns && classify == 2) ITM_DENSE(true, 1, 2);

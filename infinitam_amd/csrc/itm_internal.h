@@ -10,6 +10,7 @@
 #include "../../include/itm_debug.h"      // the library implements the test hooks; hosts never see them
 #include "itm_types.h"
 #include "accel_device.h"
+#include "device_memory.h"
 
 namespace itm {
 
@@ -60,38 +61,39 @@ struct itm_scene {
   int noTotalEntries = 0;
   int numChunks = 0;             // ceil(noTotalEntries / kSweepChunk)
   // ITMScene members, all in HBM
-  uint4* hash = nullptr;          // ITMHashEntry[noTotalEntries]
-  int32_t* excessList = nullptr;  // int[excessNum]
-  void* vba = nullptr;            // TVoxel[numVoxels]
-  int32_t* allocList = nullptr;   // int[localBlockNum]
-  itm::SceneCounters* counters = nullptr;
+  itm::DeviceBuffer<uint4> hash;          // ITMHashEntry[noTotalEntries]
+  itm::DeviceBuffer<int32_t> excessList;  // int[excessNum]
+  itm::DeviceBuffer<void> vba;            // TVoxel[numVoxels]
+  itm::DeviceBuffer<int32_t> allocList;   // int[localBlockNum]
+  itm::DeviceBuffer<itm::SceneCounters> counters;
   // allocation scratch (replaces entriesAllocType / blockCoords of the reference engines):
   // per-slot winner key of this frame's block requests, zero between frames
-  uint32_t* allocKey = nullptr;   // uint32[noTotalEntries]
-  int32_t* chunkReq = nullptr;    // int2[2][numChunks]: (requests, excess requests) per sweep chunk, double-buffered
-  int32_t* chunkVis = nullptr;    // int[numChunks]: visible slots per sweep chunk (two-pass path, FindVisibleBlocks)
-  unsigned long long* chunkGran = nullptr;  // u64[numChunks]: {epoch, visible count} granules of the one-pass visible list
-  uint32_t* chunkSweepDone = nullptr;        // u32[numChunks]: epoch stamps of chunks whose excess allocations are in place (fused sweep)
-  unsigned long long* chunkKeptGran = nullptr;      // u64 per 32 slots: {epoch, kept bits} of the excess region's shared frustum re-tests (alloc.hip)
+  itm::DeviceBuffer<uint32_t> allocKey;   // uint32[noTotalEntries]
+  itm::DeviceBuffer<int32_t> chunkReq;    // int2[2][numChunks]: (requests, excess requests) per sweep chunk, double-buffered
+  itm::DeviceBuffer<int32_t> chunkVis;    // int[numChunks]: visible slots per sweep chunk (two-pass path, FindVisibleBlocks)
+  itm::DeviceBuffer<unsigned long long> chunkGran;  // u64[numChunks]: {epoch, visible count} granules of the one-pass visible list
+  itm::DeviceBuffer<uint32_t> chunkSweepDone;        // u32[numChunks]: epoch stamps of chunks whose excess allocations are in place (fused sweep)
+  itm::DeviceBuffer<unsigned long long> chunkKeptGran;      // u64 per 32 slots: {epoch, kept bits} of the excess region's shared frustum re-tests (alloc.hip)
   uint32_t listEpoch = 0;
   // occupancy bitmap of the ordered part of the table: bit b set <=> hash[b].ptr >= -1 (an entry lives there: allocated, or swapped
   // out with its chain possibly still resident).  A clear bit
   // proves that no block hashing to bucket b is allocated (excess entries hang off occupied heads),
   // which lets the ray caster skip empty space without touching the 16-byte entries.
-  uint32_t* headBits = nullptr;   // uint32[bucketNum / 32]
+  itm::DeviceBuffer<uint32_t> headBits;   // uint32[bucketNum / 32]
   // Block directory (accel_device.h): dirPtr[cell] = voxel-block index of the block at that position or -1, cells in brick-major
   // order.  Maintained by the allocation sweep, rebuilt after uploads; an exact mirror of the table entries with ptr >= 0.
-  int32_t* dirPtr = nullptr;      // int32[kDirCells]  (512 MB)
-  int32_t* dirSlot = nullptr;     // int32[kDirCells]  (512 MB): table slot of the block at that position or -1 (request kernel)
-  void* sdfMirror = nullptr;      // the mirror's page pool: int16 / uint32 [mirrorPages * 64 * 512] (512 MB; hash scenes, accel_device.h) or nullptr;
+  itm::DeviceBuffer<int32_t> dirPtr;      // int32[kDirCells]  (512 MB)
+  itm::DeviceBuffer<int32_t> dirSlot;     // int32[kDirCells]  (512 MB): table slot of the block at that position or -1 (request kernel)
+  itm::DeviceBuffer<void> sdfMirror;      // the mirror's page pool: int16 / uint32 [mirrorPages * 64 * 512] (512 MB; hash scenes, accel_device.h) or nullptr;
                                   // its page table and page counter travel to the kernels inside `org` (AccelOrigin::mTable / mPages / mMaxPages)
+  itm::DeviceBuffer<int32_t> mirrorTable, mirrorPageCount;   // the owners of org.mTable / org.mPages (AccelOrigin is copied into kernels: raw views there)
   int mirrorPages = 0;
   // Where the two cubes lie (scene.hip, accel_place): re-placed around the camera when the view leaves them.  Invariant: the only
   // non-empty cells of dirPtr / dirSlot / sdfMirror are those of table entries with ptr >= 0 at `org` -- every path that replaces
   // the table or moves the origin empties exactly those cells first (O(allocated blocks), no 18 GB memset)
   itm::AccelOrigin org = {-itm::kDirHalf, -itm::kDirHalf, -itm::kDirHalf, -itm::kMirrorHalf, -itm::kMirrorHalf, -itm::kMirrorHalf + itm::kMirrorShift, nullptr, nullptr, 0};
   // swapping (scenes with cfg.useSwapping; swapping.hip): ITMHashSwapState per entry on the device, the ITMGlobalCache in host memory
-  uint8_t* swapStates = nullptr;           // uchar[noTotalEntries]
+  itm::DeviceBuffer<uint8_t> swapStates;           // uchar[noTotalEntries]
   struct SwapHost* swapHost = nullptr;
   unsigned tableEpoch = 0;                 // bumped whenever the table is reset or replaced (requests issued ahead are then void)
   bool countedLive = false;       // this scene is in the per-device count of live hash scenes
@@ -99,8 +101,7 @@ struct itm_scene {
   long long accelMoves = 0;       // times the cubes were re-placed (itm_scene_accel_info)
   uint32_t frameParity = 0;
   // dense integration: min / max tiles of the frame's depth image (integrate.hip), allocated on first use
-  float2* depthTiles = nullptr;
-  size_t depthTilesCap = 0;
+  itm::DeviceBuffer<float2> depthTiles;
   itm::Profiler* prof = nullptr;
   // engine calls recorded but not yet launched (pending.hip): the render state that holds them, or nullptr
   mutable itm_render_state* deferredRs = nullptr;
@@ -116,11 +117,9 @@ struct itm_scene {
   // Conditions after which the scene is no longer what the reference would hold (itm_counters::statusFlags): kernels raise them in
   // device memory AND in this word of page-locked host memory, which every entry point reads (a plain host load): the next call on
   // the scene fails with ITM_ERR_DEVICE instead of going on with a state the reference can never be in.  Cleared by ResetScene.
-  volatile int32_t* fatalHost = nullptr;   // hipHostMalloc (mapped)
-  int32_t* fatalDev = nullptr;             // the same word as the device sees it
+  itm::PinnedBuffer<volatile int32_t> fatalHost;   // mapped; device(): the same word as the device sees it
   // itm_scene_merge with this scene as destination (merge.hip): per-call scratch, kept between calls
-  void* mergeScratch = nullptr;
-  size_t mergeScratchBytes = 0;
+  itm::DeviceBuffer<void> mergeScratch;
 };
 
 struct itm_render_state {
@@ -132,21 +131,21 @@ struct itm_render_state {
   // AllocateSceneFromDepth leaves behind); lets the next allocation skip the mark-previous launch
   bool listCoherent = true;
   bool lazyThisFrame = false;
-  float2* range = nullptr;     // renderingRangeImage  Vector2f[h*w]
-  float4* raycast = nullptr;   // raycastResult        Vector4f[h*w]
-  float4* fwdProj = nullptr;   // forwardProjection    Vector4f[h*w]
-  int32_t* missing = nullptr;  // fwdProjMissingPoints int[h*w]
-  uchar4* image = nullptr;     // raycastImage         Vector4u[h*w]
-  int32_t* visibleIds = nullptr;   // int[localBlockNum]
-  uint8_t* visibleType = nullptr;  // uchar[noTotalEntries]
-  itm::RenderCounters* counters = nullptr;
+  itm::DeviceBuffer<float2> range;     // renderingRangeImage  Vector2f[h*w]
+  itm::DeviceBuffer<float4> raycast;   // raycastResult        Vector4f[h*w]
+  itm::DeviceBuffer<float4> fwdProj;   // forwardProjection    Vector4f[h*w]
+  itm::DeviceBuffer<int32_t> missing;  // fwdProjMissingPoints int[h*w]
+  itm::DeviceBuffer<uchar4> image;     // raycastImage         Vector4u[h*w]
+  itm::DeviceBuffer<int32_t> visibleIds;   // int[localBlockNum]
+  itm::DeviceBuffer<uint8_t> visibleType;  // uchar[noTotalEntries]
+  itm::DeviceBuffer<itm::RenderCounters> counters;
   // scratch
-  uint4* projBuf = nullptr;    // per visible entry: projected bounding box + z range (2 x uint4)
-  uint2* rangePartials = nullptr;  // [32][ceil(w/8)*ceil(h/8)] partial range images (LDS path)
-  int32_t* pixScratch = nullptr;  // int[h*w] (forward projection winners, ordered compaction flags)
-  int32_t* pixChunk = nullptr;    // int[ceil(h*w / kSweepChunk)]
-  uint8_t* viewFlags = nullptr;   // FindVisibleBlocks: per-slot flags (uchar[numChunks * kSweepChunk]), allocated on first use
-  int32_t* viewChunkVis = nullptr; // FindVisibleBlocks: visible slots per chunk
+  itm::DeviceBuffer<uint4> projBuf;    // per visible entry: projected bounding box + z range (2 x uint4)
+  itm::DeviceBuffer<uint2> rangePartials;  // [32][ceil(w/8)*ceil(h/8)] partial range images (LDS path)
+  itm::DeviceBuffer<int32_t> pixScratch;  // int[h*w] (forward projection winners, ordered compaction flags)
+  itm::DeviceBuffer<int32_t> pixChunk;    // int[ceil(h*w / kSweepChunk)]
+  itm::DeviceBuffer<uint8_t> viewFlags;   // FindVisibleBlocks: per-slot flags (uchar[numChunks * kSweepChunk]), allocated on first use
+  itm::DeviceBuffer<int32_t> viewChunkVis; // FindVisibleBlocks: visible slots per chunk
   // dense scenes: the expected-depth image is the constant (0.2, 3.0) of ITMVisualisationEngine_CPU<TVoxel, ITMPlainVoxelArray>::
   // CreateExpectedDepths and the rendering-block counters are its constants too; true once a launch has written them and nothing
   // else has touched them since (uploads, set_counters and loads clear it), so later frames skip the refill

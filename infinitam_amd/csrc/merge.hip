@@ -263,12 +263,8 @@ int itm_scene_merge(itm_scene* dst, const itm_scene* src, const int32_t* srcSlot
   const size_t S = (size_t)src->noTotalEntries;
   const size_t oStats = 0, oWhere = align256(kMsCount * 4), oList = oWhere + align256(S * 4), oChunk = oList + align256(S * 4),
                oSel = oChunk + align256((size_t)dst->numChunks * 8), need = oSel + align256(S);
-  if (dst->mergeScratchBytes < need) {
-    (void)hipFree(dst->mergeScratch); dst->mergeScratch = nullptr; dst->mergeScratchBytes = 0;
-    ITM_HIP(hipMalloc(&dst->mergeScratch, need));
-    dst->mergeScratchBytes = need;
-  }
-  uint8_t* base = (uint8_t*)dst->mergeScratch;
+  ITM_HIP(dst->mergeScratch.reserve(need));
+  uint8_t* base = (uint8_t*)dst->mergeScratch.get();
   int32_t* dStats = (int32_t*)(base + oStats); int32_t* where = (int32_t*)(base + oWhere); int32_t* list = (int32_t*)(base + oList);
   int2* chunkCnt = (int2*)(base + oChunk); uint8_t* sel = srcSlots_dev ? base + oSel : nullptr;
   int32_t h[kMsCount];

@@ -163,13 +163,14 @@ int itm_mesh_attributes(const itm_scene* s, itm_mesh* m, int what, itm_stream st
   hipStream_t st = as_stream(stream);
   const bool dense = s->cfg.indexType != ITM_INDEX_HASH;
   if (dense && !m->fromVolume) { m->attrCurrent |= (uint32_t)what; return ITM_OK; }   // a dense scene that itm_mesh_volume has not meshed: nothing meshed, empty attributes
-  if ((what & ITM_MESH_NORMALS) && !m->normals) {
-    const hipError_t e = hipMalloc((void**)&m->normals, (size_t)m->maxTriangles * 36);
-    if (e != hipSuccess) { m->normals = nullptr; return hip_fail(e, "mesh normals", __FILE__, __LINE__); }
+  const bool newNormals = (what & ITM_MESH_NORMALS) && !m->normals;
+  if (newNormals) {
+    const hipError_t e = m->normals.alloc((size_t)m->maxTriangles * 9);
+    if (e != hipSuccess) return hip_fail(e, "mesh normals", __FILE__, __LINE__);
   }
   if ((what & ITM_MESH_COLOURS) && !m->colours) {
-    const hipError_t e = hipMalloc((void**)&m->colours, (size_t)m->maxTriangles * 12);
-    if (e != hipSuccess) { m->colours = nullptr; return hip_fail(e, "mesh colours", __FILE__, __LINE__); }
+    const hipError_t e = m->colours.alloc((size_t)m->maxTriangles * 3);
+    if (e != hipSuccess) { if (newNormals) m->normals.reset(); return hip_fail(e, "mesh colours", __FILE__, __LINE__); }      // what this call allocated, or nothing
   }
   const VolumeView vol = make_volume(s);
   const int grid = 256 * 8;
@@ -219,18 +220,18 @@ int itm_mesh_indexed_attributes(const itm_scene* s, itm_mesh* m, int what, itm_s
   { const int rc = enter_scene(s, nullptr); if (rc) return rc; }
   hipStream_t st = as_stream(stream);
   if (m->noVertices == 0) { m->indexedAttrCurrent |= (uint32_t)what; return ITM_OK; }   // an empty index (dense scenes, nothing meshed): empty attributes
-  int rc;
-  if ((what & ITM_MESH_NORMALS) && (rc = grow_device((void**)&m->vertexNormals, &m->capVertexNormals, (size_t)m->noVertices * 3, 4, "vertex normals"))) {
+  hipError_t e;
+  if ((what & ITM_MESH_NORMALS) && (e = m->vertexNormals.reserve((size_t)m->noVertices * 3)) != hipSuccess) {
     m->indexedAttrCurrent &= ~(uint32_t)ITM_MESH_NORMALS;
-    return rc;
+    return hip_fail(e, "vertex normals", __FILE__, __LINE__);
   }
-  if ((what & ITM_MESH_COLOURS) && (rc = grow_device((void**)&m->vertexColours, &m->capVertexColours, (size_t)m->noVertices, 4, "vertex colours"))) {
+  if ((what & ITM_MESH_COLOURS) && (e = m->vertexColours.reserve((size_t)m->noVertices)) != hipSuccess) {
     m->indexedAttrCurrent &= ~(uint32_t)ITM_MESH_COLOURS;
-    return rc;
+    return hip_fail(e, "vertex colours", __FILE__, __LINE__);
   }
   const VolumeView vol = make_volume(s);
   const int grid = 256 * 8;
-  rc = dispatch_voxel(s->cfg.voxelType, [&](auto vx) {
+  const int rc = dispatch_voxel(s->cfg.voxelType, [&](auto vx) {
     using VX = decltype(vx);
     if (s->cfg.indexType != ITM_INDEX_HASH)      // the mesh of itm_mesh_volume on a dense scene: one lane per unique vertex
       mesh_attr_vertex_kernel<VX, true><<<grid, 256, 0, st>>>(vol, m->vertices, nullptr, m->noVertices, s->prm.voxelSize, (uint32_t)what, m->vertexNormals, m->vertexColours);

@@ -203,13 +203,12 @@ int launch_mesh_volume_dense(const itm_scene* s, itm_mesh* m, hipStream_t st) {
   int rc = upload_dense_tables();
   if (rc) return rc;
   if (!m->brickCount) {                                         // the per-brick buffers belong to the mesh: allocated on the first dense call
-    hipError_t e = hipMalloc((void**)&m->brickCount, (size_t)g.nBricks * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&m->brickBase, (size_t)g.nBricks * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&m->brickList, (size_t)g.nBricks * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&m->brickCounters, 16);     // [0] listed bricks (int32), [2..3] triangles generated (u64)
+    hipError_t e = m->brickCount.alloc((size_t)g.nBricks);
+    if (e == hipSuccess) e = m->brickBase.alloc((size_t)g.nBricks);
+    if (e == hipSuccess) e = m->brickList.alloc((size_t)g.nBricks);
+    if (e == hipSuccess) e = m->brickCounters.alloc(4);     // [0] listed bricks (int32), [2..3] triangles generated (u64)
     if (e != hipSuccess) {
-      (void)hipFree(m->brickCount); (void)hipFree(m->brickBase); (void)hipFree(m->brickList); (void)hipFree(m->brickCounters);
-      m->brickCount = nullptr; m->brickBase = nullptr; m->brickList = nullptr; m->brickCounters = nullptr;
+      m->brickCount.reset(); m->brickBase.reset(); m->brickList.reset(); m->brickCounters.reset();
       return hip_fail(e, "mesh brick buffers", __FILE__, __LINE__);
     }
   }

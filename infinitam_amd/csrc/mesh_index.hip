@@ -189,11 +189,17 @@ int itm_mesh_index(itm_mesh* m, itm_stream stream) {
   size_t tableSize = kIndexMinTable;
   while (tableSize < 2 * nSoup) tableSize <<= 1;                       // at least two slots per soup vertex: it cannot fill
   const int nChunks = (int)((nSoup + kIndexChunk - 1) / kIndexChunk);
-  if ((rc = grow_device((void**)&m->indexTable, &m->capIndexTable, tableSize, 4, "mesh index table"))) return rc;
-  if ((rc = grow_device((void**)&m->rep, &m->capRep, nSoup, 4, "mesh index representatives"))) return rc;
-  if ((rc = grow_device((void**)&m->faces, &m->capFaces, nSoup, 4, "mesh faces"))) return rc;
-  if ((rc = grow_device((void**)&m->indexChunks, &m->capIndexChunks, (size_t)nChunks + 1, 4, "mesh index chunk counts"))) return rc;
-  const uint32_t* soup = (const uint32_t*)m->triangles;
+  hipError_t e;
+  // an index that cannot get its memory keeps none of it: every buffer is scratch or a result of this call
+  auto fail = [&](hipError_t err, const char* what) {
+    m->indexTable.reset(); m->rep.reset(); m->faces.reset(); m->indexChunks.reset(); m->first.reset(); m->vertices.reset();
+    return hip_fail(err, what, __FILE__, __LINE__);
+  };
+  if ((e = m->indexTable.reserve(tableSize)) != hipSuccess) return fail(e, "mesh index table");
+  if ((e = m->rep.reserve(nSoup)) != hipSuccess) return fail(e, "mesh index representatives");
+  if ((e = m->faces.reserve(nSoup)) != hipSuccess) return fail(e, "mesh faces");
+  if ((e = m->indexChunks.reserve((size_t)nChunks + 1)) != hipSuccess) return fail(e, "mesh index chunk counts");
+  const uint32_t* soup = (const uint32_t*)m->triangles.get();
   const uint32_t mask = (uint32_t)(tableSize - 1);
   const int weak = g_debug_mesh_index_weak_hash;
   const int grid = 256 * 8;
@@ -206,12 +212,12 @@ int itm_mesh_index(itm_mesh* m, itm_stream stream) {
   ITM_HIP(hipMemcpyAsync(&nV, m->indexChunks + nChunks, 4, hipMemcpyDeviceToHost, st));
   ITM_HIP(hipStreamSynchronize(st));
   if (nV == 0 || nV > nSoup) return set_error(ITM_ERR_DEVICE, "mesh index: impossible vertex count");
-  if ((rc = grow_device((void**)&m->first, &m->capFirst, nV, 4, "mesh first occurrences"))) return rc;
-  if ((rc = grow_device((void**)&m->vertices, &m->capVertices, (size_t)nV * 3, 4, "mesh vertices"))) return rc;
-  mesh_index_compact_kernel<<<nChunks, 256, 0, st>>>(soup, (uint32_t)nSoup, m->rep, m->indexChunks, nV, m->first, (uint32_t*)m->vertices, m->faces);
+  if ((e = m->first.reserve(nV)) != hipSuccess) return fail(e, "mesh first occurrences");
+  if ((e = m->vertices.reserve((size_t)nV * 3)) != hipSuccess) return fail(e, "mesh vertices");
+  mesh_index_compact_kernel<<<nChunks, 256, 0, st>>>(soup, (uint32_t)nSoup, m->rep, m->indexChunks, nV, m->first, (uint32_t*)m->vertices.get(), m->faces);
   mesh_index_faces_kernel<<<grid, 256, 0, st>>>((uint32_t)nSoup, m->rep, m->faces);
   if (m->capBlocks > 0) {
-    if (!m->blockVertex) ITM_HIP(hipMalloc((void**)&m->blockVertex, ((size_t)m->capBlocks + 1) * 4));
+    if (!m->blockVertex && (e = m->blockVertex.alloc((size_t)m->capBlocks + 1)) != hipSuccess) return fail(e, "mesh block vertices");
     mesh_index_blocks_kernel<<<(m->capBlocks + 1 + 255) / 256, 256, 0, st>>>(m->listCounters, m->blockTriangles, m->totals, m->capBlocks, m->first, nV, m->blockVertex);
   }
   ITM_LAUNCH_CHECK();

@@ -11,56 +11,43 @@
 struct itm_mesh {
   const itm_scene* scene = nullptr;
   uint32_t maxTriangles = 0;
-  float* triangles = nullptr;        // ITMMesh::Triangle[maxTriangles]: 9 floats (p0, p1, p2)
-  int32_t* slots = nullptr;          // allocated slots in ascending order
-  int32_t* blockTriangles = nullptr; // per listed block: triangle count, then exclusive prefix
-  uint8_t* flags = nullptr;          // per slot: allocated?
-  int32_t* chunkCount = nullptr;
-  itm::RenderCounters* listCounters = nullptr;   // noVisibleEntries = number of listed blocks
-  uint32_t* totals = nullptr;        // [0] triangles generated, [1] noTotalTriangles (after the cap)
+  itm::DeviceBuffer<float> triangles;        // ITMMesh::Triangle[maxTriangles]: 9 floats (p0, p1, p2)
+  itm::DeviceBuffer<int32_t> slots;          // allocated slots in ascending order
+  itm::DeviceBuffer<int32_t> blockTriangles; // per listed block: triangle count, then exclusive prefix
+  itm::DeviceBuffer<uint8_t> flags;          // per slot: allocated?
+  itm::DeviceBuffer<int32_t> chunkCount;
+  itm::DeviceBuffer<itm::RenderCounters> listCounters;   // noVisibleEntries = number of listed blocks
+  itm::DeviceBuffer<uint32_t> totals;        // [0] triangles generated, [1] noTotalTriangles (after the cap)
   int capBlocks = 0;
   // itm_mesh_volume on a dense scene (mesh_dense.hip); allocated by the first such call
-  int32_t* brickCount = nullptr;     // per 8^3 brick of the array: triangle count
-  unsigned long long* brickBase = nullptr;   // per brick: triangles generated before it
-  int32_t* brickList = nullptr;      // the bricks that have triangles, ascending
-  int32_t* brickCounters = nullptr;  // [0] number of listed bricks; [2..3] triangles generated (64 bits)
+  itm::DeviceBuffer<int32_t> brickCount;     // per 8^3 brick of the array: triangle count
+  itm::DeviceBuffer<unsigned long long> brickBase;   // per brick: triangles generated before it
+  itm::DeviceBuffer<int32_t> brickList;      // the bricks that have triangles, ascending
+  itm::DeviceBuffer<int32_t> brickCounters;  // [0] number of listed bricks; [2..3] triangles generated (64 bits)
   bool fromVolume = false;           // the buffer holds the mesh itm_mesh_volume made of a dense scene; itm_mesh_scene clears it
   // vertex attributes of the triangles the last itm_mesh_scene left in the buffer (mesh_attributes.hip); allocated on first use
-  float* normals = nullptr;          // 3 floats per vertex, 3 vertices per triangle, buffer order
-  uchar4* colours = nullptr;         // one per vertex
+  itm::DeviceBuffer<float> normals;          // 3 floats per vertex, 3 vertices per triangle, buffer order
+  itm::DeviceBuffer<uchar4> colours;         // one per vertex
   uint32_t attrCurrent = 0;          // ITM_MESH_* bits computed for the buffer's present contents; itm_mesh_scene clears it
   // indexed form of the buffer's present contents (mesh_index.hip); allocated / grown by itm_mesh_index, sized from the counts
-  float* vertices = nullptr;         // 3 floats per unique vertex, in the order of first occurrence in the buffer
-  uint32_t* faces = nullptr;         // 3 vertex indices per triangle, buffer order
-  uint32_t* first = nullptr;         // per unique vertex: the smallest soup vertex index that holds its position (strictly ascending)
-  uint32_t* rep = nullptr;           // per soup vertex: first[] of its position (scratch of the build)
-  uint32_t* indexTable = nullptr;    // the hash set of representatives (scratch of the build)
-  uint32_t* indexChunks = nullptr;   // per chunk of soup vertices: unique vertices first seen there, then exclusive prefix; [capIndexChunks] = nV
-  int32_t* blockVertex = nullptr;    // per listed block: its first unique vertex (the vertices first seen in block b are [b], [b + 1])
-  size_t capRep = 0, capFaces = 0, capFirst = 0, capVertices = 0, capIndexTable = 0, capIndexChunks = 0;   // in elements
+  itm::DeviceBuffer<float> vertices;         // 3 floats per unique vertex, in the order of first occurrence in the buffer
+  itm::DeviceBuffer<uint32_t> faces;         // 3 vertex indices per triangle, buffer order
+  itm::DeviceBuffer<uint32_t> first;         // per unique vertex: the smallest soup vertex index that holds its position (strictly ascending)
+  itm::DeviceBuffer<uint32_t> rep;           // per soup vertex: first[] of its position (scratch of the build)
+  itm::DeviceBuffer<uint32_t> indexTable;    // the hash set of representatives (scratch of the build)
+  itm::DeviceBuffer<uint32_t> indexChunks;   // per chunk of soup vertices: unique vertices first seen there, then exclusive prefix, closed by nV
+  itm::DeviceBuffer<int32_t> blockVertex;    // per listed block: its first unique vertex (the vertices first seen in block b are [b], [b + 1])
   uint32_t noVertices = 0, noIndexedTriangles = 0;
   bool indexCurrent = false;         // the index describes the buffer's present contents; itm_mesh_scene clears it
   // attributes of the unique vertices (itm_mesh_indexed_attributes), independent of the soup's
-  float* vertexNormals = nullptr;    // 3 floats per unique vertex
-  uchar4* vertexColours = nullptr;   // one per unique vertex
-  size_t capVertexNormals = 0, capVertexColours = 0;
+  itm::DeviceBuffer<float> vertexNormals;    // 3 floats per unique vertex
+  itm::DeviceBuffer<uchar4> vertexColours;   // one per unique vertex
   uint32_t indexedAttrCurrent = 0;   // ITM_MESH_* bits computed for the present index; itm_mesh_scene and itm_mesh_index clear it
 };
 
 namespace itm {
 
 int launch_mesh_volume_dense(const itm_scene* s, itm_mesh* m, hipStream_t st);   // mesh_dense.hip
-
-// (re)allocates *p for `need` elements of `elem` bytes when the present capacity is smaller; the old contents are not kept
-inline int grow_device(void** p, size_t* cap, size_t need, size_t elem, const char* what) {
-  if (need <= *cap) return ITM_OK;
-  (void)hipFree(*p);
-  *p = nullptr; *cap = 0;
-  const hipError_t e = hipMalloc(p, need * elem);
-  if (e != hipSuccess) { *p = nullptr; return hip_fail(e, what, __FILE__, __LINE__); }
-  *cap = need;
-  return ITM_OK;
-}
 
 // ---- the per-cell pieces the hash mesher (meshing.hip) and the dense mesher (mesh_dense.hip) share: one copy, so the two cannot drift ----
 

@@ -136,12 +136,6 @@ __global__ void __launch_bounds__(1024) mesh_scan_kernel(int32_t* __restrict__ b
 
 static void free_mesh(itm_mesh* m) {
   if (!m) return;
-  (void)hipFree(m->triangles); (void)hipFree(m->slots); (void)hipFree(m->blockTriangles); (void)hipFree(m->flags);
-  (void)hipFree(m->chunkCount); (void)hipFree(m->listCounters); (void)hipFree(m->totals);
-  (void)hipFree(m->normals); (void)hipFree(m->colours);
-  (void)hipFree(m->brickCount); (void)hipFree(m->brickBase); (void)hipFree(m->brickList); (void)hipFree(m->brickCounters);
-  (void)hipFree(m->vertices); (void)hipFree(m->faces); (void)hipFree(m->first); (void)hipFree(m->rep); (void)hipFree(m->indexTable);
-  (void)hipFree(m->indexChunks); (void)hipFree(m->blockVertex); (void)hipFree(m->vertexNormals); (void)hipFree(m->vertexColours);
   delete m;
 }
 
@@ -162,14 +156,14 @@ int itm_mesh_create(const itm_scene* s, uint32_t maxTriangles, itm_mesh** out) {
   m->maxTriangles = maxTriangles ? maxTriangles : (uint32_t)s->cfg.localBlockNum * 32u;   // ITMMesh::noMaxTriangles (Objects/ITMMesh.h:23)
   if (m->maxTriangles < 2) { delete m; return set_error(ITM_ERR_INVALID, "a mesh needs room for at least two triangles"); }
   m->capBlocks = hash ? s->cfg.localBlockNum : 0;
-  hipError_t e = hipMalloc((void**)&m->triangles, (size_t)m->maxTriangles * 36);
-  if (e == hipSuccess) e = hipMalloc((void**)&m->totals, 8);
+  hipError_t e = m->triangles.alloc((size_t)m->maxTriangles * 9);
+  if (e == hipSuccess) e = m->totals.alloc(2);
   if (e == hipSuccess) e = hipMemset(m->totals, 0, 8);
-  if (e == hipSuccess && hash) e = hipMalloc((void**)&m->slots, (size_t)m->capBlocks * 4);
-  if (e == hipSuccess && hash) e = hipMalloc((void**)&m->blockTriangles, (size_t)m->capBlocks * 4);
-  if (e == hipSuccess && hash) e = hipMalloc((void**)&m->flags, (size_t)s->numChunks * kSweepChunk);
-  if (e == hipSuccess && hash) e = hipMalloc((void**)&m->chunkCount, (size_t)s->numChunks * 4);
-  if (e == hipSuccess && hash) e = hipMalloc((void**)&m->listCounters, sizeof(RenderCounters));
+  if (e == hipSuccess && hash) e = m->slots.alloc((size_t)m->capBlocks);
+  if (e == hipSuccess && hash) e = m->blockTriangles.alloc((size_t)m->capBlocks);
+  if (e == hipSuccess && hash) e = m->flags.alloc((size_t)s->numChunks * kSweepChunk);
+  if (e == hipSuccess && hash) e = m->chunkCount.alloc((size_t)s->numChunks);
+  if (e == hipSuccess && hash) e = m->listCounters.alloc(1);
   if (e == hipSuccess) e = hipMemset(m->triangles, 0, (size_t)m->maxTriangles * 36);   // MemoryBlock storage starts zeroed
   if (e != hipSuccess) { free_mesh(m); return hip_fail(e, "mesh buffers", __FILE__, __LINE__); }
   *out = m;
@@ -193,7 +187,7 @@ int itm_mesh_scene(const itm_scene* s, itm_mesh* m, itm_stream stream) {
   int rc = upload_tables();
   if (rc) return rc;
   mesh_flag_kernel<<<s->numChunks, 256, 0, st>>>(s->hash, s->noTotalEntries, m->flags, m->chunkCount);
-  if ((rc = launch_ordered_compaction(m->flags, m->chunkCount, s->numChunks, s->noTotalEntries, m->slots, m->capBlocks, &m->listCounters->rawVisibleCount,
+  if ((rc = launch_ordered_compaction(m->flags.get(), m->chunkCount, s->numChunks, s->noTotalEntries, m->slots, m->capBlocks, &m->listCounters->rawVisibleCount,
                                       &m->listCounters->noVisibleEntries, st))) return rc;
   const VolumeView vol = make_volume(s);
   const int grid = 256 * 4;

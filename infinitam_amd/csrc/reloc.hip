@@ -212,16 +212,16 @@ struct itm_reloc {
   std::vector<float> thresholdHost;
   std::vector<float> poses;       // 16 per row
   // device
-  std::vector<float*> pyramid;    // I_1 .. I_levels
-  float *blurTmp = nullptr, *blurOut = nullptr;      // ws x hs each
+  std::vector<itm::DeviceBuffer<float>> pyramid;     // I_1 .. I_levels
+  itm::DeviceBuffer<float> blurTmp, blurOut;         // ws x hs each
   const float* image = nullptr;   // S of the last encode: blurOut, the last pyramid level or (levels = 0, R = 0) a copy in blurOut
-  int32_t* pixel = nullptr;
-  float* threshold = nullptr;
-  uint8_t *code = nullptr, *query = nullptr;         // rowBytes each, zero beyond numFerns
-  uint8_t* db = nullptr;          // capacity x rowBytes
-  unsigned long long* partial = nullptr;             // kSearchGridCap x 8
-  uint8_t* queryPinned = nullptr; // rowBytes: a caller's code on its way to `query`
-  RelocRecord *rec = nullptr, *recDev = nullptr;     // pinned, mapped
+  itm::DeviceBuffer<int32_t> pixel;
+  itm::DeviceBuffer<float> threshold;
+  itm::DeviceBuffer<uint8_t> code, query;            // rowBytes each, zero beyond numFerns
+  itm::DeviceBuffer<uint8_t> db;  // capacity x rowBytes
+  itm::DeviceBuffer<unsigned long long> partial;     // kSearchGridCap x 8
+  itm::PinnedBuffer<uint8_t> queryPinned;            // rowBytes: a caller's code on its way to `query`
+  itm::PinnedBuffer<RelocRecord> rec;                // pinned, mapped
   hipStream_t last = nullptr;     // the stream of the last enqueueing call: the host-side calls wait for it
   bool used = false;              // `last` is one
   hipEvent_t ev[2] = {nullptr, nullptr};             // itm_debug_reloc_search_ms: around the search's launches
@@ -233,11 +233,6 @@ namespace {
 
 void reloc_free(itm_reloc* r) {
   if (!r) return;
-  for (float* p : r->pyramid) (void)hipFree(p);
-  for (void* p : {(void*)r->blurTmp, (void*)r->blurOut, (void*)r->pixel, (void*)r->threshold, (void*)r->code, (void*)r->query, (void*)r->db, (void*)r->partial})
-    if (p) (void)hipFree(p);
-  if (r->queryPinned) (void)hipHostFree(r->queryPinned);
-  if (r->rec) (void)hipHostFree(r->rec);
   for (hipEvent_t e : r->ev) if (e) (void)hipEventDestroy(e);
   delete r;
 }
@@ -275,12 +270,12 @@ int launch_scan(itm_reloc* r, const uint8_t* query, int k, hipStream_t st) {
     const long long wgs = (passes + 4 * kSearchUnroll - 1) / (4 * kSearchUnroll);
     grid = (int)(wgs < kSearchGridCap ? wgs : kSearchGridCap);
     const int pad = r->rowBytes - r->cfg.numFerns;
-#define ITM_SCAN(LL) case LL: reloc_scan_kernel<LL><<<grid, 256, 0, st>>>((const uint4*)r->db, (const uint4*)query, (uint32_t)r->count, rowVec, pad, r->partial); break;
+#define ITM_SCAN(LL) case LL: reloc_scan_kernel<LL><<<grid, 256, 0, st>>>((const uint4*)r->db.get(), (const uint4*)query, (uint32_t)r->count, rowVec, pad, r->partial); break;
     switch (logL) { ITM_SCAN(0) ITM_SCAN(1) ITM_SCAN(2) ITM_SCAN(3) ITM_SCAN(4) ITM_SCAN(5) ITM_SCAN(6) }
 #undef ITM_SCAN
     ITM_LAUNCH_CHECK();
   }
-  reloc_merge_kernel<<<1, 256, 0, st>>>(r->partial, grid * kRelocMaxK, r->cfg.numFerns, k, r->recDev);
+  reloc_merge_kernel<<<1, 256, 0, st>>>(r->partial, grid * kRelocMaxK, r->cfg.numFerns, k, r->rec.device());
   ITM_LAUNCH_CHECK();
   if (r->timing) { ITM_HIP(hipEventRecord(r->ev[1], st)); r->timed = true; }
   return ITM_OK;
@@ -347,17 +342,16 @@ int itm_reloc_create(const itm_reloc_config* cfg, const int32_t* pixel_host, con
   r->pixelHost.assign(pixel_host, pixel_host + n);
   r->thresholdHost.assign(threshold_host, threshold_host + n);
   hipError_t e = hipSuccess;
-  auto dev = [&e](auto** p, size_t bytes) { if (e == hipSuccess) e = hipMalloc((void**)p, bytes ? bytes : 1); };
-  r->pyramid.assign((size_t)cfg->levels, nullptr);
-  for (int l = 1; l <= cfg->levels; ++l) dev(&r->pyramid[(size_t)l - 1], (size_t)(cfg->w >> l) * (size_t)(cfg->h >> l) * 4);
-  dev(&r->blurTmp, (size_t)ws * hs * 4); dev(&r->blurOut, (size_t)ws * hs * 4);
-  dev(&r->pixel, (size_t)n * 4); dev(&r->threshold, (size_t)n * 4);
-  dev(&r->code, (size_t)r->rowBytes); dev(&r->query, (size_t)r->rowBytes);
-  dev(&r->db, (size_t)cfg->capacity * (size_t)r->rowBytes);
-  dev(&r->partial, (size_t)kSearchGridCap * kRelocMaxK * 8);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&r->queryPinned, (size_t)r->rowBytes, hipHostMallocDefault);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&r->rec, sizeof(RelocRecord), hipHostMallocMapped | hipHostMallocCoherent);
-  if (e == hipSuccess) { memset(r->rec, 0, sizeof(RelocRecord)); e = hipHostGetDevicePointer((void**)&r->recDev, r->rec, 0); }
+  auto dev = [&e](auto& buf, size_t elems) { if (e == hipSuccess) e = buf.alloc(elems, 1); };
+  r->pyramid.resize((size_t)cfg->levels);
+  for (int l = 1; l <= cfg->levels; ++l) dev(r->pyramid[(size_t)l - 1], (size_t)(cfg->w >> l) * (size_t)(cfg->h >> l));
+  dev(r->blurTmp, (size_t)ws * hs); dev(r->blurOut, (size_t)ws * hs);
+  dev(r->pixel, (size_t)n); dev(r->threshold, (size_t)n);
+  dev(r->code, (size_t)r->rowBytes); dev(r->query, (size_t)r->rowBytes);
+  dev(r->db, (size_t)cfg->capacity * (size_t)r->rowBytes);
+  dev(r->partial, (size_t)kSearchGridCap * kRelocMaxK);
+  if (e == hipSuccess) e = r->queryPinned.alloc((size_t)r->rowBytes, hipHostMallocDefault);
+  if (e == hipSuccess) e = r->rec.alloc(1, hipHostMallocMapped | hipHostMallocCoherent, true);
   if (e == hipSuccess) e = hipMemcpy(r->pixel, pixel_host, (size_t)n * 4, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(r->threshold, threshold_host, (size_t)n * 4, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemset(r->code, 0, (size_t)r->rowBytes);

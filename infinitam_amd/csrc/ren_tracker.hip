@@ -113,7 +113,7 @@ __global__ void __launch_bounds__(kGHThreads) ren_eval_kernel(VolumeView vol, co
 struct itm_ren_tracker {
   mutable std::mutex mu;
   itm::GHChannel ch;
-  float4* points = nullptr; size_t pointsBytes = 0;
+  itm::DeviceBuffer<float4> points;
   int w = 0, h = 0;                // size of the last prepared depth image (0: nothing prepared)
 };
 
@@ -121,8 +121,8 @@ namespace itm {
 
 static void ren_release(itm_ren_tracker* t) {
   t->ch.release();
-  (void)hipFree(t->points);
-  t->points = nullptr; t->pointsBytes = 0; t->w = t->h = 0;
+  t->points.reset();
+  t->w = t->h = 0;
 }
 
 static int ren_prepare(itm_ren_tracker* t, const itm_view* view, hipStream_t st) {
@@ -131,14 +131,8 @@ static int ren_prepare(itm_ren_tracker* t, const itm_view* view, hipStream_t st)
   if (t->ch.moved()) ren_release(t);
   int rc = t->ch.reserve(kGHGroups);
   if (rc) return rc;
-  const size_t bytes = (size_t)view->w * view->h * sizeof(float4);
-  if (t->pointsBytes < bytes) {
-    (void)hipFree(t->points);
-    t->points = nullptr; t->pointsBytes = 0;
-    const hipError_t e = hipMalloc((void**)&t->points, bytes);
-    if (e != hipSuccess) return hip_fail(e, "Ren tracker points", __FILE__, __LINE__);
-    t->pointsBytes = bytes;
-  }
+  const hipError_t e = t->points.reserve((size_t)view->w * view->h);
+  if (e != hipSuccess) { ren_release(t); return hip_fail(e, "Ren tracker points", __FILE__, __LINE__); }
   // the view's depth image may be the target of a recorded (not yet launched) engine call
   rc = flush_overlapping(view->depth, (size_t)view->w * view->h * 4, st);
   if (rc) return rc;
@@ -166,11 +160,11 @@ static int ren_evaluate(itm_ren_tracker* t, const itm_scene* s, const float invM
   const int rc = dispatch_voxel(s->cfg.voxelType, [&](auto vx) {
     using VX = decltype(vx);
     if (dense) {
-      if (gh) ren_eval_kernel<VX, true, true><<<kGHGroups, kGHThreads, 0, st>>>(vol, t->points, p, t->ch.recDev, seq);
-      else ren_eval_kernel<VX, true, false><<<kGHGroups, kGHThreads, 0, st>>>(vol, t->points, p, t->ch.recDev, seq);
+      if (gh) ren_eval_kernel<VX, true, true><<<kGHGroups, kGHThreads, 0, st>>>(vol, t->points, p, t->ch.rec.device(), seq);
+      else ren_eval_kernel<VX, true, false><<<kGHGroups, kGHThreads, 0, st>>>(vol, t->points, p, t->ch.rec.device(), seq);
     } else {
-      if (gh) ren_eval_kernel<VX, false, true><<<kGHGroups, kGHThreads, 0, st>>>(vol, t->points, p, t->ch.recDev, seq);
-      else ren_eval_kernel<VX, false, false><<<kGHGroups, kGHThreads, 0, st>>>(vol, t->points, p, t->ch.recDev, seq);
+      if (gh) ren_eval_kernel<VX, false, true><<<kGHGroups, kGHThreads, 0, st>>>(vol, t->points, p, t->ch.rec.device(), seq);
+      else ren_eval_kernel<VX, false, false><<<kGHGroups, kGHThreads, 0, st>>>(vol, t->points, p, t->ch.rec.device(), seq);
     }
     return ITM_OK;
   });

@@ -190,7 +190,7 @@ AccelWriter accel_writer(const itm_scene* s) {
 // every voxel of every page of the pool "no block here" (-32768 per short, all ones per float), no page handed out (scene creation only)
 static hipError_t mirror_clear(itm_scene* s, hipStream_t st) {
   const size_t voxels = mirror_voxels(s);
-  hipError_t e = mirror_is_float(s) ? hipMemsetAsync(s->sdfMirror, 0xff, voxels * 4, st) : hipMemsetD16Async((unsigned short*)s->sdfMirror, (unsigned short)0x8000, voxels, st);
+  hipError_t e = mirror_is_float(s) ? hipMemsetAsync(s->sdfMirror, 0xff, voxels * 4, st) : hipMemsetD16Async((unsigned short*)s->sdfMirror.get(), (unsigned short)0x8000, voxels, st);
   if (e == hipSuccess && s->org.mTable) e = hipMemsetAsync(s->org.mTable, 0xff, kMirrorTableCells * 4, st);
   if (e == hipSuccess && s->org.mPages) e = hipMemsetAsync(s->org.mPages, 0, 4, st);
   return e;
@@ -405,15 +405,10 @@ static void free_scene(itm_scene* s) {
     for (itm_render_state* r : s->renderStates) { forget_deferred(r); r->ahead.valid = false; r->scene = nullptr; }
     s->renderStates.clear();
   }
-  if (s->fatalHost) (void)hipHostFree((void*)s->fatalHost);
   if (s->countedLive && s->device >= 0 && s->device < 64) g_liveHashScenes[s->device].fetch_sub(1);
   free_swap_state(s);
   if (s->prof) { s->prof->flush(); for (hipEvent_t e : s->prof->pool) (void)hipEventDestroy(e); delete s->prof; }
-  (void)hipFree(s->hash); (void)hipFree(s->excessList); (void)hipFree(s->vba); (void)hipFree(s->allocList);
-  (void)hipFree(s->counters); (void)hipFree(s->headBits); (void)hipFree(s->allocKey); (void)hipFree(s->chunkReq); (void)hipFree(s->chunkVis); (void)hipFree(s->chunkGran); (void)hipFree(s->chunkSweepDone); (void)hipFree(s->chunkKeptGran);
-  (void)hipFree(s->dirPtr); (void)hipFree(s->dirSlot); (void)hipFree(s->sdfMirror); (void)hipFree(s->org.mTable); (void)hipFree(s->org.mPages); (void)hipFree(s->depthTiles);
-  (void)hipFree(s->mergeScratch);
-  delete s;
+  delete s;      // (its buffers free themselves)
 }
 static void free_rs(itm_render_state* r) {
   if (!r) return;
@@ -434,9 +429,6 @@ static void free_rs(itm_render_state* r) {
     }
   }
   forget_deferred(r);
-  (void)hipFree(r->range); (void)hipFree(r->raycast); (void)hipFree(r->fwdProj); (void)hipFree(r->missing);
-  (void)hipFree(r->image); (void)hipFree(r->visibleIds); (void)hipFree(r->visibleType); (void)hipFree(r->counters);
-  (void)hipFree(r->projBuf); (void)hipFree(r->rangePartials); (void)hipFree(r->pixScratch); (void)hipFree(r->pixChunk); (void)hipFree(r->viewFlags); (void)hipFree(r->viewChunkVis);
   if (r->sideStream) { (void)hipStreamSynchronize(r->sideStream); (void)hipStreamDestroy(r->sideStream); }
   if (r->listReady) (void)hipEventDestroy(r->listReady);
   if (r->projectionDone) (void)hipEventDestroy(r->projectionDone);
@@ -537,33 +529,33 @@ int itm_scene_create(const itm_scene_config* cfg_in, const itm_scene_params* prm
   s->cfg = cfg; s->prm = *prm; s->voxBytes = vb;
   (void)hipGetDevice(&s->device);
   hipError_t e = hipSuccess;
-  auto alloc = [&](void** p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes ? bytes : 16); };
+  auto alloc = [&](auto& buf, size_t n) { if (e == hipSuccess) e = buf.alloc(n); };
   if (cfg.indexType == ITM_INDEX_HASH) {
     s->noTotalEntries = cfg.bucketNum + cfg.excessNum;
     s->numChunks = (s->noTotalEntries + kSweepChunk - 1) / kSweepChunk;
     s->numVoxels = (size_t)cfg.localBlockNum * kBlockVoxels;
-    alloc((void**)&s->hash, (size_t)s->noTotalEntries * 16);
-    alloc((void**)&s->excessList, (size_t)cfg.excessNum * 4);
-    alloc((void**)&s->allocList, (size_t)cfg.localBlockNum * 4);
-    alloc((void**)&s->allocKey, (size_t)s->noTotalEntries * 4);
-    alloc((void**)&s->headBits, (size_t)(cfg.bucketNum + 31) / 32 * 4);
-    alloc((void**)&s->chunkReq, (size_t)s->numChunks * 2 * 2 * 4);
-    alloc((void**)&s->chunkVis, (size_t)s->numChunks * 4);
-    alloc((void**)&s->chunkGran, (size_t)s->numChunks * 8);
-    alloc((void**)&s->chunkSweepDone, (size_t)s->numChunks * 4);
-    alloc((void**)&s->chunkKeptGran, (size_t)s->numChunks * (kSweepChunk / 32) * 8);
+    alloc(s->hash, (size_t)s->noTotalEntries);
+    alloc(s->excessList, (size_t)cfg.excessNum);
+    alloc(s->allocList, (size_t)cfg.localBlockNum);
+    alloc(s->allocKey, (size_t)s->noTotalEntries);
+    alloc(s->headBits, (size_t)(cfg.bucketNum + 31) / 32);
+    alloc(s->chunkReq, (size_t)s->numChunks * 2 * 2);
+    alloc(s->chunkVis, (size_t)s->numChunks);
+    alloc(s->chunkGran, (size_t)s->numChunks);
+    alloc(s->chunkSweepDone, (size_t)s->numChunks);
+    alloc(s->chunkKeptGran, (size_t)s->numChunks * (kSweepChunk / 32));
   } else {
     s->numVoxels = (size_t)cfg.denseSize[0] * cfg.denseSize[1] * cfg.denseSize[2];
-    alloc((void**)&s->allocList, 4);
+    alloc(s->allocList, 1);
   }
-  alloc(&s->vba, s->numVoxels * vb + 16);
-  alloc((void**)&s->counters, sizeof(SceneCounters));
-  if (e != hipSuccess) { free_scene(s); return hip_fail(e, "hipMalloc(scene)", __FILE__, __LINE__); }
+  alloc(s->vba, s->numVoxels * vb + 16);
+  alloc(s->counters, 1);
+  if (e != hipSuccess) { free_scene(s); return hip_fail(e, "scene buffers", __FILE__, __LINE__); }
   // The directories are accelerators like the mirror below: a device without a gigabyte to spare runs without them (every look-up then
   // walks the table, as the reference does) instead of failing to create the scene
   if (cfg.indexType == ITM_INDEX_HASH && !getenv("ITM_NO_ACCELERATION_CUBES")) {
-    if (hipMalloc((void**)&s->dirPtr, kDirCells * 4) != hipSuccess) { s->dirPtr = nullptr; (void)hipGetLastError(); }
-    else if (hipMalloc((void**)&s->dirSlot, kDirCells * 4) != hipSuccess) { (void)hipFree(s->dirPtr); s->dirPtr = nullptr; s->dirSlot = nullptr; (void)hipGetLastError(); }
+    if (s->dirPtr.alloc(kDirCells) != hipSuccess) (void)hipGetLastError();
+    else if (s->dirSlot.alloc(kDirCells) != hipSuccess) { s->dirPtr.reset(); (void)hipGetLastError(); }
   }
   // The sdf mirror is an accelerator, in one of two forms (accel_device.h): DENSE -- the whole cube of 256^3 blocks, 17 GB, the faster one
   // (ray cast 38.3 us against 42.8-43.4 on BASELINE configs[1]) -- while the device has three times that to spare, i.e. for the first
@@ -596,18 +588,20 @@ int itm_scene_create(const itm_scene_config* cfg_in, const itm_scene_params* prm
     const bool paged = !off && !dense && haveInfo && freeB > 3 * (size_t)pages * pageBytes;
     auto drop = [&]() {
       (void)hipGetLastError();
-      (void)hipFree(s->sdfMirror); (void)hipFree(s->org.mTable); (void)hipFree(s->org.mPages);
-      s->sdfMirror = nullptr; s->org.mTable = nullptr; s->org.mPages = nullptr; s->org.mMaxPages = 0; s->mirrorPages = 0;
+      s->sdfMirror.reset(); s->mirrorTable.reset(); s->mirrorPageCount.reset();
+      s->org.mTable = nullptr; s->org.mPages = nullptr; s->org.mMaxPages = 0; s->mirrorPages = 0;
     };
     if (dense) {
       s->org.mMaxPages = -denseBits;
       { const int half = 1 << (denseBits - 1); s->org.mx = -half; s->org.my = -half; s->org.mz = -half + half / 2; }      // (until the first view places it)
-      if (hipMalloc(&s->sdfMirror, denseBytes) != hipSuccess || mirror_clear(s, nullptr) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) drop();
+      if (s->sdfMirror.alloc(denseBytes) != hipSuccess || mirror_clear(s, nullptr) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) drop();
     } else if (paged) {
       s->mirrorPages = pages;
       s->org.mMaxPages = pages;
-      if (hipMalloc(&s->sdfMirror, (size_t)pages * pageBytes) != hipSuccess || hipMalloc((void**)&s->org.mTable, kMirrorTableCells * 4) != hipSuccess ||
-          hipMalloc((void**)&s->org.mPages, 4) != hipSuccess || mirror_clear(s, nullptr) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) drop();
+      const bool have = s->sdfMirror.alloc((size_t)pages * pageBytes) == hipSuccess && s->mirrorTable.alloc(kMirrorTableCells) == hipSuccess &&
+                        s->mirrorPageCount.alloc(1) == hipSuccess;
+      s->org.mTable = s->mirrorTable; s->org.mPages = s->mirrorPageCount;
+      if (!have || mirror_clear(s, nullptr) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) drop();
     }
   }
   if (cfg.indexType == ITM_INDEX_HASH && s->device >= 0 && s->device < 64) { g_liveHashScenes[s->device].fetch_add(1); s->countedLive = true; }
@@ -628,11 +622,7 @@ int itm_scene_create(const itm_scene_config* cfg_in, const itm_scene_params* prm
   }
   // the host-visible status word (itm_internal.h); a device that cannot map host memory runs without it
   {
-    void* h = nullptr; void* d = nullptr;
-    if (hipHostMalloc(&h, 64, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess && hipHostGetDevicePointer(&d, h, 0) == hipSuccess) {
-      memset(h, 0, 64);
-      s->fatalHost = (volatile int32_t*)h; s->fatalDev = (int32_t*)d;
-    } else { if (h) (void)hipHostFree(h); (void)hipGetLastError(); }
+    if (s->fatalHost.alloc(16, hipHostMallocMapped | hipHostMallocCoherent, true) != hipSuccess) (void)hipGetLastError();
   }
   s->deferredFusion = deferred_fusion_default();
   *out = s;
@@ -686,7 +676,7 @@ int itm_reset_scene(itm_scene* s, itm_stream stream) {
   if (s->fatalHost && *s->fatalHost) { ITM_HIP(hipStreamSynchronize(st)); *s->fatalHost = 0; }   // nothing still running may raise it again
   const int grid = 2048;
   if (s->cfg.voxelType == ITM_VOXEL_S && (s->numVoxels % 4) == 0) {
-    reset_voxels_s_x4_kernel<<<grid, 256, 0, st>>>((uint4*)s->vba, s->numVoxels / 4);
+    reset_voxels_s_x4_kernel<<<grid, 256, 0, st>>>((uint4*)s->vba.get(), s->numVoxels / 4);
   } else {
     int rc = dispatch_voxel(s->cfg.voxelType, [&](auto vx) {
       using VX = decltype(vx);
@@ -721,22 +711,22 @@ int itm_render_state_create(const itm_scene* s, int w, int h, itm_render_state**
   r->capIds = r->hash ? s->cfg.localBlockNum : 0;
   size_t P = (size_t)w * h;
   hipError_t e = hipSuccess;
-  auto alloc = [&](void** p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes ? bytes : 16); };
-  alloc((void**)&r->range, P * 8);
-  alloc((void**)&r->raycast, P * 16);
-  alloc((void**)&r->fwdProj, P * 16);
-  alloc((void**)&r->missing, P * 4);
-  alloc((void**)&r->image, P * 4);
-  alloc((void**)&r->counters, sizeof(RenderCounters));
-  alloc((void**)&r->pixScratch, P * 4);
-  alloc((void**)&r->pixChunk, ((P + kSweepChunk - 1) / kSweepChunk) * 4 + 16);
+  auto alloc = [&](auto& buf, size_t n) { if (e == hipSuccess) e = buf.alloc(n); };
+  alloc(r->range, P);
+  alloc(r->raycast, P);
+  alloc(r->fwdProj, P);
+  alloc(r->missing, P);
+  alloc(r->image, P);
+  alloc(r->counters, 1);
+  alloc(r->pixScratch, P);
+  alloc(r->pixChunk, (P + kSweepChunk - 1) / kSweepChunk + 4);
   if (r->hash) {
-    alloc((void**)&r->visibleIds, (size_t)r->capIds * 4);
-    alloc((void**)&r->visibleType, (size_t)s->noTotalEntries);
-    alloc((void**)&r->projBuf, (size_t)r->capIds * 32);
-    if ((size_t)((w + 7) / 8) * ((h + 7) / 8) * 8 <= 150 * 1024) alloc((void**)&r->rangePartials, (size_t)64 * ((w + 7) / 8) * ((h + 7) / 8) * 8);   // room for up to 64 partial images
+    alloc(r->visibleIds, (size_t)r->capIds);
+    alloc(r->visibleType, (size_t)s->noTotalEntries);
+    alloc(r->projBuf, (size_t)r->capIds * 2);
+    if ((size_t)((w + 7) / 8) * ((h + 7) / 8) * 8 <= 150 * 1024) alloc(r->rangePartials, (size_t)64 * ((w + 7) / 8) * ((h + 7) / 8));   // room for up to 64 partial images
   }
-  if (e != hipSuccess) { free_rs(r); return hip_fail(e, "hipMalloc(render state)", __FILE__, __LINE__); }
+  if (e != hipSuccess) { free_rs(r); return hip_fail(e, "render state buffers", __FILE__, __LINE__); }
   // MemoryBlock<T> storage is zero-initialised in the reference (ORUtils/MemoryBlock.h Clear on allocate)
   e = hipMemset(r->counters, 0, sizeof(RenderCounters));
   if (e == hipSuccess) e = hipMemset(r->raycast, 0, P * 16);

@@ -30,9 +30,9 @@ struct SwapHost {
   uint8_t* hasStored = nullptr;        // bool[noTotalEntries]
   uint8_t* stored = nullptr;           // TVoxel[noTotalEntries * 512], calloc
   // transfer buffers (ITMGlobalCache::syncedVoxelBlocks / hasSyncedData / neededEntryIDs): device + pinned host
-  void* xferBlocksDev = nullptr; void* xferBlocksHost = nullptr;
-  uint8_t* xferFlagsDev = nullptr; uint8_t* xferFlagsHost = nullptr;
-  int32_t* xferIdsDev = nullptr; int32_t* xferIdsHost = nullptr;     // [cap + 1]: ids, then the count
+  itm::DeviceBuffer<void> xferBlocksDev; itm::PinnedBuffer<void> xferBlocksHost;
+  itm::DeviceBuffer<uint8_t> xferFlagsDev; itm::PinnedBuffer<uint8_t> xferFlagsHost;
+  itm::DeviceBuffer<int32_t> xferIdsDev; itm::PinnedBuffer<int32_t> xferIdsHost;     // [cap + 1]: ids, then the count
 };
 
 namespace itm {
@@ -176,27 +176,23 @@ int create_swap_state(itm_scene* s) {
   h->hasStored = (uint8_t*)calloc(N, 1);
   h->stored = (uint8_t*)calloc(N, blockBytes);
   if (!h->hasStored || !h->stored) return set_error(ITM_ERR_DEVICE, "out of host memory (global cache)");
-  hipError_t e = hipMalloc((void**)&s->swapStates, N);
+  hipError_t e = s->swapStates.alloc(N);
   if (e == hipSuccess) e = hipMemset(s->swapStates, 0, N);
-  if (e == hipSuccess) e = hipMalloc(&h->xferBlocksDev, (size_t)h->cap * blockBytes);
-  if (e == hipSuccess) e = hipMalloc((void**)&h->xferFlagsDev, (size_t)h->cap);
-  if (e == hipSuccess) e = hipMalloc((void**)&h->xferIdsDev, ((size_t)h->cap + 1) * 4);
-  if (e == hipSuccess) e = hipHostMalloc(&h->xferBlocksHost, (size_t)h->cap * blockBytes, hipHostMallocDefault);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&h->xferFlagsHost, (size_t)h->cap, hipHostMallocDefault);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&h->xferIdsHost, ((size_t)h->cap + 1) * 4, hipHostMallocDefault);
+  if (e == hipSuccess) e = h->xferBlocksDev.alloc((size_t)h->cap * blockBytes);
+  if (e == hipSuccess) e = h->xferFlagsDev.alloc((size_t)h->cap);
+  if (e == hipSuccess) e = h->xferIdsDev.alloc((size_t)h->cap + 1);
+  if (e == hipSuccess) e = h->xferBlocksHost.alloc((size_t)h->cap * blockBytes, hipHostMallocDefault);
+  if (e == hipSuccess) e = h->xferFlagsHost.alloc((size_t)h->cap, hipHostMallocDefault);
+  if (e == hipSuccess) e = h->xferIdsHost.alloc((size_t)h->cap + 1, hipHostMallocDefault);
   if (e != hipSuccess) return hip_fail(e, "swapping buffers", __FILE__, __LINE__);
   return ITM_OK;
 }
 void free_swap_state(itm_scene* s) {
-  (void)hipFree(s->swapStates); s->swapStates = nullptr;
+  s->swapStates.reset();
   SwapHost* h = s->swapHost;
   if (!h) return;
   free(h->hasStored); free(h->stored);
-  (void)hipFree(h->xferBlocksDev); (void)hipFree(h->xferFlagsDev); (void)hipFree(h->xferIdsDev);
-  if (h->xferBlocksHost) (void)hipHostFree(h->xferBlocksHost);
-  if (h->xferFlagsHost) (void)hipHostFree(h->xferFlagsHost);
-  if (h->xferIdsHost) (void)hipHostFree(h->xferIdsHost);
-  delete h;
+  delete h;      // (its transfer buffers free themselves)
   s->swapHost = nullptr;
 }
 
@@ -230,7 +226,7 @@ int itm_swap_integrate_global_into_local(itm_scene* s, itm_render_state* rs, itm
   for (int i = 0; i < n; ++i) {
     const int id = h->xferIdsHost[i];
     h->xferFlagsHost[i] = h->hasStored[id];
-    if (h->hasStored[id]) { memcpy((uint8_t*)h->xferBlocksHost + (size_t)i * blockBytes, h->stored + (size_t)id * blockBytes, blockBytes); any = true; }
+    if (h->hasStored[id]) { memcpy((uint8_t*)h->xferBlocksHost.get() + (size_t)i * blockBytes, h->stored + (size_t)id * blockBytes, blockBytes); any = true; }
   }
   ITM_HIP(hipMemcpyAsync(h->xferFlagsDev, h->xferFlagsHost, (size_t)n, hipMemcpyHostToDevice, st));
   if (any) ITM_HIP(hipMemcpyAsync(h->xferBlocksDev, h->xferBlocksHost, (size_t)n * blockBytes, hipMemcpyHostToDevice, st));
@@ -272,7 +268,7 @@ int itm_swap_save_to_global_memory(itm_scene* s, itm_render_state* rs, itm_strea
   for (int i = 0; i < n; ++i) {               // ITMGlobalCache::SetStoredData
     const int id = h->xferIdsHost[i];
     h->hasStored[id] = 1;
-    memcpy(h->stored + (size_t)id * blockBytes, (const uint8_t*)h->xferBlocksHost + (size_t)i * blockBytes, blockBytes);
+    memcpy(h->stored + (size_t)id * blockBytes, (const uint8_t*)h->xferBlocksHost.get() + (size_t)i * blockBytes, blockBytes);
   }
   return ITM_OK;          // (the occupancy bit of a head whose block left stays set: its chain may hold resident blocks)
 }

@@ -463,16 +463,18 @@ __global__ void __launch_bounds__(kGHThreads) gh_session_kernel(const unsigned l
 struct itm_tracker {
   std::mutex mu;
   itm::GHChannel ch;                      // pinned host records of every evaluation (a session's coarse levels included)
-  std::vector<float*> pyramid; std::vector<size_t> pyramidBytes;
-  std::vector<float*> weightPyramid; std::vector<size_t> weightPyramidBytes;   // weighted ICP: the sigmaZ pyramid (allocated on first use)
+  std::vector<itm::DeviceBuffer<float>> pyramid;
+  std::vector<itm::DeviceBuffer<float>> weightPyramid;   // weighted ICP: the sigmaZ pyramid (allocated on first use)
   int sessionUsable = -1;                 // -1 not probed yet, 0 launch per evaluation, 1 resident evaluation kernel
   int sessionFallbacks = 0;
   int debugEvaluations = 0;
   // evaluation session (gh_session_kernel)
-  itm::GHBlockRecord* devRec = nullptr;   // device memory: the workgroups' records of a session's fine levels (kGHGroups)
-  unsigned long long* cmd = nullptr; unsigned long long* cmdDev = nullptr;   // command granules (BAR-mapped device memory or pinned host memory) + their device address
-  itm::GHResult* res = nullptr; itm::GHResult* resDev = nullptr;     // pinned result + its device address
-  unsigned long long* devCmd = nullptr;   // device memory: republished command granules
+  itm::DeviceBuffer<itm::GHBlockRecord> devRec;   // device memory: the workgroups' records of a session's fine levels (kGHGroups)
+  itm::DeviceBuffer<unsigned long long> cmdBar;      // command granules as BAR-mapped device memory, or
+  itm::PinnedBuffer<unsigned long long> cmdPinned;   // as pinned host memory: one of the two is in use (cmdDirect), and
+  unsigned long long* cmd = nullptr; unsigned long long* cmdDev = nullptr;   // the host's and the device's address of that one
+  itm::PinnedBuffer<itm::GHResult> res;              // pinned result + its device address
+  itm::DeviceBuffer<unsigned long long> devCmd;   // device memory: republished command granules
   unsigned int session = 0;
   bool sessionOpen = false;
   bool cmdDirect = false;        // the command block is device memory the host writes through the BAR
@@ -492,22 +494,19 @@ static void tracker_release(itm_tracker* t) {
     t->sessionOpen = false;
   }
   t->ch.release();
-  (void)hipFree(t->devRec);
-  if (t->cmd) { if (t->cmdDirect) (void)hipFree(t->cmd); else (void)hipHostFree(t->cmd); }
-  if (t->res) (void)hipHostFree(t->res);
-  (void)hipFree(t->devCmd);
-  t->devRec = nullptr; t->cmd = nullptr; t->cmdDev = nullptr; t->res = nullptr; t->resDev = nullptr; t->devCmd = nullptr;
+  t->devRec.reset(); t->cmdBar.reset(); t->cmdPinned.reset(); t->res.reset(); t->devCmd.reset();
+  t->cmd = nullptr; t->cmdDev = nullptr;
   t->sessionOpen = false;
-  for (float* q : t->pyramid) (void)hipFree(q);
-  t->pyramid.clear(); t->pyramidBytes.clear();
-  for (float* q : t->weightPyramid) (void)hipFree(q);
-  t->weightPyramid.clear(); t->weightPyramidBytes.clear();
+  t->pyramid.clear();
+  t->weightPyramid.clear();
 }
 
 // records for `blocks` workgroups on the current device
 static int tracker_reserve(itm_tracker* t, size_t blocks) {
   if (t->ch.moved()) tracker_release(t);           // buffers of another device (incl. the pyramid and the session's) are of no use here
-  return t->ch.reserve(blocks);
+  const int rc = t->ch.reserve(blocks);
+  if (rc) tracker_release(t);                      // a handle that could not get its memory keeps none of it
+  return rc;
 }
 
 static GHParams gh_params(int w, int h, const float* viewIntr, int sceneW, int sceneH, const float* sceneIntr, const float* approxInvPose,
@@ -555,12 +554,12 @@ static int compute_g_and_h(itm_tracker* trk, const float* depth, int w, int h, c
   const int np = (iterationType == ITM_TRACKER_ITERATION_BOTH) ? 6 : 3;
   const unsigned int seq = trk->ch.begin();
   if (weight) {          // weighted ICP (ITMWeightedICPTracker_CPU::ComputeGandH): the same tiles, grid and order of the additions
-    if (iterationType == 1) gh_partial_kernel<1, true><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, trk->ch.recDev, seq);
-    else if (iterationType == 2) gh_partial_kernel<2, true><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, trk->ch.recDev, seq);
-    else gh_partial_kernel<3, true><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, trk->ch.recDev, seq);
-  } else if (iterationType == 1) gh_partial_kernel<1><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, trk->ch.recDev, seq);
-  else if (iterationType == 2) gh_partial_kernel<2><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, trk->ch.recDev, seq);
-  else gh_partial_kernel<3><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, trk->ch.recDev, seq);
+    if (iterationType == 1) gh_partial_kernel<1, true><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, trk->ch.rec.device(), seq);
+    else if (iterationType == 2) gh_partial_kernel<2, true><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, trk->ch.rec.device(), seq);
+    else gh_partial_kernel<3, true><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, trk->ch.rec.device(), seq);
+  } else if (iterationType == 1) gh_partial_kernel<1><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, trk->ch.rec.device(), seq);
+  else if (iterationType == 2) gh_partial_kernel<2><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, trk->ch.rec.device(), seq);
+  else gh_partial_kernel<3><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, trk->ch.rec.device(), seq);
   ITM_LAUNCH_CHECK();
   // Wait for every workgroup's tagged record and add them in block order (fixed order => deterministic, in double; bounded wait)
   double sums[kGHValues];
@@ -590,29 +589,24 @@ static int session_reserve(itm_tracker* t) {
   int dev = 0, largeBar = 0;
   (void)hipGetDevice(&dev);
   if (!g_debug_tracker_host_command && hipDeviceGetAttribute(&largeBar, hipDeviceAttributeIsLargeBar, dev) == hipSuccess && largeBar &&
-      hipExtMallocWithFlags((void**)&t->cmd, cmdBytes, hipDeviceMallocFinegrained) == hipSuccess) {
+      t->cmdBar.alloc(64, 16, hipDeviceMallocFinegrained) == hipSuccess) {
     t->cmdDirect = true;
-    t->cmdDev = t->cmd;
+    t->cmd = t->cmdDev = t->cmdBar;
     e = hipMemset(t->cmd, 0, cmdBytes);
   } else {
     (void)hipGetLastError();
     t->cmdDirect = false;
-    e = hipHostMalloc((void**)&t->cmd, cmdBytes, hipHostMallocMapped | hipHostMallocCoherent);
-    if (e == hipSuccess) { memset(t->cmd, 0, cmdBytes); e = hipHostGetDevicePointer((void**)&t->cmdDev, t->cmd, 0); }
+    e = t->cmdPinned.alloc(64, hipHostMallocMapped | hipHostMallocCoherent, true);
+    t->cmd = t->cmdPinned; t->cmdDev = t->cmdPinned.device();
   }
-  if (e == hipSuccess) e = hipHostMalloc((void**)&t->res, sizeof(GHResult), hipHostMallocMapped | hipHostMallocCoherent);
-  if (e == hipSuccess) { memset(t->res, 0, sizeof(GHResult)); e = hipHostGetDevicePointer((void**)&t->resDev, t->res, 0); }
-  if (e == hipSuccess) e = hipMalloc((void**)&t->devCmd, cmdBytes);
+  if (e == hipSuccess) e = t->res.alloc(1, hipHostMallocMapped | hipHostMallocCoherent, true);
+  if (e == hipSuccess) e = t->devCmd.alloc(64);
   if (e == hipSuccess) e = hipMemset(t->devCmd, 0, cmdBytes);
-  if (e == hipSuccess) e = hipMalloc((void**)&t->devRec, kGHGroups * sizeof(GHBlockRecord));
+  if (e == hipSuccess) e = t->devRec.alloc(kGHGroups);
   if (e == hipSuccess) e = hipMemset(t->devRec, 0, kGHGroups * sizeof(GHBlockRecord));        // tag 0: no record
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e != hipSuccess) {
-    if (t->cmd) { if (t->cmdDirect) (void)hipFree(t->cmd); else (void)hipHostFree(t->cmd); }
-    if (t->res) (void)hipHostFree(t->res);
-    (void)hipFree(t->devCmd);
-    (void)hipFree(t->devRec);
-    t->cmd = nullptr; t->res = nullptr; t->devCmd = nullptr; t->devRec = nullptr;
+    tracker_release(t);
     return hip_fail(e, "tracker session buffers", __FILE__, __LINE__);
   }
   return ITM_OK;
@@ -620,7 +614,7 @@ static int session_reserve(itm_tracker* t) {
 
 static int session_launch(itm_tracker* t, unsigned int firstSeq, hipStream_t st) {
   ++t->session;
-  gh_session_kernel<<<kGHGroups, kGHThreads, 0, st>>>(t->cmdDev, t->devCmd, t->devRec, t->resDev, t->ch.recDev, t->session, firstSeq, t->cmdDirect ? 1 : 0);
+  gh_session_kernel<<<kGHGroups, kGHThreads, 0, st>>>(t->cmdDev, t->devCmd, t->devRec, t->res.device(), t->ch.rec.device(), t->session, firstSeq, t->cmdDirect ? 1 : 0);
   ITM_LAUNCH_CHECK();
   t->sessionOpen = true;
   return ITM_OK;
@@ -735,21 +729,16 @@ struct DepthLevel { const float* depth; int w, h; float intr[4]; };
 
 // FilterSubsampleWithHoles levels 1 .. levels-1 of `src` (w x h) into `bufs` (grown as needed; bufs[0] is not used): one launch of
 // pyramid_kernel for up to four coarser levels, a launch per level otherwise.  lv[i]: level i (lv[0] = src).
-static int subsample_pyramid(const float* src, int w, int h, int levels, std::vector<float*>& bufs, std::vector<size_t>& bufBytes,
+static int subsample_pyramid(const float* src, int w, int h, int levels, std::vector<DeviceBuffer<float>>& bufs,
                              std::vector<const float*>& lv, hipStream_t st) {
   lv.assign(levels, src);
-  if ((int)bufs.size() < levels) { bufs.resize(levels, nullptr); bufBytes.resize(levels, 0); }
+  if ((int)bufs.size() < levels) bufs.resize(levels);
   std::vector<int> lw(levels), lh(levels);
   lw[0] = w; lh[0] = h;
   for (int i = 1; i < levels; ++i) {
     lw[i] = lw[i - 1] / 2; lh[i] = lh[i - 1] / 2;
     if (lw[i] < 1 || lh[i] < 1) return set_error(ITM_ERR_INVALID, "image too small for the hierarchy");
-    const size_t bytes = (size_t)lw[i] * lh[i] * 4;
-    if (bufBytes[i] < bytes) {
-      (void)hipFree(bufs[i]); bufs[i] = nullptr; bufBytes[i] = 0;
-      ITM_HIP(hipMalloc((void**)&bufs[i], bytes));
-      bufBytes[i] = bytes;
-    }
+    ITM_HIP(bufs[i].reserve((size_t)lw[i] * lh[i]));
     lv[i] = bufs[i];
   }
   if (levels >= 2 && levels <= 5 && !g_debug_tracker_launch_per_evaluation) {
@@ -769,7 +758,7 @@ static int subsample_pyramid(const float* src, int w, int h, int levels, std::ve
 static int build_pyramid(itm_tracker* trk, const itm_view* view, int levels, std::vector<DepthLevel>& out, hipStream_t st) {
   out.resize(levels);
   std::vector<const float*> lv;
-  const int rc = subsample_pyramid(view->depth, view->w, view->h, levels, trk->pyramid, trk->pyramidBytes, lv, st);
+  const int rc = subsample_pyramid(view->depth, view->w, view->h, levels, trk->pyramid, lv, st);
   if (rc) return rc;
   for (int i = 0; i < levels; ++i) {
     out[i].depth = lv[i];
@@ -792,7 +781,7 @@ static int track_camera(itm_tracker* trk, const itm_tracker_config* cfg, const i
   if (rc) return rc;
   std::vector<DepthLevel> pyr;
   ITM_TT(const auto tc0 = std::chrono::steady_clock::now();)
-  if ((rc = build_pyramid(trk, view, levels, pyr, st))) return rc;
+  if ((rc = build_pyramid(trk, view, levels, pyr, st))) { if (rc == ITM_ERR_DEVICE) tracker_release(trk); return rc; }
   ITM_TT(const auto tc1 = std::chrono::steady_clock::now();)
   auto per_launch = [&](int level, int mode, const float invPose[16], float distThresh, itm_tracker_gh* e) {
     return compute_g_and_h(trk, pyr[level].depth, pyr[level].w, pyr[level].h, pyr[level].intr, pointsMap, normalsMap, view->w, view->h,
@@ -846,8 +835,8 @@ static int weighted_track_camera(itm_tracker* trk, const itm_tracker_config* cfg
   if (rc) return rc;
   std::vector<DepthLevel> pyr;
   std::vector<const float*> weights;
-  if ((rc = build_pyramid(trk, view, levels, pyr, st))) return rc;
-  if ((rc = subsample_pyramid(sigmaZ, view->w, view->h, levels, trk->weightPyramid, trk->weightPyramidBytes, weights, st))) return rc;
+  if ((rc = build_pyramid(trk, view, levels, pyr, st))) { if (rc == ITM_ERR_DEVICE) tracker_release(trk); return rc; }
+  if ((rc = subsample_pyramid(sigmaZ, view->w, view->h, levels, trk->weightPyramid, weights, st))) { if (rc == ITM_ERR_DEVICE) tracker_release(trk); return rc; }
   return wicp_track(cfg, view->M_d, M_d_out, [&](int level, int mode, const float invPose[16], float distThresh, itm_tracker_gh* e) {
     return compute_g_and_h(trk, pyr[level].depth, pyr[level].w, pyr[level].h, pyr[level].intr, pointsMap, normalsMap, view->w, view->h,
                            pyr[0].intr, invPose, scenePose, distThresh, mode, e, st, weights[level]);

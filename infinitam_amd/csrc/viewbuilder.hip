@@ -201,8 +201,8 @@ struct itm_depth_stager {
   int w = 0, h = 0, slots = 0;
   int device = 0;
   hipStream_t copy = nullptr;
-  std::vector<int16_t*> buf;
-  std::vector<float*> depth;                  // per slot, once a conversion has been set: the float depth image of the slot's frame
+  std::vector<itm::DeviceBuffer<int16_t>> buf;
+  std::vector<itm::DeviceBuffer<float>> depth;                // per slot, once a conversion has been set: the float depth image of the slot's frame
   int calibType = -1; float c0 = 0, c1 = 0, fx = 0;
   std::vector<hipEvent_t> uploaded, consumed;
   // one thread may upload while another acquires / releases (a producer beside the frame loop): the counters both sides read are atomic
@@ -216,8 +216,6 @@ static void free_stager(itm_depth_stager* g) {
   if (g->copy) { (void)hipStreamSynchronize(g->copy); (void)hipStreamDestroy(g->copy); }
   for (auto e : g->uploaded) if (e) (void)hipEventDestroy(e);
   for (auto e : g->consumed) if (e) (void)hipEventDestroy(e);
-  for (auto b : g->buf) if (b) (void)hipFree(b);
-  for (auto b : g->depth) if (b) (void)hipFree(b);
   delete g;
 }
 
@@ -226,14 +224,14 @@ int itm_depth_stager_create(int w, int h, int slots, itm_depth_stager** out) {
   itm_depth_stager* g = new (std::nothrow) itm_depth_stager();
   if (!g) return set_error(ITM_ERR_DEVICE, "out of host memory");
   g->w = w; g->h = h; g->slots = slots;
-  g->buf.assign(slots, nullptr); g->uploaded.assign(slots, nullptr); g->consumed.assign(slots, nullptr);
+  g->buf.resize(slots); g->uploaded.assign(slots, nullptr); g->consumed.assign(slots, nullptr);
   g->consumedRecorded.reset(new (std::nothrow) std::atomic<char>[slots]);
   if (!g->consumedRecorded) { delete g; return set_error(ITM_ERR_DEVICE, "out of host memory"); }
   for (int i = 0; i < slots; ++i) g->consumedRecorded[i].store(0);
   hipError_t e = hipGetDevice(&g->device);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&g->copy, hipStreamNonBlocking);
   for (int i = 0; i < slots && e == hipSuccess; ++i) {
-    e = hipMalloc((void**)&g->buf[i], (size_t)w * h * sizeof(int16_t));
+    e = g->buf[i].alloc((size_t)w * h);
     // DEVICE-scope release: producer and consumer of a slot are streams of this device.  The default (system-scope) release of
     // hipEventRecord writes back and invalidates the L2s -- recorded on the FRAME's stream once per frame (`consumed`), that made every
     // frame's kernels start on cold caches (the exchange found the same, exchange.hip)
@@ -279,8 +277,8 @@ int itm_depth_stager_upload(itm_depth_stager* g, const int16_t* host) {
   void* mapped = nullptr;
   if (hipHostGetDevicePointer(&mapped, (void*)host, 0) == hipSuccess && mapped && (bytes % 16) == 0 && ((uintptr_t)mapped % 16) == 0) {
     const size_t n = bytes / 16;
-    if (g->calibType >= 0) stage_copy_kernel<true><<<kStageWorkgroups, 256, 0, g->copy>>>((const uint4*)mapped, (uint4*)g->buf[b], n, (float4*)g->depth[b], g->calibType, g->c0, g->c1, g->fx);
-    else stage_copy_kernel<false><<<kStageWorkgroups, 256, 0, g->copy>>>((const uint4*)mapped, (uint4*)g->buf[b], n, nullptr, 0, 0.0f, 0.0f, 0.0f);
+    if (g->calibType >= 0) stage_copy_kernel<true><<<kStageWorkgroups, 256, 0, g->copy>>>((const uint4*)mapped, (uint4*)g->buf[b].get(), n, (float4*)g->depth[b].get(), g->calibType, g->c0, g->c1, g->fx);
+    else stage_copy_kernel<false><<<kStageWorkgroups, 256, 0, g->copy>>>((const uint4*)mapped, (uint4*)g->buf[b].get(), n, nullptr, 0, 0.0f, 0.0f, 0.0f);
     ITM_LAUNCH_CHECK();
   } else {
     (void)hipGetLastError();                  // pageable memory: the runtime's staged copy
@@ -322,15 +320,12 @@ int itm_depth_stager_set_conversion(itm_depth_stager* g, int calibType, float c0
   if (g->tail.load(std::memory_order_acquire) != g->head.load(std::memory_order_acquire)) return set_error(ITM_ERR_INVALID, "frames are waiting in the ring");
   if (g->depth.empty()) {
     // all slots or none: a partly filled vector would pass for "allocated" on a retry, and the converting copy would write through a null slot
-    std::vector<float*> imgs((size_t)g->slots, nullptr);
+    std::vector<DeviceBuffer<float>> imgs((size_t)g->slots);
     for (int i = 0; i < g->slots; ++i) {
-      const hipError_t e = hipMalloc((void**)&imgs[i], (size_t)g->w * g->h * sizeof(float));
-      if (e != hipSuccess) {
-        for (float* q : imgs) if (q) (void)hipFree(q);
-        return hip_fail(e, "hipMalloc(stager float images)", __FILE__, __LINE__);
-      }
+      const hipError_t e = imgs[i].alloc((size_t)g->w * g->h);
+      if (e != hipSuccess) return hip_fail(e, "stager float images", __FILE__, __LINE__);
     }
-    g->depth = imgs;
+    g->depth = std::move(imgs);
   }
   g->calibType = calibType; g->c0 = c0; g->c1 = c1; g->fx = fx;
   return ITM_OK;

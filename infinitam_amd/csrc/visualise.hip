@@ -663,7 +663,15 @@ int itm_debug_set(int key, int value) {
   if (key == ITM_DEBUG_EXCHANGE_CORRUPT_WORD) { g_debug_exchange_corrupt_word = value; return ITM_OK; }
   if (key == ITM_DEBUG_MESH_ATTR_PER_VERTEX) { g_debug_mesh_attr_per_vertex = value; return ITM_OK; }
   if (key == ITM_DEBUG_MESH_INDEX_WEAK_HASH) { g_debug_mesh_index_weak_hash = value; return ITM_OK; }
+  if (key == ITM_DEBUG_FAIL_ALLOCATION) { memory_stats().failAt.store(value > 0 ? value : 0); return ITM_OK; }
   return set_error(ITM_ERR_INVALID, "unknown debug key");
+}
+
+int itm_debug_memory(int64_t out[3]) {
+  if (!out) return set_error(ITM_ERR_INVALID, "null argument");
+  const MemoryStats& m = memory_stats();
+  out[0] = m.live.load(); out[1] = m.liveBytes.load(); out[2] = m.attempted.load();
+  return ITM_OK;
 }
 
 int itm_find_surface(const itm_scene* s, const float M[16], const float intr[4], itm_render_state* rs, itm_stream stream) {

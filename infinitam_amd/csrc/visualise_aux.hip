@@ -101,7 +101,7 @@ int launch_forward_render(const itm_scene* s, const itm_view* v, itm_render_stat
   fwd_scatter_kernel<<<blocks, 256, 0, st>>>(rs->raycast, rs->pixScratch, fp);
   fwd_gather_flag_kernel<<<blocks, 256, 0, st>>>(rs->raycast, rs->pixScratch, rs->fwdProj, rs->range, v->depth, rs->pixChunk, W, H);
   // the flagged pixel indices in raster order (ordered compaction; the list has room for every pixel)
-  int rc = launch_ordered_compaction(rs->pixScratch, rs->pixChunk, nChunks, P, rs->missing, P, (int32_t*)nullptr, &rs->counters->noFwdProjMissingPoints, st);
+  int rc = launch_ordered_compaction(rs->pixScratch.get(), rs->pixChunk, nChunks, P, rs->missing, P, (int32_t*)nullptr, &rs->counters->noFwdProjMissingPoints, st);
   if (rc) return rc;
   const bool dense = s->cfg.indexType == ITM_INDEX_DENSE;
   rc = dispatch_voxel(s->cfg.voxelType, [&](auto vx) {
