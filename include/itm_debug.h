@@ -39,6 +39,7 @@ extern "C" {
 #define ITM_DEBUG_MESH_ATTR_PER_VERTEX 26        /* itm_mesh_attributes: one lane per vertex reading through the hash instead of one workgroup per block reading from LDS */
 #define ITM_DEBUG_MESH_INDEX_WEAK_HASH 27        /* itm_mesh_index: the hash cut to 8 bits (256 start slots spread over the table, the last 64 slots before its end): probe chains hundreds of slots long and the wrap-around on small meshes */
 #define ITM_DEBUG_FAIL_ALLOCATION 28             /* n > 0: the n-th allocation the library attempts from now on (device or pinned memory) fails with out-of-memory before the runtime is called, then the key clears itself; 0 = off */
+#define ITM_DEBUG_POSE_QUALITY_ROWS 29            /* itm_pose_quality_evaluate: a wave covers 64 x 1 pixels of a row instead of an 8 x 8 tile (same counts and residual image; the sums are added in another order) */
 int ITM_FN(debug_set)(int key, int value);
 /* Everything the library allocates passes through one pair of functions (csrc/device_memory.h): out = {live allocations, live bytes,
  * allocations attempted since the library was loaded}, device and pinned memory together, process-wide.  Memory handed out by

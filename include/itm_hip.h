@@ -872,6 +872,63 @@ int ITM_FN(reloc_upload)(itm_reloc* reloc, int32_t n, const uint8_t* codes_host,
 int ITM_FN(reloc_save)(itm_reloc* reloc, const char* dir);
 int ITM_FN(reloc_load)(itm_reloc* reloc, const char* dir);
 
+/* ---- pose quality: "does this depth image, under this pose, agree with the fused volume?" -------------------------------------------
+ * The judgement later InfiniTAM releases attach to a tracker's result (GOOD / POOR / FAILED), made here against the TSDF itself and
+ * not against a tracker's residuals: it holds for every tracker type (an external pose source included), voxel type and index type,
+ * and a tracker's own outlier rejection cannot flatter it.  The reference at this revision has none; this definition is the
+ * specification and tests/pose_quality_terms.py its restatement.  ITMMainEngine_HIP acts on the verdict when
+ * ITMLibSettings::useTrackingVerdict is set (include/itm_hip_engines.hpp).
+ *
+ * Sequential definition (float32, every product and sum rounded on its own, division IEEE).  For pixel (x, y) of view->depth (w x h,
+ * intr_d = (fx, fy, cx, cy), pose M_d):
+ *   d = depth[y * w + x].  !(d > 0) (negative, zero, NaN): the pixel is NONE.
+ *   pc = (d * ((float(x) - cx) / fx), d * ((float(y) - cy) / fy), d)                 (the ICP tracker's back-projection order)
+ *   pw = invM * (pc, 1), invM = Matrix4::inv of M_d as AllocateSceneFromDepth forms it, the product left to right as ORUtils'
+ *        Matrix4 * Vector4: pw[r] = ((m[r] * x + m[4 + r] * y) + m[8 + r] * z) + m[12 + r]
+ *   (sdf, weight, flags) = itm_scene_query_points at pw with ITM_QUERY_METRES: the interpolated sdf, the weight and the flags
+ *   KNOWN    flags has bit 0 (the voxel at ROUND(p) exists), not ITM_QUERY_INVALID, and weight >= cfg.minWeight
+ *   UNKNOWN  every other pixel that is not NONE; a block that is swapped out reads as absent
+ *   r = sdf * mu (metres; the sdf is clamped, so |r| <= mu)
+ *   INLIER   KNOWN and fabsf(r) <= cfg.inlierDistance
+ * itm_pose_quality: noPixels = w * h, noValid = pixels that are not NONE, noKnown, noInliers; sumSqKnown / sumSqInliers = the sum of
+ * (double)r * (double)r (an exact product) over the KNOWN / INLIER pixels, added in a fixed order: the same call gives the same bits.
+ * The optional residual image float[h * w] holds r for KNOWN pixels, ITM_POSE_QUALITY_UNKNOWN for UNKNOWN, ITM_POSE_QUALITY_NONE for
+ * NONE.
+ *
+ * Verdict (itm_pose_quality_verdict: host only, a pure function of counts and configuration, compared in double):
+ *   ITM_TRACKING_FAILED  noValid < minValidFraction * noPixels, or noKnown < failOverlap * noValid, or noInliers < failInliers *
+ *                        noKnown, or noKnown == 0
+ *   ITM_TRACKING_POOR    not failed, and noKnown < poorOverlap * noValid or noInliers < goodInliers * noKnown
+ *   ITM_TRACKING_GOOD    otherwise
+ * Defaults (itm_pose_quality_default_config(mu): host only): inlierDistance 0.5f * mu, minWeight 1, minValidFraction 0.05,
+ * failOverlap 0.10, poorOverlap 0.30, failInliers 0.50, goodInliers 0.90.  The thresholds are POLICY: they separate the true pose from
+ * shifted and rotated ones on the synthetic sphere-and-wall scene of the tests; nobody has tuned them on sensor data.
+ * ITM_ERR_INVALID: !(0 < inlierDistance), a fraction outside [0, 1], failOverlap > poorOverlap, failInliers > goodInliers,
+ * minWeight < 1, a null argument, w * h <= 0.
+ *
+ * Calls.  A handle owns its reduction records and serialises its own calls (two host threads use two handles).  evaluate launches the
+ * scene's recorded calls first, only reads the scene, enqueues ONE launch on `stream` and returns with *out filled: the result
+ * arrives through tagged records in page-locked host memory, no stream synchronise.  residuals_dev (device float[h * w]) may be
+ * NULL. */
+#define ITM_TRACKING_FAILED 0
+#define ITM_TRACKING_POOR 1
+#define ITM_TRACKING_GOOD 2
+#define ITM_POSE_QUALITY_UNKNOWN 1e30f
+#define ITM_POSE_QUALITY_NONE (-1e30f)
+typedef struct itm_pose_quality_handle itm_pose_quality_handle;
+typedef struct itm_pose_quality_config {
+  float inlierDistance;      /* metres */
+  int32_t minWeight;         /* w_depth a voxel needs to count as KNOWN */
+  float minValidFraction, failOverlap, poorOverlap, failInliers, goodInliers;
+} itm_pose_quality_config;
+typedef struct itm_pose_quality { int32_t noPixels, noValid, noKnown, noInliers; double sumSqKnown, sumSqInliers; } itm_pose_quality;
+int ITM_FN(pose_quality_default_config)(float mu, itm_pose_quality_config* cfg);
+int ITM_FN(pose_quality_verdict)(const itm_pose_quality* stats, const itm_pose_quality_config* cfg, int32_t* result);
+int ITM_FN(pose_quality_create)(itm_pose_quality_handle** out);
+int ITM_FN(pose_quality_destroy)(itm_pose_quality_handle* handle);
+int ITM_FN(pose_quality_evaluate)(itm_pose_quality_handle* handle, const itm_scene* scene, const itm_view* view, const itm_pose_quality_config* cfg,
+                                  itm_pose_quality* out, float* residuals_dev, itm_stream stream);
+
 /* The acceleration structures a hash scene carries beside the reference's table (none of them part of the reference's state, all
  * derived from it): a block directory and a slot directory over a cube of 512^3 blocks, an sdf mirror over 256^3 blocks for the
  * short voxel types.  The cubes are NOT tied to the world origin: the first frame places them around its camera (the reference's

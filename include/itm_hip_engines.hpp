@@ -144,6 +144,14 @@ struct ITMLibSettings {
   bool useRelocalisation = false;
   float relocHarvestingThreshold = 0.2f;      // a frame becomes a keyframe when its nearest keyframe is further than this
   int relocCapacity = 65536;                  // rows of the keyframe database
+  // Tracking verdict (ITMPoseQuality_HIP, itm_pose_quality_*; the reference at this revision has none).  false (default): nothing is
+  // created and no code path changes.  true: ITMMainEngine_HIP judges every tracked pose against the fused volume, fuses and
+  // harvests GOOD frames only and, with useRelocalisation, recovers a FAILED pose from the nearest keyframe.
+  bool useTrackingVerdict = false;
+  // The verdict's thresholds: filled by itm_pose_quality_default_config(mu) when inlierDistance is 0.  The defaults are policy,
+  // chosen on a synthetic scene and not tuned on sensor data (include/itm_hip.h).
+  itm_pose_quality_config poseQuality = {0.0f, 0, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  int relocFusionDelay = 10;                  // GOOD frames that are tracked but not fused after a recovery
 };
 
 struct ITMSceneParams : itm_scene_params {
@@ -646,6 +654,40 @@ class ITMRelocaliser_HIP {
   itm_reloc* Handle() { return handle; }
 };
 
+// Pose quality (itm_pose_quality_*, include/itm_hip.h): a view's depth image under the tracking state's pose, judged against the
+// fused volume.  One launch per Evaluate; the counts are on the host when it returns.
+class ITMPoseQuality_HIP {
+  itm_pose_quality_handle* handle = nullptr;
+
+ public:
+  enum TrackingResult { TRACKING_FAILED = ITM_TRACKING_FAILED, TRACKING_POOR = ITM_TRACKING_POOR, TRACKING_GOOD = ITM_TRACKING_GOOD };
+  itm_pose_quality_config config;
+  itm_stream stream = nullptr;
+  // config_.inlierDistance == 0: the defaults for `mu`
+  ITMPoseQuality_HIP(float mu, const itm_pose_quality_config& config_) : config(config_) {
+    if (config.inlierDistance == 0.0f) check(itm_pose_quality_default_config(mu, &config), "itm_pose_quality_default_config");
+    check(itm_pose_quality_create(&handle), "itm_pose_quality_create");
+  }
+  explicit ITMPoseQuality_HIP(float mu) : ITMPoseQuality_HIP(mu, itm_pose_quality_config{0.0f, 0, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}) {}
+  ~ITMPoseQuality_HIP() { itm_pose_quality_destroy(handle); }
+  ITMPoseQuality_HIP(const ITMPoseQuality_HIP&) = delete;
+  ITMPoseQuality_HIP& operator=(const ITMPoseQuality_HIP&) = delete;
+
+  // residuals: device float[h * w] or nullptr (ITM_POSE_QUALITY_UNKNOWN / _NONE mark the pixels without a residual)
+  template <class TVoxel, class TIndex>
+  itm_pose_quality Evaluate(const ITMScene<TVoxel, TIndex>* scene, const ITMView* view, const ITMTrackingState* trackingState, float* residuals = nullptr) {
+    itm_view v = make_view(view, trackingState);
+    itm_pose_quality out;
+    check(itm_pose_quality_evaluate(handle, scene->handle, &v, &config, &out, residuals, stream), "ITMPoseQuality_HIP::Evaluate");
+    return out;
+  }
+  TrackingResult Verdict(const itm_pose_quality& stats) const {
+    int32_t r = ITM_TRACKING_FAILED;
+    check(itm_pose_quality_verdict(&stats, &config, &r), "ITMPoseQuality_HIP::Verdict");
+    return (TrackingResult)r;
+  }
+};
+
 // ITMTrackingController (Engine/ITMTrackingController.cpp:11-46): Track and Prepare, statement for statement
 template <class TVoxel, class TIndex>
 class ITMTrackingController_HIP {
@@ -716,6 +758,13 @@ class ITMMainEngine_HIP {
   void* depthImageBuf = nullptr;                       // device uchar4 of the depth size: the coloured depth / uncertainty image of GetImage
   ITMRelocaliser_HIP* relocaliser = nullptr;           // settings.useRelocalisation
   bool harvestingActive = true;
+  // settings.useTrackingVerdict (all unused without it)
+  ITMPoseQuality_HIP* poseQuality = nullptr;
+  ITMPoseQuality_HIP::TrackingResult trackingResult = ITMPoseQuality_HIP::TRACKING_GOOD;
+  itm_pose_quality lastQuality = {0, 0, 0, 0, 0.0, 0.0};
+  ITMPose endPose;                 // pose_d as the previous frame left it
+  bool haveEndPose = false, anyFrameFused = false, lastFrameFused = false;
+  int fusionDelay = 0, relocalisationCount = 0;
 
  public:
   // calibType / c0 / c1: ITMDisparityCalib (0 = TRAFO_KINECT, 1 = TRAFO_AFFINE); sizes as ITMMainEngine's imgSize_rgb / imgSize_d
@@ -761,8 +810,10 @@ class ITMMainEngine_HIP {
     if (settings.useRelocalisation)
       relocaliser = new ITMRelocaliser_HIP(imgSize_d, Vector2f{params.viewFrustum_min, params.viewFrustum_max}, settings.relocHarvestingThreshold, 500, 4,
                                            settings.relocCapacity);
+    if (settings.useTrackingVerdict) poseQuality = new ITMPoseQuality_HIP(params.mu, settings.poseQuality);
   }
   ~ITMMainEngine_HIP() {
+    delete poseQuality;
     delete relocaliser;
     itm_mesh_destroy(exportMesh);
     delete renderState_freeview; itm_dev_free(depthImageBuf);
@@ -823,6 +874,7 @@ class ITMMainEngine_HIP {
  private:
   void ProcessView() {
     if (!mainProcessingActive) return;
+    if (poseQuality) { ProcessViewJudged(); return; }
     // pose of this frame against the maps of the last ray cast
     trackingController->Track(&trackingState, &view);
     // allocate + integrate (the library records both; they launch with the two calls of Prepare as ONE fused frame, pending.hip)
@@ -851,11 +903,12 @@ class ITMMainEngine_HIP {
     viewBuilder->UpdateView(&view, rawDepthImage, (float*)depthBuf, (float*)scratchBuf, settings.useBilateralFilter, ModelSensorNoise(),
                             (float*)normalBuf, (float*)sigmaBuf);
     view.depthUncertainty = ModelSensorNoise() ? (const float*)sigmaBuf : nullptr;
-    if (!relocaliser) return -1;
-    int nearest = -1; float distance = 1.0f;
-    relocaliser->ProcessFrame(view.depth, nullptr, 1, &nearest, &distance, false);
-    if (nearest < 0) return -1;
-    trackingState.pose_d = relocaliser->RetrievePose(nearest);
+    return RecoverFromKeyframe();
+  }
+
+ private:
+  // the live visible list rebuilt for pose_d
+  void FindVisibleBlocksAtPose() {
     if (settings.trackerType == ITMLibSettings::TRACKER_COLOR) {      // the live render state is the colour camera's (Prepare)
       ITMPose pose_rgb;
       float M[16];
@@ -865,12 +918,89 @@ class ITMMainEngine_HIP {
     } else {
       visualisationEngine.FindVisibleBlocks(&trackingState.pose_d, &view.calib.intrinsics_d, renderState_live);
     }
+  }
+
+  // The recovery of Relocalise for the view as it stands (also what a FAILED verdict runs): -1 and nothing changed without a
+  // relocaliser or a keyframe, else the keyframe's id.
+  int RecoverFromKeyframe() {
+    if (!relocaliser) return -1;
+    int nearest = -1; float distance = 1.0f;
+    relocaliser->ProcessFrame(view.depth, nullptr, 1, &nearest, &distance, false);
+    if (nearest < 0) return -1;
+    trackingState.pose_d = relocaliser->RetrievePose(nearest);
+    FindVisibleBlocksAtPose();
     trackingState.requiresFullRendering = true;
     trackingController->Prepare(&trackingState, &view, renderState_live);
     trackingController->Track(&trackingState, &view);
     trackingController->Prepare(&trackingState, &view, renderState_live);
     return nearest;
   }
+
+  // view.depth under pose_d against the fused volume; the counts stay in lastQuality
+  ITMPoseQuality_HIP::TrackingResult Judge() {
+    lastQuality = poseQuality->Evaluate(&scene, &view, &trackingState);
+    return poseQuality->Verdict(lastQuality);
+  }
+
+  // ProcessView with settings.useTrackingVerdict: the tracked pose is judged before anything is written.  GOOD: the frame is fused
+  // and offered as a keyframe as ever (unless a recovery's delay is pending: it counts down on GOOD frames only).  POOR: neither,
+  // the maps are prepared from the tracked pose.  FAILED: neither, pose_d goes back to the pose the frame started from -- for poses
+  // from outside (ITMExternalTracker: the host has overwritten pose_d before the call) the pose the previous frame ended with --
+  // and, with a relocaliser, the recovery of Relocalise runs and is judged in its turn: it stands unless it FAILED too.
+  void ProcessViewJudged() {
+    typedef ITMPoseQuality_HIP Q;
+    const bool posesFromOutside = !depthTracker && !colourTracker && !renTracker && !wicpTracker;
+    const ITMPose remembered = (posesFromOutside && haveEndPose) ? endPose : trackingState.pose_d;
+    trackingController->Track(&trackingState, &view);
+    lastFrameFused = false;
+    Q::TrackingResult result = Q::TRACKING_GOOD;      // nothing fused yet: the map is empty and every pose is as good as another
+    if (anyFrameFused) result = Judge();
+    else lastQuality = itm_pose_quality{0, 0, 0, 0, 0.0, 0.0};
+    if (result == Q::TRACKING_GOOD) {
+      const bool delayed = fusionDelay > 0;
+      if (fusionActive && !delayed) {
+        denseMapper.ProcessFrame(&view, &trackingState, &scene, renderState_live);
+        anyFrameFused = lastFrameFused = true;
+      }
+      trackingController->Prepare(&trackingState, &view, renderState_live);
+      if (relocaliser && fusionActive && harvestingActive && !delayed) {
+        int nearest; float distance;
+        relocaliser->ProcessFrame(view.depth, &trackingState.pose_d, 1, &nearest, &distance, true);
+      }
+      if (delayed) --fusionDelay;
+    } else if (result == Q::TRACKING_POOR) {
+      trackingController->Prepare(&trackingState, &view, renderState_live);
+    } else {
+      trackingState.pose_d = remembered;
+      bool recovered = false;
+      if (RecoverFromKeyframe() >= 0) {
+        const Q::TrackingResult again = Judge();
+        if (again != Q::TRACKING_FAILED) {
+          recovered = true; result = again;
+          fusionDelay = settings.relocFusionDelay;
+          ++relocalisationCount;
+        } else {
+          trackingState.pose_d = remembered;
+          FindVisibleBlocksAtPose();      // the recovery left the keyframe's visible list behind
+        }
+      }
+      if (!recovered) {
+        trackingState.requiresFullRendering = true;
+        trackingController->Prepare(&trackingState, &view, renderState_live);
+      }
+    }
+    trackingResult = result;
+    endPose = trackingState.pose_d; haveEndPose = true;
+  }
+
+ public:
+  // Tracking verdict (settings.useTrackingVerdict; without it: GOOD, zero counts, 0, false).  The result and counts of the last
+  // frame -- after a recovery those of the second evaluation, at the recovered pose --, the recoveries so far, and whether the
+  // last frame was integrated.
+  ITMPoseQuality_HIP::TrackingResult GetTrackingResult() const { return trackingResult; }
+  const itm_pose_quality& GetPoseQuality() const { return lastQuality; }
+  int GetRelocalisationCount() const { return relocalisationCount; }
+  bool LastFrameFused() const { return lastFrameFused; }
   void turnOnIntegration() { fusionActive = true; }
   void turnOffIntegration() { fusionActive = false; }
   void turnOnMainProcessing() { mainProcessingActive = true; }

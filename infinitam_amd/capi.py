@@ -193,6 +193,26 @@ class RelocConfig(C.Structure):
 RELOC_MAX_K, RELOC_MAX_FERNS = 8, 1024
 
 
+class PoseQualityConfig(C.Structure):
+    """itm_pose_quality_config (include/itm_hip.h, the tracking verdict)."""
+    _fields_ = [("inlierDistance", C.c_float), ("minWeight", C.c_int32), ("minValidFraction", C.c_float), ("failOverlap", C.c_float),
+                ("poorOverlap", C.c_float), ("failInliers", C.c_float), ("goodInliers", C.c_float)]
+
+
+class PoseQualityStats(C.Structure):
+    """itm_pose_quality (include/itm_hip.h)."""
+    _fields_ = [("noPixels", C.c_int32), ("noValid", C.c_int32), ("noKnown", C.c_int32), ("noInliers", C.c_int32),
+                ("sumSqKnown", C.c_double), ("sumSqInliers", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+TRACKING_FAILED, TRACKING_POOR, TRACKING_GOOD = 0, 1, 2
+POSE_QUALITY_UNKNOWN, POSE_QUALITY_NONE = np.float32(1e30), np.float32(-1e30)
+DEBUG_POSE_QUALITY_ROWS = 29
+
+
 class ItmError(RuntimeError):
     pass
 
@@ -377,6 +397,12 @@ _HOST_IO_SIGS = {
     "reloc_save": (C.c_int, [_P, C.c_char_p]),
     "reloc_load": (C.c_int, [_P, C.c_char_p]),
     "debug_reloc_search_ms": (C.c_int, [_P, C.c_int, C.POINTER(C.c_float)]),
+    # pose quality / tracking verdict (product only); default_config and verdict are host-only
+    "pose_quality_default_config": (C.c_int, [C.c_float, C.POINTER(PoseQualityConfig)]),
+    "pose_quality_verdict": (C.c_int, [C.POINTER(PoseQualityStats), C.POINTER(PoseQualityConfig), C.POINTER(C.c_int32)]),
+    "pose_quality_create": (C.c_int, [C.POINTER(_P)]),
+    "pose_quality_destroy": (C.c_int, [_P]),
+    "pose_quality_evaluate": (C.c_int, [_P, _P, C.POINTER(ViewStruct), C.POINTER(PoseQualityConfig), C.POINTER(PoseQualityStats), _P, _P]),
 }
 
 
@@ -868,6 +894,55 @@ class Relocaliser:
     def close(self):
         if self.h:
             self.be.fn["reloc_destroy"](_P(self.h))
+            self.h = 0
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PoseQuality:
+    """itm_pose_quality_handle: a depth image under a pose judged against the fused volume (include/itm_hip.h).  One handle per host
+    thread; evaluate returns the counts (PoseQualityStats), with residuals=True also the per-pixel image float32[h, w]."""
+
+    def __init__(self, be: Backend):
+        self.be, self.h = be, 0
+        p = _P()
+        be.check(be.fn["pose_quality_create"](C.byref(p)), "pose_quality_create")
+        self.h = p.value
+
+    @staticmethod
+    def default_config(be: Backend, mu: float) -> PoseQualityConfig:
+        cfg = PoseQualityConfig()
+        be.check(be.fn["pose_quality_default_config"](float(mu), C.byref(cfg)), "pose_quality_default_config")
+        return cfg
+
+    @staticmethod
+    def verdict(be: Backend, stats: PoseQualityStats, cfg: PoseQualityConfig) -> int:
+        out = C.c_int32(-1)
+        be.check(be.fn["pose_quality_verdict"](C.byref(stats), C.byref(cfg), C.byref(out)), "pose_quality_verdict")
+        return out.value
+
+    def evaluate(self, scene: "Scene", view: "View", cfg: Optional[PoseQualityConfig] = None, residuals=False, stream=None):
+        """itm_pose_quality_evaluate of view.depth under view.M_d; cfg None: the defaults for the scene's mu.  Returns the stats, or
+        (stats, residual image) with residuals=True (downloaded: synchronises `stream`)."""
+        if cfg is None:
+            cfg = self.default_config(self.be, scene.params.mu)
+        vs = view.struct()
+        out = PoseQualityStats()
+        buf = DevBuffer(self.be, view.w * view.h * 4, np.float32, (view.h, view.w)) if residuals else None
+        rc = self.be.fn["pose_quality_evaluate"](_P(self.h), _P(scene.h), C.byref(vs), C.byref(cfg), C.byref(out), _P(buf.ptr if buf else None), _P(stream))
+        img = buf.numpy(stream) if (buf is not None and rc == 0) else None
+        if buf is not None:
+            buf.close()
+        self.be.check(rc, "pose_quality_evaluate")
+        return (out, img) if residuals else out
+
+    def close(self):
+        if self.h:
+            self.be.fn["pose_quality_destroy"](_P(self.h))
             self.h = 0
 
     def __del__(self):
