@@ -1,8 +1,8 @@
 // mesh_attributes.hip -- per-vertex normals and colours of the marching-cubes mesh, and the PLY writer that carries them.
 //
 // Reference behaviour (the reference's ITMMesh holds positions only; the two per-point functions are the reference's own):
-//   computeSingleNormalFromSDF            DeviceAgnostic/ITMRepresentationAccess.h:224-337   (shading_device.h: sdf_gradient)
-//   readFromSDF_color4u_interpolated      DeviceAgnostic/ITMRepresentationAccess.h:187-222   (shading_device.h: colour_at)
+//   computeSingleNormalFromSDF            DeviceAgnostic/ITMRepresentationAccess.h:224-337   (sample_device.h: gradient_axis)
+//   readFromSDF_color4u_interpolated      DeviceAgnostic/ITMRepresentationAccess.h:187-222   (sample_device.h: colour_from)
 //   drawPixelColour (float -> uchar)      DeviceAgnostic/ITMVisualisationEngine.h:270-279
 // evaluated at p = vertex / voxelSize (three IEEE divisions) for every vertex of the triangles the last itm_mesh_scene left in
 // the buffer, in buffer order.  The normal is the gradient times 1 / sqrt(g.g) (as normal_from_sdf forms it, no light test) and
@@ -40,9 +40,9 @@ constexpr int kHaloSide = kBlockSide + 5;         // -2 .. +10
 constexpr int kHaloCells = kHaloSide * kHaloSide * kHaloSide;
 
 // the attributes of vertex v through the hash (directory / mirror where they cover) or, DENSE, the voxel array: the reference's
-// functions as the renders use them
+// functions as the renders use them (forced inline: out of line, the colour instances of the per-vertex kernel take scratch for the call)
 template <class VX, bool DENSE = false>
-__device__ inline void vertex_global(const VolumeView& vol, size_t v, float px, float py, float pz, uint32_t what,
+__device__ __forceinline__ void vertex_global(const VolumeView& vol, size_t v, float px, float py, float pz, uint32_t what,
                                      float* __restrict__ normals, uchar4* __restrict__ colours) {
   if (what & ITM_MESH_NORMALS) {
     float gx, gy, gz;
@@ -174,12 +174,10 @@ int itm_mesh_attributes(const itm_scene* s, itm_mesh* m, int what, itm_stream st
   }
   const VolumeView vol = make_volume(s);
   const int grid = 256 * 8;
-  const int rc = dispatch_voxel(s->cfg.voxelType, [&](auto vx) {
+  const int rc = dispatch_volume(s, [&](auto vx, auto isDense) {
     using VX = decltype(vx);
-    if (dense)                                   // the mesh of itm_mesh_volume: every vertex through the voxel array
-      mesh_attr_vertex_kernel<VX, true><<<grid, 256, 0, st>>>(vol, m->triangles, m->totals, 0u, s->prm.voxelSize, (uint32_t)what, m->normals, m->colours);
-    else if (g_debug_mesh_attr_per_vertex)
-      mesh_attr_vertex_kernel<VX, false><<<grid, 256, 0, st>>>(vol, m->triangles, m->totals, 0u, s->prm.voxelSize, (uint32_t)what, m->normals, m->colours);
+    if (isDense.value || g_debug_mesh_attr_per_vertex)      // the mesh of itm_mesh_volume: every vertex through the voxel array
+      mesh_attr_vertex_kernel<VX, isDense.value><<<grid, 256, 0, st>>>(vol, m->triangles, m->totals, 0u, s->prm.voxelSize, (uint32_t)what, m->normals, m->colours);
     else
       mesh_attr_block_kernel<VX, false><<<grid, 256, 0, st>>>(vol, m->slots, m->listCounters, m->blockTriangles, m->triangles, m->totals, m->capBlocks, s->prm.voxelSize,
                                                       (uint32_t)what, m->normals, m->colours);
@@ -231,9 +229,9 @@ int itm_mesh_indexed_attributes(const itm_scene* s, itm_mesh* m, int what, itm_s
   }
   const VolumeView vol = make_volume(s);
   const int grid = 256 * 8;
-  const int rc = dispatch_voxel(s->cfg.voxelType, [&](auto vx) {
+  const int rc = dispatch_volume(s, [&](auto vx, auto isDense) {
     using VX = decltype(vx);
-    if (s->cfg.indexType != ITM_INDEX_HASH)      // the mesh of itm_mesh_volume on a dense scene: one lane per unique vertex
+    if (isDense.value)                           // the mesh of itm_mesh_volume on a dense scene: one lane per unique vertex
       mesh_attr_vertex_kernel<VX, true><<<grid, 256, 0, st>>>(vol, m->vertices, nullptr, m->noVertices, s->prm.voxelSize, (uint32_t)what, m->vertexNormals, m->vertexColours);
     else
       mesh_attr_block_kernel<VX, true><<<grid, 256, 0, st>>>(vol, m->slots, m->listCounters, m->blockVertex, m->vertices, m->totals, m->capBlocks, s->prm.voxelSize,

@@ -9,7 +9,7 @@
 //     through the dense readVoxel (ITMRepresentationAccess.h:129-142): a corner outside the array is "not found";
 //   * the buffer is ITMMesh's: cleared first, the count stops at noMaxTriangles - 1, the last slot keeps the last triangle generated.
 // A hash scene whose blocks hold the same voxels at the same global positions gives the same triangles, block run for block run --
-// the float operations are those of mesh_cells_kernel (meshing.hip), in the same order.
+// both kernels classify and emit a cell through mc_device.h.
 //
 // MI355X design: three launches, no host round trip.
 //   1. mesh_bricks_kernel<COUNT>: persistent 512-lane workgroups stride over all bricks.  The 9^3 sdf samples of a brick (its voxels
@@ -20,19 +20,14 @@
 //   2. mesh_brick_scan_kernel: one workgroup, four bricks per lane: exclusive 64-bit prefix of the counts (base of every brick) and,
 //      in the same sweep, the ascending list of the bricks that have triangles.
 //   3. mesh_bricks_kernel<WRITE>: the same staging over the listed bricks only; lanes interpolate and write at base + offset.
-#include <mutex>
 #include <new>
 
 #include "itm_internal.h"
-#include "mc_tables.h"
-#include "shading_device.h"
+#include "mc_device.h"
 #include "mesh_types.h"
 #include "wave_utils.h"
 
 namespace itm {
-
-// the case table of this translation unit (constant memory is per code object symbol); uploaded by upload_dense_tables
-__device__ __constant__ uint64_t d_denseTriangleCases[256];
 
 constexpr int kBrickSamples = 9 * 9 * 9;
 
@@ -87,61 +82,17 @@ __global__ void __launch_bounds__(512) mesh_bricks_kernel(VolumeView vol, BrickG
       continue;
     }
     const int x = t & 7, y = (t >> 3) & 7, z = t >> 6;       // z outer, x inner == ascending t
-    float val[8];
-    bool ok = true;
-    uint32_t cube = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int c = kCubeCorner[k];
-      val[k] = sdf[(x + (c & 1)) + (y + ((c >> 1) & 1)) * 9 + (z + (c >> 2)) * 81];
-      ok = ok && !(val[k] != val[k]) && !(val[k] == 1.0f);   // findPointNeighbors: every corner found and != 1.0f
-      if (val[k] < 0.0f) cube |= 1u << k;
-    }
-    int nTri = 0;
-    uint64_t cases = ~0ull;
-    if (ok && cube != 0u && cube != 255u) {
-      cases = d_denseTriangleCases[cube];
-      for (uint64_t l = cases; (l & 0xfull) != 0xfull; l >>= 12) ++nTri;
-    }
+    const McCell cell = classify_cell(sdf, x, y, z);
     int total;
-    const int offset = block_exclusive_scan<8>(nTri, scan, &total);
+    const int offset = block_exclusive_scan<8>(cell.nTri, scan, &total);
     if (!WRITE) {
       if (t == 0) brickCount[cur] = total;
       continue;
     }
-    if (nTri == 0) continue;
+    if (cell.nTri == 0) continue;
     // L = (array index) + denseOffset, the integer sum converted (as blockLocation + offset of the hash mesher)
-    const int lx = cbx * kBlockSide + x + vol.ox, ly = cby * kBlockSide + y + vol.oy, lz = cbz * kBlockSide + z + vol.oz;
-    float corner[8][3];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int c = kCubeCorner[k];
-      corner[k][0] = (float)(lx + (c & 1)); corner[k][1] = (float)(ly + ((c >> 1) & 1)); corner[k][2] = (float)(lz + (c >> 2));
-    }
-    const uint32_t edges = crossed_edges(cube);
-    float vert[12][3];
-#pragma unroll
-    for (int e = 0; e < 12; ++e)
-      if (edges & (1u << e)) edge_vertex(corner[kCubeEdge[e][0]], corner[kCubeEdge[e][1]], val[kCubeEdge[e][0]], val[kCubeEdge[e][1]], vert[e]);
-    const unsigned long long generated = *generatedTotal;
-    unsigned long long g = brickBase[cur] + (unsigned long long)offset;
-    for (uint64_t l = cases; (l & 0xfull) != 0xfull; l >>= 12, ++g) {
-      // triangles[noTriangles] = ...; if (noTriangles < noMaxTriangles - 1) noTriangles++   (_CPU.cpp:48-52)
-      unsigned long long dst = g;
-      if (g >= (unsigned long long)maxTriangles - 1ull) {
-        if (g != generated - 1ull) continue;              // only the last triangle generated survives in the last slot
-        dst = (unsigned long long)maxTriangles - 1ull;
-      }
-      float* o = triangles + dst * 9ull;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const int e = (int)((l >> (4 * k)) & 0xfull);
-        float vx = 0.0f, vy = 0.0f, vz = 0.0f;
-#pragma unroll
-        for (int q = 0; q < 12; ++q) if (q == e) { vx = vert[q][0]; vy = vert[q][1]; vz = vert[q][2]; }
-        o[3 * k + 0] = vx * factor; o[3 * k + 1] = vy * factor; o[3 * k + 2] = vz * factor;
-      }
-    }
+    emit_cell(cell, cbx * kBlockSide + x + vol.ox, cby * kBlockSide + y + vol.oy, cbz * kBlockSide + z + vol.oz, brickBase[cur] + (unsigned long long)offset,
+              *generatedTotal, maxTriangles, factor, triangles);
   }
 }
 
@@ -189,8 +140,6 @@ __global__ void __launch_bounds__(1024) mesh_brick_scan_kernel(const int32_t* __
   }
 }
 
-static int upload_dense_tables() { return upload_case_table<struct DenseMesherTable>(HIP_SYMBOL(d_denseTriangleCases)); }
-
 // the dense part of itm_mesh_volume: the buffer and totals are already cleared on `st`
 int launch_mesh_volume_dense(const itm_scene* s, itm_mesh* m, hipStream_t st) {
   BrickGrid g;
@@ -200,8 +149,6 @@ int launch_mesh_volume_dense(const itm_scene* s, itm_mesh* m, hipStream_t st) {
   const long long nb = (long long)g.nbx * g.nby * g.nbz;
   if (nb <= 0 || nb > 0x7fffffffll - 4096) return set_error(ITM_ERR_INVALID, "dense volume has no bricks or too many to mesh");
   g.nBricks = (int)nb;
-  int rc = upload_dense_tables();
-  if (rc) return rc;
   if (!m->brickCount) {                                         // the per-brick buffers belong to the mesh: allocated on the first dense call
     hipError_t e = m->brickCount.alloc((size_t)g.nBricks);
     if (e == hipSuccess) e = m->brickBase.alloc((size_t)g.nBricks);
@@ -217,7 +164,7 @@ int launch_mesh_volume_dense(const itm_scene* s, itm_mesh* m, hipStream_t st) {
   // persistent grid: four 512-lane workgroups fill a compute unit (2 048 lanes), 256 compute units on the MI355X -- the grid of the hash
   // mesher.  The emit pass keeps it although it strides over the listed bricks only: workgroups without a brick leave at once.
   const int launch = g.nBricks < 256 * 4 ? g.nBricks : 256 * 4;
-  rc = dispatch_voxel(s->cfg.voxelType, [&](auto vx) {
+  const int rc = dispatch_voxel(s->cfg.voxelType, [&](auto vx) {
     using VX = decltype(vx);
     mesh_bricks_kernel<VX, false><<<launch, 512, 0, st>>>(vol, g, m->brickList, m->brickCounters, m->brickCount, m->brickBase, generated, m->triangles, m->maxTriangles,
                                                           s->prm.voxelSize);

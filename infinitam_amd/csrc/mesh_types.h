@@ -2,11 +2,8 @@
 // mesh_index.hip (the indexed form: shared vertices and faces).
 #pragma once
 
-#include <mutex>
-
 #include "itm_internal.h"
-#include "mc_tables.h"
-#include "shading_device.h"
+#include "volume_device.h"
 
 struct itm_mesh {
   const itm_scene* scene = nullptr;
@@ -48,62 +45,5 @@ struct itm_mesh {
 namespace itm {
 
 int launch_mesh_volume_dense(const itm_scene* s, itm_mesh* m, hipStream_t st);   // mesh_dense.hip
-
-// ---- the per-cell pieces the hash mesher (meshing.hip) and the dense mesher (mesh_dense.hip) share: one copy, so the two cannot drift ----
-
-// which of the 12 edges a sign configuration crosses: an edge is crossed when its two corners have different signs
-__device__ inline uint32_t crossed_edges(uint32_t cube) {
-  uint32_t mask = 0;
-#pragma unroll
-  for (int e = 0; e < 12; ++e)
-    if (((cube >> kCubeEdge[e][0]) ^ (cube >> kCubeEdge[e][1])) & 1u) mask |= 1u << e;
-  return mask;
-}
-
-// sdfInterp (DeviceAgnostic/ITMMeshingEngine.h:194-201), per component; p1/p2 are integer-valued voxel coordinates
-__device__ inline void edge_vertex(const float* p1, const float* p2, float v1, float v2, float* out) {
-  if (fabsf(0.0f - v1) < 0.00001f) { out[0] = p1[0]; out[1] = p1[1]; out[2] = p1[2]; return; }
-  if (fabsf(0.0f - v2) < 0.00001f) { out[0] = p2[0]; out[1] = p2[1]; out[2] = p2[2]; return; }
-  if (fabsf(v1 - v2) < 0.00001f) { out[0] = p1[0]; out[1] = p1[1]; out[2] = p1[2]; return; }
-  const float t = (0.0f - v1) / (v2 - v1);
-  out[0] = p1[0] + t * (p2[0] - p1[0]);
-  out[1] = p1[1] + t * (p2[1] - p1[1]);
-  out[2] = p1[2] + t * (p2[2] - p1[2]);
-}
-
-// what a mesher's scan leaves in itm_mesh::totals: [0] = the triangles generated, [1] = noTotalTriangles -- the reference's count stops at
-// noMaxTriangles - 1 (its last slot keeps being overwritten, _CPU.cpp:48-52)
-__device__ inline void store_triangle_totals(uint32_t* totals, unsigned long long generated, uint32_t maxTriangles) {
-  totals[0] = (uint32_t)generated;
-  totals[1] = (generated < (unsigned long long)maxTriangles - 1ull) ? (uint32_t)generated : maxTriangles - 1u;
-}
-
-// kTriangleCases into a translation unit's constant-memory table (a constant symbol belongs to its code object, so each mesher has
-// its own; TAG keeps their "done" flags apart): once per device, also when several host threads create meshes at the same time
-template <class TAG>
-inline int upload_case_table(const void* symbol) {
-  static std::mutex guard;
-  static bool done[64] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64) dev = 0;
-  std::lock_guard<std::mutex> lock(guard);
-  if (!done[dev]) {
-    ITM_HIP(hipMemcpyToSymbol(symbol, kTriangleCases, sizeof(kTriangleCases)));
-    done[dev] = true;
-  }
-  return ITM_OK;
-}
-
-// block base (voxel index of its first voxel) of block (bx, by, bz), or -1: directory where it covers, table walk elsewhere
-__device__ inline int block_base(const VolumeView& vol, int bx, int by, int bz) {
-  const uint32_t ux = (uint32_t)(bx - vol.org.dx), uy = (uint32_t)(by - vol.org.dy), uz = (uint32_t)(bz - vol.org.dz);
-  if (vol.dirPtr && dir_covers(ux, uy, uz)) {
-    const int ptr = vol.dirPtr[dir_cell(ux, uy, uz)];
-    return ptr < 0 ? -1 : ptr * kBlockVoxels;
-  }
-  if ((int)(int16_t)bx != bx || (int)(int16_t)by != by || (int)(int16_t)bz != bz) return -1;   // beyond the table's short coordinates
-  return resolve_block(vol, unpack_entry(vol.hash[hash_index(bx, by, bz, vol.mask)]), bx, by, bz);
-}
 
 }  // namespace itm

@@ -23,18 +23,13 @@
 #include <new>
 #include <vector>
 
-#include <mutex>
-
 #include "itm_internal.h"
-#include "mc_tables.h"
-#include "shading_device.h"
+#include "mc_device.h"
 #include "mesh_types.h"
 #include "ordered_device.h"
 #include "wave_utils.h"
 
 namespace itm {
-
-__device__ __constant__ uint64_t d_triangleCases[256];
 
 __global__ void __launch_bounds__(256) mesh_flag_kernel(const uint4* __restrict__ hash, int nEntries, uint8_t* __restrict__ flags, int32_t* __restrict__ chunkCount) {
   flag_chunk(nEntries, flags, chunkCount, [&](int slot) { return (int)hash[slot].w >= 0; });
@@ -63,65 +58,16 @@ __global__ void __launch_bounds__(512) mesh_cells_kernel(VolumeView vol, const i
     }
     __syncthreads();
     const int x = t & 7, y = (t >> 3) & 7, z = t >> 6;       // the reference's loop order: z outer, x inner == ascending t
-    float val[8];
-    bool ok = true;
-    uint32_t cube = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int c = kCubeCorner[k];
-      val[k] = sdf[(x + (c & 1)) + (y + ((c >> 1) & 1)) * 9 + (z + (c >> 2)) * 81];
-      ok = ok && !(val[k] != val[k]) && !(val[k] == 1.0f);   // findPointNeighbors: every corner stored and != 1.0f
-      if (val[k] < 0.0f) cube |= 1u << k;
-    }
-    int nTri = 0;
-    uint64_t list = ~0ull;
-    if (ok && cube != 0u && cube != 255u) {
-      list = d_triangleCases[cube];
-      for (uint64_t l = list; (l & 0xfull) != 0xfull; l >>= 12) ++nTri;
-    }
+    const McCell cell = classify_cell(sdf, x, y, z);
     int total;
-    const int offset = block_exclusive_scan<8>(nTri, scan, &total);
+    const int offset = block_exclusive_scan<8>(cell.nTri, scan, &total);
     if (!WRITE) {
       if (t == 0) blockTriangles[b] = total;
       continue;
     }
-    if (nTri == 0) continue;
-    // vertices on the crossed edges, in voxel units (global voxel coordinates as floats), then scaled by the voxel size
-    const float gx = (float)(he.px * kBlockSide + x), gy = (float)(he.py * kBlockSide + y), gz = (float)(he.pz * kBlockSide + z);
-    float corner[8][3];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int c = kCubeCorner[k];
-      // (blockLocation + offset).toFloat(): integer sum converted, the same value as the float sum for these magnitudes
-      corner[k][0] = (float)(he.px * kBlockSide + x + (c & 1)); corner[k][1] = (float)(he.py * kBlockSide + y + ((c >> 1) & 1));
-      corner[k][2] = (float)(he.pz * kBlockSide + z + (c >> 2));
-    }
-    (void)gx; (void)gy; (void)gz;
-    const uint32_t edges = crossed_edges(cube);
-    float vert[12][3];
-#pragma unroll
-    for (int e = 0; e < 12; ++e)
-      if (edges & (1u << e)) edge_vertex(corner[kCubeEdge[e][0]], corner[kCubeEdge[e][1]], val[kCubeEdge[e][0]], val[kCubeEdge[e][1]], vert[e]);
-    const uint64_t generated = totals[0];
-    uint64_t g = (uint64_t)(uint32_t)blockTriangles[b] + (uint64_t)offset;
-    for (uint64_t l = list; (l & 0xfull) != 0xfull; l >>= 12, ++g) {
-      // triangles[noTriangles] = ...; if (noTriangles < noMaxTriangles - 1) noTriangles++   (_CPU.cpp:48-52)
-      uint64_t dst = g;
-      if (g >= (uint64_t)maxTriangles - 1ull) {
-        if (g != generated - 1ull) continue;            // only the last triangle generated survives in the last slot
-        dst = (uint64_t)maxTriangles - 1ull;
-      }
-      float* o = triangles + dst * 9ull;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const int e = (int)((l >> (4 * k)) & 0xfull);
-        // a dynamically indexed private array would live in scratch: select through a switch-free chain over the 12 edges
-        float vx = 0.0f, vy = 0.0f, vz = 0.0f;
-#pragma unroll
-        for (int q = 0; q < 12; ++q) if (q == e) { vx = vert[q][0]; vy = vert[q][1]; vz = vert[q][2]; }
-        o[3 * k + 0] = vx * factor; o[3 * k + 1] = vy * factor; o[3 * k + 2] = vz * factor;
-      }
-    }
+    if (cell.nTri == 0) continue;
+    emit_cell(cell, he.px * kBlockSide + x, he.py * kBlockSide + y, he.pz * kBlockSide + z, (uint64_t)(uint32_t)blockTriangles[b] + (uint64_t)offset, totals[0],
+              maxTriangles, factor, triangles);
   }
 }
 
@@ -133,13 +79,6 @@ __global__ void __launch_bounds__(1024) mesh_scan_kernel(int32_t* __restrict__ b
       lc->noVisibleEntries, [&](int i) { return blockTriangles[i]; }, [&](int i, unsigned long long before) { blockTriangles[i] = (int32_t)(uint32_t)before; });
   if (threadIdx.x == 0) store_triangle_totals(totals, generated, maxTriangles);
 }
-
-static void free_mesh(itm_mesh* m) {
-  if (!m) return;
-  delete m;
-}
-
-static int upload_tables() { return upload_case_table<struct HashMesherTable>(HIP_SYMBOL(d_triangleCases)); }
 
 }  // namespace itm
 
@@ -165,12 +104,12 @@ int itm_mesh_create(const itm_scene* s, uint32_t maxTriangles, itm_mesh** out) {
   if (e == hipSuccess && hash) e = m->chunkCount.alloc((size_t)s->numChunks);
   if (e == hipSuccess && hash) e = m->listCounters.alloc(1);
   if (e == hipSuccess) e = hipMemset(m->triangles, 0, (size_t)m->maxTriangles * 36);   // MemoryBlock storage starts zeroed
-  if (e != hipSuccess) { free_mesh(m); return hip_fail(e, "mesh buffers", __FILE__, __LINE__); }
+  if (e != hipSuccess) { delete m; return hip_fail(e, "mesh buffers", __FILE__, __LINE__); }
   *out = m;
   return ITM_OK;
 }
 
-int itm_mesh_destroy(itm_mesh* m) { free_mesh(m); return ITM_OK; }
+int itm_mesh_destroy(itm_mesh* m) { delete m; return ITM_OK; }
 
 int itm_mesh_scene(const itm_scene* s, itm_mesh* m, itm_stream stream) {
   if (!s || !m) return set_error(ITM_ERR_INVALID, "null argument");
@@ -184,11 +123,10 @@ int itm_mesh_scene(const itm_scene* s, itm_mesh* m, itm_stream stream) {
   ITM_HIP(hipMemsetAsync(m->triangles, 0, (size_t)m->maxTriangles * 36, st));
   ITM_HIP(hipMemsetAsync(m->totals, 0, 8, st));
   if (s->cfg.indexType != ITM_INDEX_HASH) return ITM_OK;       // ITMPlainVoxelArray: empty in the reference
-  int rc = upload_tables();
-  if (rc) return rc;
   mesh_flag_kernel<<<s->numChunks, 256, 0, st>>>(s->hash, s->noTotalEntries, m->flags, m->chunkCount);
-  if ((rc = launch_ordered_compaction(m->flags.get(), m->chunkCount, s->numChunks, s->noTotalEntries, m->slots, m->capBlocks, &m->listCounters->rawVisibleCount,
-                                      &m->listCounters->noVisibleEntries, st))) return rc;
+  int rc = launch_ordered_compaction(m->flags.get(), m->chunkCount, s->numChunks, s->noTotalEntries, m->slots, m->capBlocks, &m->listCounters->rawVisibleCount,
+                                      &m->listCounters->noVisibleEntries, st);
+  if (rc) return rc;
   const VolumeView vol = make_volume(s);
   const int grid = 256 * 4;
   rc = dispatch_voxel(s->cfg.voxelType, [&](auto vx) {

@@ -3,7 +3,7 @@
 // in the header is the specification and tests/pose_quality_terms.py its restatement.
 //
 // Reads restated (every value through the functions the ray cast and the scene queries use):
-//   readFromSDF_float_interpolated / _uninterpolated   DeviceAgnostic/ITMRepresentationAccess.h:144-185   (raycast_device.h: Corners)
+//   readFromSDF_float_interpolated / _uninterpolated   DeviceAgnostic/ITMRepresentationAccess.h:144-185   (volume_device.h: Corners)
 //   readVoxel: an absent voxel reads TVoxel()          :85-142                                            (locate_voxel)
 //
 // MI355X design.  ONE launch per evaluation: a lane back-projects its pixel, transforms it, gathers the trilinear cell and the nearest
@@ -24,8 +24,7 @@
 
 #include "itm_internal.h"
 #include "gh_reduce.h"
-#include "raycast_device.h"
-#include "shading_device.h"
+#include "volume_device.h"
 
 namespace itm {
 
@@ -187,18 +186,12 @@ int itm_pose_quality_evaluate(itm_pose_quality_handle* q, const itm_scene* s, co
   const long long groups = (units + kGHWaves - 1) / kGHWaves;
   const int grid = (int)(groups < kGHGroups ? groups : kGHGroups);
   const VolumeView vol = make_volume(s);
-  const bool dense = s->cfg.indexType != ITM_INDEX_HASH;
   const unsigned int seq = q->ch.begin();
   GHBlockRecord* rec = q->ch.rec.device();
-  const int rc = dispatch_voxel(s->cfg.voxelType, [&](auto vx) {
+  const int rc = dispatch_volume(s, [&](auto vx, auto dense) {
     using VX = decltype(vx);
-    if (dense) {
-      if (tiles) pose_quality_kernel<VX, true, true><<<grid, kGHThreads, 0, st>>>(vol, view->depth, p, residuals_dev, rec, seq);
-      else pose_quality_kernel<VX, true, false><<<grid, kGHThreads, 0, st>>>(vol, view->depth, p, residuals_dev, rec, seq);
-    } else {
-      if (tiles) pose_quality_kernel<VX, false, true><<<grid, kGHThreads, 0, st>>>(vol, view->depth, p, residuals_dev, rec, seq);
-      else pose_quality_kernel<VX, false, false><<<grid, kGHThreads, 0, st>>>(vol, view->depth, p, residuals_dev, rec, seq);
-    }
+    if (tiles) pose_quality_kernel<VX, dense.value, true><<<grid, kGHThreads, 0, st>>>(vol, view->depth, p, residuals_dev, rec, seq);
+    else pose_quality_kernel<VX, dense.value, false><<<grid, kGHThreads, 0, st>>>(vol, view->depth, p, residuals_dev, rec, seq);
     return ITM_OK;
   });
   if (rc) return rc;

@@ -2,7 +2,7 @@
 // itm_scene_cast_rays): the reads the engines make per pixel, with a work item that is not a pixel.
 //
 // Reference behaviour restated (every value through the functions the renders and the mesh attributes already use):
-//   readFromSDF_float_uninterpolated / _interpolated  DeviceAgnostic/ITMRepresentationAccess.h:144-185   (raycast_device.h)
+//   readFromSDF_float_uninterpolated / _interpolated  DeviceAgnostic/ITMRepresentationAccess.h:144-185   (volume_device.h)
 //   readFromSDF_color4u_interpolated                  :187-222                                           (sample_device.h: colour_from)
 //   computeSingleNormalFromSDF                        :224-337                                           (sample_device.h: gradient_axis)
 //   readVoxel: an absent voxel reads TVoxel()         :85-142
@@ -19,8 +19,8 @@
 // loads are issued back to back from addresses that are always valid, and only then is the first value used.  The colours' eight
 // full-voxel loads go through the same resolved blocks.  A lane whose point is invalid samples position (0, 0, 0) and drops the values.
 #include "itm_internal.h"
+#include "raycast_device.h"
 #include "sample_device.h"
-#include "shading_device.h"
 
 namespace itm {
 
@@ -379,13 +379,10 @@ int itm_scene_query_points(const itm_scene* s, const float* points_dev, uint32_t
   if (o.colour) work |= kColour;
   hipStream_t st = as_stream(stream);
   const VolumeView vol = make_volume(s);
-  const bool dense = s->cfg.indexType != ITM_INDEX_HASH;
   const uint32_t groups = (n + 255u) / 256u;
   const int grid = (int)(groups < 2048u ? groups : 2048u);
-  const int rc = dispatch_voxel(s->cfg.voxelType, [&](auto vx) {
-    using VX = decltype(vx);
-    if (dense) launch_points<VX, true>(work, grid, st, vol, points_dev, n, s->prm.voxelSize, units == ITM_QUERY_METRES, o);
-    else launch_points<VX, false>(work, grid, st, vol, points_dev, n, s->prm.voxelSize, units == ITM_QUERY_METRES, o);
+  const int rc = dispatch_volume(s, [&](auto vx, auto dense) {
+    launch_points<decltype(vx), dense.value>(work, grid, st, vol, points_dev, n, s->prm.voxelSize, units == ITM_QUERY_METRES, o);
     return ITM_OK;
   });
   if (rc) return rc;
@@ -402,13 +399,10 @@ int itm_scene_cast_rays(const itm_scene* s, const float* rays_dev, uint32_t n, f
   hipStream_t st = as_stream(stream);
   const VolumeView vol = make_volume(s);
   const float oneOverVoxel = 1.0f / s->prm.voxelSize, stepScale = s->prm.mu * oneOverVoxel;      // as make_ray_params / march_ray form them
-  const bool dense = s->cfg.indexType != ITM_INDEX_HASH;
   const uint32_t groups = (n + 255u) / 256u;
   const int grid = (int)(groups < 2048u ? groups : 2048u);
-  const int rc = dispatch_voxel(s->cfg.voxelType, [&](auto vx) {
-    using VX = decltype(vx);
-    if (dense) cast_rays_kernel<VX, true><<<grid, 256, 0, st>>>(vol, rays_dev, n, oneOverVoxel, stepScale, (float4*)hits_dev);
-    else cast_rays_kernel<VX, false><<<grid, 256, 0, st>>>(vol, rays_dev, n, oneOverVoxel, stepScale, (float4*)hits_dev);
+  const int rc = dispatch_volume(s, [&](auto vx, auto dense) {
+    cast_rays_kernel<decltype(vx), dense.value><<<grid, 256, 0, st>>>(vol, rays_dev, n, oneOverVoxel, stepScale, (float4*)hits_dev);
     return ITM_OK;
   });
   if (rc) return rc;

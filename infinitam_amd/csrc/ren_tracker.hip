@@ -7,7 +7,7 @@
 //   ITMRenTracker::TrackCamera / ComputeSingleStep / GetMFromParam                         Engine/ITMRenTracker.cpp (host loop: ren_solver.h)
 //
 // Device part: one launch unprojects the depth image (level 0 only: the reference's level 1 is never read); one launch per
-// evaluation, one lane per point, reads the scene through the ray cast's voxel access (raycast_device.h: sdf mirror, block directory,
+// evaluation, one lane per point, reads the scene through the shared voxel access (volume_device.h: sdf mirror, block directory,
 // table walk, dense array -- the same values on every path) and computes the energy and -- in the same pass -- the Jacobian terms with
 // the reference's float operations (no contraction: the valid count is exact), reduced with the fixed-order double tree of
 // gh_reduce.h.
@@ -19,8 +19,7 @@
 
 #include "itm_internal.h"
 #include "gh_reduce.h"
-#include "raycast_device.h"
-#include "shading_device.h"
+#include "volume_device.h"
 #include "ren_solver.h"
 #include "se3.h"
 
@@ -155,17 +154,11 @@ static int ren_evaluate(itm_ren_tracker* t, const itm_scene* s, const float invM
   p.oneOverVoxel = 1.0f / s->prm.voxelSize;
   p.n = t->w * t->h;
   const VolumeView vol = make_volume(s);
-  const bool dense = s->cfg.indexType == ITM_INDEX_DENSE;
   const unsigned int seq = t->ch.begin();
-  const int rc = dispatch_voxel(s->cfg.voxelType, [&](auto vx) {
+  const int rc = dispatch_volume(s, [&](auto vx, auto dense) {
     using VX = decltype(vx);
-    if (dense) {
-      if (gh) ren_eval_kernel<VX, true, true><<<kGHGroups, kGHThreads, 0, st>>>(vol, t->points, p, t->ch.rec.device(), seq);
-      else ren_eval_kernel<VX, true, false><<<kGHGroups, kGHThreads, 0, st>>>(vol, t->points, p, t->ch.rec.device(), seq);
-    } else {
-      if (gh) ren_eval_kernel<VX, false, true><<<kGHGroups, kGHThreads, 0, st>>>(vol, t->points, p, t->ch.rec.device(), seq);
-      else ren_eval_kernel<VX, false, false><<<kGHGroups, kGHThreads, 0, st>>>(vol, t->points, p, t->ch.rec.device(), seq);
-    }
+    if (gh) ren_eval_kernel<VX, dense.value, true><<<kGHGroups, kGHThreads, 0, st>>>(vol, t->points, p, t->ch.rec.device(), seq);
+    else ren_eval_kernel<VX, dense.value, false><<<kGHGroups, kGHThreads, 0, st>>>(vol, t->points, p, t->ch.rec.device(), seq);
     return ITM_OK;
   });
   if (rc) return rc;

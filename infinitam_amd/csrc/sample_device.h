@@ -1,5 +1,6 @@
-// sample_device.h -- the reference's per-point samplers over ANY source of voxel values: the callers fetch the neighbourhood their own
-// way (LDS planes of a block: mesh_attributes.hip; one gather per query point: query.hip) and hand it over as a functor.
+// sample_device.h -- the reference's per-point samplers over ANY source of voxel values, the only statement of their arithmetic: the
+// callers fetch the neighbourhood their own way (the volume voxel by voxel: shading_device.h; LDS planes of a block: mesh_attributes.hip;
+// one gather per query point: query.hip) and hand it over as a functor.
 //
 // Reference behaviour restated:
 //   computeSingleNormalFromSDF            DeviceAgnostic/ITMRepresentationAccess.h:224-337
@@ -11,8 +12,11 @@
 
 namespace itm {
 
-// sdf_gradient (shading_device.h) over any source of raw sdf values: `raw(dx, dy, dz)` is the voxel at floor(p) + (dx, dy, dz).
-// The products and sums are gradient_component's, term for term.
+// One component of the sdf gradient at a fractional position over any source of raw sdf values: `raw(dx, dy, dz)` is the voxel at
+// floor(p) + (dx, dy, dz).  Along AXIS the volume is sampled on the four integer planes k = -1, 0, 1, 2 around the position, each plane
+// blended bilinearly over the other two axes (u, v: the remaining axes in x < y < z order); the component is the difference between the
+// linear blends of planes (1, 2) and of planes (0, -1).  The products and sums are the reference's, term for term:
+//   plane = s00 (1-fu)(1-fv) + s10 fu (1-fv) + s01 (1-fu) fv + s11 fu fv,   lower = plane0 fa + plane-1 (1-fa),   upper = plane1 (1-fa) + plane2 fa
 template <class VX, int AXIS, class S>
 __device__ inline float gradient_axis(S&& raw, float fa, float fu, float fv) {
   auto sample = [&](int k, int u, int v) {
@@ -30,7 +34,8 @@ __device__ inline float gradient_axis(S&& raw, float fa, float fu, float fv) {
   return VX::to_float(plane[2] * ga + plane[3] * fa - lower);
 }
 
-// colour_at (shading_device.h) over any source of packed colours (r | g << 8 | b << 16; 0 where no voxel is stored)
+// The colour at a fractional position (cx, cy, cz: its fractions) over any source of packed colours: `packed(dx, dy, dz)` is the voxel at
+// floor(p) + (dx, dy, dz) as r | g << 8 | b << 16, 0 where no voxel is stored.  Returns (r, g, b) / 255 and w = 1.
 template <class C>
 __device__ inline float4 colour_from(C&& packed, float cx, float cy, float cz) {
   float r[3] = {0.0f, 0.0f, 0.0f};

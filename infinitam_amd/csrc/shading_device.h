@@ -9,21 +9,9 @@
 
 #include "itm_internal.h"
 #include "raycast_device.h"
+#include "sample_device.h"
 
 namespace itm {
-
-static inline VolumeView make_volume(const itm_scene* s) {
-  VolumeView v;
-  v.hash = s->hash; v.vba = s->vba; v.headBits = s->headBits;
-  v.dirPtr = g_debug_no_directory ? nullptr : s->dirPtr;
-  v.sdfMirror = (g_debug_no_directory || g_debug_no_sdf_mirror) ? nullptr : s->sdfMirror;
-  v.pageTable = s->org.mTable;
-  v.org = s->org;
-  v.mask = (uint32_t)s->cfg.bucketNum - 1u; v.bucketNum = s->cfg.bucketNum;
-  v.sx = s->cfg.denseSize[0]; v.sy = s->cfg.denseSize[1]; v.sz = s->cfg.denseSize[2];
-  v.ox = s->cfg.denseOffset[0]; v.oy = s->cfg.denseOffset[1]; v.oz = s->cfg.denseOffset[2];
-  return v;
-}
 
 static inline void make_ray_params(const itm_scene* s, const float* invM, const float* intr, int W, int H, RayParams& p) {
   memcpy(p.invM.m, invM, 64);
@@ -83,36 +71,18 @@ __device__ inline float raw_at(const VolumeView& vol, int x, int y, int z) {
   return read_raw_sdf<VX, DENSE>(vol, x, y, z, f, c);
 }
 
-// One component of the sdf gradient at a fractional position (computeSingleNormalFromSDF, DeviceAgnostic/ITMRepresentationAccess.h:
-// 187-252): along AXIS the volume is sampled on the four integer planes k = -1, 0, 1, 2 around the position, each plane blended
-// bilinearly over the other two axes (u, v: the remaining axes in x < y < z order); the component is the difference between the
-// linear blends of planes (1, 2) and of planes (0, -1).  The products and sums are the reference's, term for term:
-//   plane = s00 (1-fu)(1-fv) + s10 fu (1-fv) + s01 (1-fu) fv + s11 fu fv,   lower = plane0 fa + plane-1 (1-fa),   upper = plane1 (1-fa) + plane2 fa
-template <class VX, bool DENSE, int AXIS>
-__device__ inline float gradient_component(const VolumeView& vol, int ix, int iy, int iz, float fa, float fu, float fv) {
-  auto sample = [&](int k, int u, int v) {
-    const int dx = (AXIS == 0) ? k : u;
-    const int dy = (AXIS == 1) ? k : (AXIS == 0 ? u : v);
-    const int dz = (AXIS == 2) ? k : v;
-    return raw_at<VX, DENSE>(vol, ix + dx, iy + dy, iz + dz);
-  };
-  const float gu = 1.0f - fu, gv = 1.0f - fv, ga = 1.0f - fa;
-  float plane[4];
-#pragma unroll
-  for (int k = -1; k <= 2; ++k)
-    plane[k + 1] = sample(k, 0, 0) * gu * gv + sample(k, 1, 0) * fu * gv + sample(k, 0, 1) * gu * fv + sample(k, 1, 1) * fu * fv;
-  const float lower = plane[1] * fa + plane[0] * ga;
-  return VX::to_float(plane[2] * ga + plane[3] * fa - lower);
-}
-
+// computeSingleNormalFromSDF at a point of the volume: gradient_axis (sample_device.h) over the uncached reads -- a fresh BlockCache per
+// voxel (raw_at), as the reference's readVoxel overload there.  (The functor captures by reference: by value the compiler hoists the
+// view's loads over the cover tests of the hash path, 160 registers instead of 98 and the mesh attributes a third slower)
 template <class VX, bool DENSE>
 __device__ inline void sdf_gradient(const VolumeView& vol, float px, float py, float pz, float& gx, float& gy, float& gz) {
   const float bx = floorf(px), by = floorf(py), bz = floorf(pz);
   const float fx = px - bx, fy = py - by, fz = pz - bz;
   const int ix = (int)bx, iy = (int)by, iz = (int)bz;
-  gx = gradient_component<VX, DENSE, 0>(vol, ix, iy, iz, fx, fy, fz);
-  gy = gradient_component<VX, DENSE, 1>(vol, ix, iy, iz, fy, fx, fz);
-  gz = gradient_component<VX, DENSE, 2>(vol, ix, iy, iz, fz, fx, fy);
+  auto raw = [&](int dx, int dy, int dz) { return raw_at<VX, DENSE>(vol, ix + dx, iy + dy, iz + dz); };
+  gx = gradient_axis<VX, 0>(raw, fx, fy, fz);
+  gy = gradient_axis<VX, 1>(raw, fy, fx, fz);
+  gz = gradient_axis<VX, 2>(raw, fz, fx, fy);
 }
 
 template <class VX, bool DENSE>
@@ -125,7 +95,8 @@ __device__ inline bool normal_from_sdf(const VolumeView& vol, float px, float py
   return angle > 0.0f;
 }
 
-// readFromSDF_color4u_interpolated; returns (r,g,b)/255 and w = 1
+// readFromSDF_color4u_interpolated at a point of the volume; returns (r,g,b)/255 and w = 1: colour_from (sample_device.h) over the voxels,
+// one block cache carried across the eight taps
 template <class VX, bool DENSE>
 __device__ inline float4 colour_at(const VolumeView& vol, float px, float py, float pz) {
   if constexpr (!VX::kColor) {
@@ -133,26 +104,15 @@ __device__ inline float4 colour_at(const VolumeView& vol, float px, float py, fl
   } else {
     BlockCache cache;
     const float flx = floorf(px), fly = floorf(py), flz = floorf(pz);
-    const float cx = px - flx, cy = py - fly, cz = pz - flz;
     const int ix = (int)flx, iy = (int)fly, iz = (int)flz;
-    float r[3] = {0.0f, 0.0f, 0.0f};
-    auto add = [&](int dx, int dy, int dz, float wgt) {
+    auto packed = [&](int dx, int dy, int dz) {
       const long long a = locate_voxel<DENSE>(vol, ix + dx, iy + dy, iz + dz, cache);
       int c[3] = {0, 0, 0}, wc = 0;
       if (a >= 0) VX::get_color(VX::load(vol.vba, (size_t)a), c, wc);
-      r[0] += wgt * (float)c[0]; r[1] += wgt * (float)c[1]; r[2] += wgt * (float)c[2];
+      return (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16);
     };
-    add(0, 0, 0, (1.0f - cx) * (1.0f - cy) * (1.0f - cz));
-    add(1, 0, 0, (cx) * (1.0f - cy) * (1.0f - cz));
-    add(0, 1, 0, (1.0f - cx) * (cy) * (1.0f - cz));
-    add(1, 1, 0, (cx) * (cy) * (1.0f - cz));
-    add(0, 0, 1, (1.0f - cx) * (1.0f - cy) * cz);
-    add(1, 0, 1, (cx) * (1.0f - cy) * cz);
-    add(0, 1, 1, (1.0f - cx) * (cy)*cz);
-    add(1, 1, 1, (cx) * (cy)*cz);
-    return make_float4(r[0] / 255.0f, r[1] / 255.0f, r[2] / 255.0f, 255.0f / 255.0f);
+    return colour_from(packed, px - flx, py - fly, pz - flz);
   }
 }
-
 
 }  // namespace itm

@@ -617,14 +617,11 @@ int launch_render_image(const itm_scene* s, const float* M, const float* intr, i
   RayParams p; make_ray_params(s, invM, intr, rs->w, rs->h, p);
   const VolumeView vol = make_volume(s);
   const dim3 grid((rs->w + 15) / 16, (rs->h + 15) / 16);
-  const bool dense = s->cfg.indexType == ITM_INDEX_DENSE;
   const bool colour = voxel_has_colour(s->cfg.voxelType);
   if (type == ITM_RENDER_COLOUR_FROM_VOLUME && !colour) type = ITM_RENDER_SHADED_GREYSCALE;  // _CPU.cpp:205-206
   if (type != ITM_RENDER_COLOUR_FROM_VOLUME && type != ITM_RENDER_COLOUR_FROM_NORMAL) type = ITM_RENDER_SHADED_GREYSCALE;
-  rc = dispatch_voxel(s->cfg.voxelType, [&](auto vx) {
-    using VX = decltype(vx);
-    if (dense) render_image_kernel<VX, true><<<grid, 256, 0, st>>>(vol, rs->raycast, out, type, p);
-    else render_image_kernel<VX, false><<<grid, 256, 0, st>>>(vol, rs->raycast, out, type, p);
+  rc = dispatch_volume(s, [&](auto vx, auto dense) {
+    render_image_kernel<decltype(vx), dense.value><<<grid, 256, 0, st>>>(vol, rs->raycast, out, type, p);
     return ITM_OK;
   });
   if (rc) return rc;

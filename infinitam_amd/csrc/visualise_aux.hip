@@ -103,11 +103,8 @@ int launch_forward_render(const itm_scene* s, const itm_view* v, itm_render_stat
   // the flagged pixel indices in raster order (ordered compaction; the list has room for every pixel)
   int rc = launch_ordered_compaction(rs->pixScratch.get(), rs->pixChunk, nChunks, P, rs->missing, P, (int32_t*)nullptr, &rs->counters->noFwdProjMissingPoints, st);
   if (rc) return rc;
-  const bool dense = s->cfg.indexType == ITM_INDEX_DENSE;
-  rc = dispatch_voxel(s->cfg.voxelType, [&](auto vx) {
-    using VX = decltype(vx);
-    if (dense) fwd_raycast_missing_kernel<VX, true><<<1024, 256, 0, st>>>(vol, rs->missing, rs->counters, rs->range, rs->fwdProj, rp);
-    else fwd_raycast_missing_kernel<VX, false><<<1024, 256, 0, st>>>(vol, rs->missing, rs->counters, rs->range, rs->fwdProj, rp);
+  rc = dispatch_volume(s, [&](auto vx, auto dense) {
+    fwd_raycast_missing_kernel<decltype(vx), dense.value><<<1024, 256, 0, st>>>(vol, rs->missing, rs->counters, rs->range, rs->fwdProj, rp);
     return ITM_OK;
   });
   if (rc) return rc;
@@ -164,17 +161,11 @@ int launch_point_cloud(const itm_scene* s, const itm_view* v, itm_render_state* 
   RayParams rp; make_ray_params(s, invM, v->intr_rgb, W, H, rp);
   const VolumeView vol = make_volume(s);
   const int blocks = (P + 255) / 256;
-  const bool dense = s->cfg.indexType == ITM_INDEX_DENSE;
   fwd_clear_kernel<<<blocks, 256, 0, st>>>(rs->pixScratch, rs->pixChunk, P, nChunks);
-  rc = dispatch_voxel(s->cfg.voxelType, [&](auto vx) {
+  rc = dispatch_volume(s, [&](auto vx, auto dense) {
     using VX = decltype(vx);
-    if (dense) {
-      pc_flag_kernel<VX, true><<<blocks, 256, 0, st>>>(vol, rs->raycast, rs->image, rs->pixScratch, rs->pixChunk, skip ? 1 : 0, rp);
-      pc_write_kernel<VX, true><<<nChunks, 256, 0, st>>>(vol, rs->raycast, rs->pixScratch, rs->pixChunk, nChunks, loc, col, rs->counters, rp);
-    } else {
-      pc_flag_kernel<VX, false><<<blocks, 256, 0, st>>>(vol, rs->raycast, rs->image, rs->pixScratch, rs->pixChunk, skip ? 1 : 0, rp);
-      pc_write_kernel<VX, false><<<nChunks, 256, 0, st>>>(vol, rs->raycast, rs->pixScratch, rs->pixChunk, nChunks, loc, col, rs->counters, rp);
-    }
+    pc_flag_kernel<VX, dense.value><<<blocks, 256, 0, st>>>(vol, rs->raycast, rs->image, rs->pixScratch, rs->pixChunk, skip ? 1 : 0, rp);
+    pc_write_kernel<VX, dense.value><<<nChunks, 256, 0, st>>>(vol, rs->raycast, rs->pixScratch, rs->pixChunk, nChunks, loc, col, rs->counters, rp);
     return ITM_OK;
   });
   if (rc) return rc;

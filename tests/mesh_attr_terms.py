@@ -2,7 +2,7 @@
 
   sample position   p = vertex / voxelSize                                     three IEEE float divisions
   gradient          computeSingleNormalFromSDF(p)      DeviceAgnostic/ITMRepresentationAccess.h:224-337
-  normal            g * (1 / sqrt(g.g)), (0, 0, 0) where that is not finite    (normal_from_sdf, shading_device.h)
+  normal            g * (1 / sqrt(g.g)), (0, 0, 0) where that is not finite    (store_normal, sample_device.h)
   colour            readFromSDF_color4u_interpolated(p)  :187-222, bytes as drawPixelColour: (uchar)(c * 255.0f), alpha 255
 
 fed from downloaded scene buffers (hash entries + voxel blocks).  Every product and sum is rounded to float32 on its own, in the

@@ -21,7 +21,7 @@ import mesh_attr_terms as MT
 import mesh_dense_cases as MD
 import mesh_index_terms as MI
 from infinitam_amd import capi
-from infinitam_amd.capi import BUF_VOXEL_BLOCKS, MESH_COLOURS, MESH_NORMALS, Mesh
+from infinitam_amd.capi import BUF_HASH_ENTRIES, BUF_VOXEL_BLOCKS, MESH_COLOURS, MESH_NORMALS, Mesh
 
 F = np.float32
 COLOUR = (capi.VOXEL_S_RGB, capi.VOXEL_F_RGB)
@@ -212,12 +212,7 @@ def test_hip_scan_over_several_sweeps(hip):
     m2.MeshVolume()
     assert m2.info() == (cap - 1, cap)
     assert_triangles(m2.triangles(), want[:cap - 1], "three sweeps, full buffer")
-    last = np.zeros((1, 3, 3), F)
-    dev = capi._P()
-    s.be.check(s.be.fn["mesh_info"](capi._P(m2.h), None, None, C.byref(dev), None), "mesh_info")
-    s.be.check(s.be.fn["memcpy_d2h"](last.ctypes.data_as(capi._P), capi._P(dev.value + (cap - 1) * 36), 36, None), "memcpy_d2h")
-    s.be.sync()
-    assert np.array_equal(bits(last[0]), bits(want[-1]))
+    assert np.array_equal(bits(last_slot(s, m2, cap)), bits(want[-1]))
 
 
 @pytest.mark.gpu
@@ -234,6 +229,56 @@ def test_hip_full_buffer(hip):
     m2.MeshVolume()
     assert m2.info() == (n_all, n_all + 1)
     assert_triangles(m2.triangles(), want, "max_triangles = n_all + 1")
+
+
+def last_slot(s, m, cap):
+    """slot cap - 1 of a mesh's buffer: past the counted triangles, so read from the device"""
+    last = np.zeros((1, 3, 3), F)
+    dev = capi._P()
+    s.be.check(s.be.fn["mesh_info"](capi._P(m.h), None, None, C.byref(dev), None), "mesh_info")
+    s.be.check(s.be.fn["memcpy_d2h"](last.ctypes.data_as(capi._P), capi._P(dev.value + (cap - 1) * 36), 36, None), "memcpy_d2h")
+    s.be.sync()
+    return last[0]
+
+
+def sorted_rows(tri):
+    rows = bits(tri).reshape(len(tri), 9)
+    return rows[np.lexsort(rows.T[::-1])]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("vt", [capi.VOXEL_S, capi.VOXEL_F_RGB])
+def test_hip_dense_and_hash_meshers_emit_the_same_cells(hip, vt):
+    """the ragged volume as a dense scene and as its equivalent hash scene: both meshers go through one cell function, handed positions
+    and samples their own way (clipped bricks, a non-zero offset, corners in a neighbouring block) -- the same triangles bit for bit as
+    multisets, and with a full buffer each keeps ITS last generated triangle in the last slot"""
+    v, want, table, blocks = expected_ragged(vt)
+    n = want.shape[0]
+    assert n > 100
+    key = ("ragged hash order", vt)
+    if key not in _expected:
+        _expected[key] = MD.oracle_mesh(table, blocks, vt, MD.RAGGED_VOXEL_SIZE, n + 2)
+    want_hash = _expected[key]                                           # table-slot order: the hash mesher's
+    assert want_hash.shape == want.shape and not np.array_equal(bits(want_hash), bits(want))
+    d = upload_dense(hip, v, MD.RAGGED_SIZE, MD.RAGGED_OFFSET, vt, MD.RAGGED_VOXEL_SIZE)
+    h = hip.create_scene(vt, capi.INDEX_HASH, capi.default_params(voxelSize=MD.RAGGED_VOXEL_SIZE), localBlockNum=max(len(blocks) // 512 + 1, 16))
+    h.reco.ResetScene()
+    h.upload(BUF_HASH_ENTRIES, table)
+    h.upload(BUF_VOXEL_BLOCKS, blocks)
+    md, mh = Mesh(d, n + 2), Mesh(h, n + 2)
+    md.MeshVolume(); mh.MeshScene()
+    assert md.info() == (n, n + 2) == mh.info()
+    td, th = md.triangles(), mh.triangles()
+    assert np.array_equal(sorted_rows(td), sorted_rows(th))
+    assert_triangles(td, want, "dense order"); assert_triangles(th, want_hash, "hash order")
+    # three too small: cap - 1 counted triangles, the last slot keeps the mesher's own last triangle (the two orders end differently)
+    cap = n - 3
+    assert not np.array_equal(bits(want[-1]), bits(want_hash[-1]))
+    for s, m, mesh, expected, what in ((d, Mesh(d, cap), "MeshVolume", want, "dense"), (h, Mesh(h, cap), "MeshScene", want_hash, "hash")):
+        getattr(m, mesh)()
+        assert m.info() == (cap - 1, cap)
+        assert_triangles(m.triangles(), expected[:cap - 1], what + ", full buffer")
+        assert np.array_equal(bits(last_slot(s, m, cap)), bits(expected[-1])), what + ": last slot"
 
 
 @pytest.mark.gpu
