@@ -807,6 +807,59 @@ typedef struct itm_query_out {      /* device pointers, NULL = not wanted */
 int ITM_FN(scene_query_points)(const itm_scene* scene, const float* points_dev, uint32_t n, int units, const itm_query_out* out, itm_stream stream);
 int ITM_FN(scene_cast_rays)(const itm_scene* scene, const float* rays_dev, uint32_t n, float* hits_dev, itm_stream stream);
 
+/* ---- distance field: Euclidean distance transform of a box of the volume ------------------------------------------------------------
+ * What a planner asks: how far is this voxel from the nearest surface, how far from space nobody has seen.  The TSDF answers within
+ * +-mu of a surface only; here every cell of a box gets the exact Euclidean distance, in voxels squared, to the nearest SITE of the box.
+ * The reference has no counterpart.  Read-only on the scene; DEVICE pointers; launches on `stream`, nothing is synchronised.
+ *
+ * Sequential definition.  The box has a first voxel o = origin (voxel units, any alignment, may be negative) and a size (nx, ny, nz).
+ * Cell (i, j, k) is voxel p = o + (i, j, k) and lies at linear index i + nx * (j + ny * k).
+ *  1. Classification, one byte per cell (`state`).  Voxels are read as readVoxel reads them (DeviceAgnostic/ITMRepresentationAccess.h:
+ *     85-142): an absent voxel is TVoxel().
+ *       ITM_ESDF_STORED    a voxel exists at p
+ *       ITM_ESDF_OBSERVED  stored and w_depth >= min_weight (min_weight >= 1)
+ *       ITM_ESDF_INSIDE    observed and SDF_valueToFloat(sdf) <= 0
+ *       ITM_ESDF_SITE      the cell is a site under one of the rules `sites` selects:
+ *         ITM_ESDF_SITE_SURFACE  p is observed and has a 6-neighbour q that is observed with INSIDE(q) != INSIDE(p).  Neighbours are
+ *                                read from the scene also where they lie outside the box: the classification of a sub-box is the crop
+ *                                of a larger box's classification
+ *         ITM_ESDF_SITE_UNKNOWN  p is not observed
+ *     `sites` has at least one of the two bits and no others.
+ *  2. Transform.  R = max_distance in voxels, 0 = unbounded.
+ *       dist2[c]    min over the sites s of the box of |c - s|^2 (int32); ITM_ESDF_NONE where that exceeds R^2 (R > 0) or the box holds
+ *                   no site
+ *       nearest[c]  linear index of the site that attains the minimum, the smallest such index among ties; -1 with ITM_ESDF_NONE
+ *     A separable transform meets this exactly: per axis, x then y then z, the candidates along the line taken in ascending order
+ *     with a strict `<`; along every axis the smaller position is the smaller linear index of the site it stands for.  A window of
+ *     +-R per axis loses nothing (a site within R has every axis offset within R) and every candidate is a real site.
+ *  3. distance[c] = voxelSize * sqrtf((float)dist2[c]), negated where the cell is INSIDE; +-INFINITY (same sign rule) with
+ *     ITM_ESDF_NONE.  dist2 < 2^24 at the allowed sizes, so the conversion is exact; sqrt and the product are IEEE, each rounded once.
+ * Limits, refused with ITM_ERR_INVALID before anything is launched: each of nx, ny, nz in [1, 1024]; nx * ny * nz <= 2^27;
+ * max_distance in [0, 1023]; every coordinate of the box with its one-voxel halo (o - 1 .. o + n) has |p| < 262136 (the limit of
+ * itm_scene_query_points: block coordinates stay short).  out->dist2 is required: it is also the passes' working storage.
+ *
+ * itm_scene_esdf classifies the box of the scene (recorded calls are launched first) and transforms it.  itm_esdf_transform is the
+ * scene-free half: it reads the SITE and INSIDE bits of a caller-supplied byte grid [nx * ny * nz], runs the same passes and ignores
+ * out->state. */
+#define ITM_ESDF_STORED 1
+#define ITM_ESDF_OBSERVED 2
+#define ITM_ESDF_INSIDE 4
+#define ITM_ESDF_SITE 8
+#define ITM_ESDF_SITE_SURFACE 1
+#define ITM_ESDF_SITE_UNKNOWN 2
+#define ITM_ESDF_NONE 0x7fffffff
+typedef struct itm_esdf_box { int32_t origin[3]; int32_t size[3]; } itm_esdf_box;
+typedef struct itm_esdf_out {      /* device pointers, [nx * ny * nz] each; NULL = not wanted, except dist2 */
+  int32_t* dist2;                  /* required: also the passes' working storage */
+  int32_t* nearest;
+  float* distance;
+  uint8_t* state;
+} itm_esdf_out;
+int ITM_FN(scene_esdf)(const itm_scene* scene, const itm_esdf_box* box, int sites, int min_weight, int max_distance, const itm_esdf_out* out,
+                       itm_stream stream);
+int ITM_FN(esdf_transform)(const uint8_t* state_dev, const int32_t size[3], int max_distance, float voxel_size, const itm_esdf_out* out,
+                           itm_stream stream);
+
 /* ---- keyframe relocaliser: "where have I seen this depth image before?" -------------------------------------------------------------
  * Randomised ferns over a small, smoothed depth image (Glocker et al., Real-Time RGB-D Camera Relocalization via Randomized Ferns
  * for Keyframe Encoding): a code of numFerns bytes per frame, a database of keyframe codes (device memory) with their poses (host),

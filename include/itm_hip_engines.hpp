@@ -330,6 +330,20 @@ class ITMSceneQueryEngine_HIP {
   }
 };
 
+// Distance field (itm_scene_esdf; no counterpart in the reference): the Euclidean distance transform of a box of the volume -- for
+// every cell the squared distance in voxels to the nearest site (surface crossing and / or unobserved voxel), which site that is, the
+// signed metric distance and the classification byte.  Device pointers; launches on `stream`, nothing is synchronised.
+template <class TVoxel, class TIndex>
+class ITMDistanceFieldEngine_HIP {
+ public:
+  itm_stream stream = nullptr;
+  // box: first voxel and size in voxels; out: dist2 is required, the others NULL = not wanted; maxDistance in voxels, 0 = unbounded
+  void Compute(const ITMScene<TVoxel, TIndex>* scene, const itm_esdf_box& box, const itm_esdf_out& out, int sites = ITM_ESDF_SITE_SURFACE, int minWeight = 1,
+               int maxDistance = 0) const {
+    check(itm_scene_esdf(scene->handle, &box, sites, minWeight, maxDistance, &out, stream), "DistanceField");
+  }
+};
+
 template <class TVoxel, class TIndex>
 class ITMDenseMapper_HIP {
   ITMSceneReconstructionEngine_HIP<TVoxel, TIndex> reco;
@@ -842,6 +856,10 @@ class ITMMainEngine_HIP {
     ITMSceneQueryEngine_HIP<TVoxel, TIndex>().QueryPoints(&scene, points, n, out, units);
   }
   void CastRays(const float* rays, uint32_t n, float* hits) const { ITMSceneQueryEngine_HIP<TVoxel, TIndex>().CastRays(&scene, rays, n, hits); }
+  // The distance transform of a box of the fused volume (ITMDistanceFieldEngine_HIP; device pointers)
+  void DistanceField(const itm_esdf_box& box, const itm_esdf_out& out, int sites = ITM_ESDF_SITE_SURFACE, int minWeight = 1, int maxDistance = 0) const {
+    ITMDistanceFieldEngine_HIP<TVoxel, TIndex>().Compute(&scene, box, out, sites, minWeight, maxDistance);
+  }
   ITMRenderState* GetRenderState() { return renderState_live; }
   const ITMVisualisationEngine_HIP<TVoxel, TIndex>* GetVisualisationEngine() const { return &visualisationEngine; }
   const ITMViewBuilder_HIP* GetViewBuilder() const { return viewBuilder; }

@@ -184,6 +184,41 @@ QUERY_OUTPUTS = {"sdf": (np.float32, ()), "sdf_nearest": (np.float32, ()), "grad
                  "colour": (np.uint8, (4,)), "weight": (np.uint8, ()), "flags": (np.uint32, ())}
 
 
+class EsdfBox(C.Structure):
+    """itm_esdf_box (include/itm_hip.h, itm_scene_esdf): first voxel and size of the box, voxel units."""
+    _fields_ = [("origin", C.c_int32 * 3), ("size", C.c_int32 * 3)]
+
+
+class EsdfOut(C.Structure):
+    """itm_esdf_out: device pointers, NULL = not wanted, except dist2 (the passes' working storage)."""
+    _fields_ = [(n, C.c_void_p) for n in ("dist2", "nearest", "distance", "state")]
+
+
+ESDF_STORED, ESDF_OBSERVED, ESDF_INSIDE, ESDF_SITE = 1, 2, 4, 8
+ESDF_SITE_SURFACE, ESDF_SITE_UNKNOWN = 1, 2
+ESDF_NONE = 0x7fffffff
+ESDF_SITES = {"surface": ESDF_SITE_SURFACE, "unknown": ESDF_SITE_UNKNOWN}
+ESDF_OUTPUTS = {"dist2": np.int32, "nearest": np.int32, "distance": np.float32, "state": np.uint8}
+ESDF_MAX_SIDE, ESDF_MAX_CELLS = 1024, 1 << 27
+
+
+def _esdf_buffers(be, size, want):
+    """(EsdfOut, {name: DevBuffer}) for a grid of `size` = (nx, ny, nz): dist2 always, the others where wanted.  A size the library
+    will refuse gets one-byte buffers: it is refused before anything is written."""
+    unknown = [w for w in want if w not in ESDF_OUTPUTS]
+    if unknown:
+        raise ItmError(f"distance field: unknown outputs {unknown}")
+    nx, ny, nz = (int(v) for v in size)
+    ok = all(1 <= v <= ESDF_MAX_SIDE for v in (nx, ny, nz)) and nx * ny * nz <= ESDF_MAX_CELLS
+    n, shape = (nx * ny * nz, (nz, ny, nx)) if ok else (0, (0,))
+    bufs = {w: DevBuffer(be, n * np.dtype(ESDF_OUTPUTS[w]).itemsize, ESDF_OUTPUTS[w], shape)
+            for w in ESDF_OUTPUTS if w == "dist2" or w in want}
+    out = EsdfOut()
+    for w, b in bufs.items():
+        setattr(out, w, b.ptr)
+    return out, bufs
+
+
 class RelocConfig(C.Structure):
     """itm_reloc_config (include/itm_hip.h, the keyframe relocaliser)."""
     _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("levels", C.c_int32), ("blurRadius", C.c_int32), ("blurTaps", C.c_float * 9),
@@ -381,6 +416,9 @@ _HOST_IO_SIGS = {
     # scene queries at caller-supplied points / along caller-supplied rays (product only: the reference reads per pixel, inside its engines)
     "scene_query_points": (C.c_int, [_P, _P, C.c_uint32, C.c_int, C.POINTER(QueryOut), _P]),
     "scene_cast_rays": (C.c_int, [_P, _P, C.c_uint32, _P, _P]),
+    # distance field of a box of the volume and its scene-free transform (product only: the reference has no counterpart)
+    "scene_esdf": (C.c_int, [_P, C.POINTER(EsdfBox), C.c_int, C.c_int, C.c_int, C.POINTER(EsdfOut), _P]),
+    "esdf_transform": (C.c_int, [_P, C.POINTER(C.c_int32), C.c_int, C.c_float, C.POINTER(EsdfOut), _P]),
     # keyframe relocaliser (product only: the reference at this revision has none); the two defaults are host-only
     "reloc_default_config": (C.c_int, [C.c_int, C.c_int, C.POINTER(RelocConfig)]),
     "reloc_default_ferns": (C.c_int, [C.POINTER(RelocConfig), C.c_uint64, C.c_float, C.c_float, _P, _P]),
@@ -479,6 +517,26 @@ class Backend:
 
     def sync(self, stream=None):
         self.check(self.fn["stream_synchronize"](_P(stream)), "stream_synchronize")
+
+    def esdf_transform(self, state, max_distance=0, voxel_size=1.0, want=("dist2", "distance"), stream=None) -> dict:
+        """itm_esdf_transform: the distance transform of a caller's own byte grid `state` [nz, ny, nx] (its ESDF_SITE and ESDF_INSIDE
+        bits) -> the outputs named in `want` (ESDF_OUTPUTS without "state") as numpy arrays [nz, ny, nx].  Uploads, downloads and
+        synchronises `stream`."""
+        grid = np.ascontiguousarray(np.asarray(state, np.uint8))
+        if grid.ndim != 3:
+            raise ItmError("esdf_transform: state is a [nz, ny, nx] array")
+        if "state" in want:
+            raise ItmError("esdf_transform: state is the input")
+        size = (C.c_int32 * 3)(*grid.shape[::-1])
+        out, bufs = _esdf_buffers(self, grid.shape[::-1], want)
+        dev = self.to_backend(grid, stream) if grid.size else None
+        rc = self.fn["esdf_transform"](_P(dev.ptr if dev else None), size, int(max_distance), float(voxel_size), C.byref(out), _P(stream))
+        self.sync(stream)
+        res = {w: bufs[w].numpy(stream) for w in want} if rc == 0 else None
+        for b in list(bufs.values()) + ([dev] if dev else []):
+            b.close()
+        self.check(rc, "esdf_transform")
+        return res
 
     def create_scene(self, voxelType=VOXEL_S, indexType=INDEX_HASH, params: Optional[SceneParams] = None,
                      bucketNum=0, excessNum=0, localBlockNum=0, denseSize=(0, 0, 0), denseOffset=None,
@@ -711,6 +769,23 @@ class Scene:
         res = hits.numpy(stream) if rc == 0 else None
         dev_rays.close(); hits.close()
         self.be.check(rc, "scene_cast_rays")
+        return res
+
+    def distance_field(self, origin, size, sites=("surface",), min_weight=1, max_distance=0, want=("dist2", "distance", "state"), stream=None) -> dict:
+        """itm_scene_esdf: the Euclidean distance transform of the box with first voxel `origin` and `size` = (nx, ny, nz), voxel units.
+        sites: names of ESDF_SITES (or the mask itself); max_distance in voxels, 0 = unbounded.  Returns the outputs named in `want`
+        (ESDF_OUTPUTS) as numpy arrays [nz, ny, nx].  Downloads the outputs and synchronises `stream`."""
+        mask = sites if isinstance(sites, int) else sum({ESDF_SITES[s] for s in sites})
+        box = EsdfBox()
+        box.origin[:] = [int(v) for v in origin]
+        box.size[:] = [int(v) for v in size]
+        out, bufs = _esdf_buffers(self.be, size, want)
+        rc = self.be.fn["scene_esdf"](_P(self.h), C.byref(box), int(mask), int(min_weight), int(max_distance), C.byref(out), _P(stream))
+        self.be.sync(stream)
+        res = {w: bufs[w].numpy(stream) for w in want} if rc == 0 else None
+        for b in bufs.values():
+            b.close()
+        self.be.check(rc, "scene_esdf")
         return res
 
     def accel_info(self) -> dict:
