@@ -40,6 +40,7 @@ extern "C" {
 #define ITM_DEBUG_MESH_INDEX_WEAK_HASH 27        /* itm_mesh_index: the hash cut to 8 bits (256 start slots spread over the table, the last 64 slots before its end): probe chains hundreds of slots long and the wrap-around on small meshes */
 #define ITM_DEBUG_FAIL_ALLOCATION 28             /* n > 0: the n-th allocation the library attempts from now on (device or pinned memory) fails with out-of-memory before the runtime is called, then the key clears itself; 0 = off */
 #define ITM_DEBUG_POSE_QUALITY_ROWS 29            /* itm_pose_quality_evaluate: a wave covers 64 x 1 pixels of a row instead of an 8 x 8 tile (same counts and residual image; the sums are added in another order) */
+#define ITM_DEBUG_MESH_COMPONENTS_PER_LANE 30      /* itm_mesh_components: the statistics with one atomic per lane instead of one per wave segment (lanes of a wave that share a component aggregate first) */
 int ITM_FN(debug_set)(int key, int value);
 /* Everything the library allocates passes through one pair of functions (csrc/device_memory.h): out = {live allocations, live bytes,
  * allocations attempted since the library was loaded}, device and pinned memory together, process-wide.  Memory handed out by
@@ -70,7 +71,14 @@ int ITM_FN(debug_divide)(int mode, const float* a, const float* b, const float* 
  * flags, ascending, and its own pattern everywhere else, also in the guard words past cap.  counts = {total, min(total, cap)}. */
 #define ITM_DEBUG_ORDERED_GUARD 8
 int ITM_FN(debug_ordered_compact)(const void* flags_host, int elemBytes, int n, int cap, int32_t* ids_host, int32_t counts[2], itm_stream stream);
-
+/* The labelling of itm_mesh_components on a caller-supplied face array (the triangle buffer cannot be uploaded): faces_host holds
+ * noTriangles x 3 vertex indices < noVertices (an index >= noVertices: ITM_ERR_INVALID); the product's union / check / numbering / count
+ * kernels run on it.  vertexComponent_host receives noVertices numbers, components_host min(noComponents, capComponents) entries with
+ * the box left zero (it needs positions); a vertex no triangle names is a component of its own with 0 triangles.  *rounds = the union
+ * rounds taken.  All pointers are HOST memory; vertexComponent_host and components_host may be NULL. */
+int ITM_FN(debug_mesh_components)(const uint32_t* faces_host, uint32_t noTriangles, uint32_t noVertices, uint32_t* vertexComponent_host,
+                                  itm_mesh_component* components_host, uint32_t capComponents, uint32_t* noComponents, uint32_t* rounds,
+                                  itm_stream stream);
 
 /* Read-only probes of the acceleration cubes of a hash scene (block directory, slot directory, sdf mirror: itm_types.h).  Both launch
  * the scene's recorded, unflushed engine calls first, as a download does, and only read; a scene without directories, without a mirror

@@ -671,6 +671,50 @@ int ITM_FN(mesh_download_indexed_attributes)(const itm_mesh* mesh, float* normal
  * missing index: ITM_ERR_INVALID. */
 int ITM_FN(mesh_write_ply_indexed)(const itm_mesh* mesh, const char* path, itm_stream stream);
 int ITM_FN(mesh_write_obj_indexed)(const itm_mesh* mesh, const char* path, itm_stream stream);
+/* Connected components of the indexed mesh (the reference has none; defined on the present index: noVertices unique vertices k,
+ * noTriangles faces[i] = (a, b, c)).  Two vertices are LINKED iff some triangle names both -- degenerate triangles count like any other,
+ * and nothing is linked by position: the index has decided which positions are one vertex, bit for bit.  A COMPONENT is a class of the
+ * transitive closure; root(k) = the smallest vertex index of k's component.  Components are numbered c = 0 .. noComponents - 1 in
+ * ascending order of their root (vertices are numbered by first occurrence, so this is the order in which the components first appear in
+ * the triangle buffer).  Then
+ *   vertexComponent[k]   = the number of vertex k's component
+ *   triangleComponent[i] = vertexComponent[faces[i][0]]
+ *   components[c]        = {firstVertex = the root, noVertices, noTriangles, reserved = 0, bbMin[3], bbMax[3]}: the box is the per-axis
+ *                          minimum and maximum over the component's vertices in the total order of the IEEE bit patterns (sign-magnitude
+ *                          mapped to a monotone unsigned: -0.0f < +0.0f); the stored floats are a vertex's own bits.
+ * Everything is an integer or independent of order: no tolerance, deterministic, compared bit for bit.  (Surface area is not here: a
+ * float sum over atomics depends on arrival order; a host that wants it computes it from the downloads.)
+ * itm_mesh_components labels the present index in device memory owned by the mesh (sized from the counts; the call synchronises `stream`
+ * to read them; a call that cannot get its memory keeps none of it).  It needs a current index (ITM_ERR_INVALID otherwise);
+ * itm_mesh_scene, itm_mesh_volume, itm_mesh_index and itm_mesh_filter_components make the labelling stale.  An empty index gives zero
+ * components and no error. */
+typedef struct itm_mesh_component {
+  uint32_t firstVertex;   /* the component's smallest vertex index */
+  uint32_t noVertices;
+  uint32_t noTriangles;
+  uint32_t reserved;      /* 0 */
+  float bbMin[3];
+  float bbMax[3];
+} itm_mesh_component;     /* 40 bytes */
+int ITM_FN(mesh_components)(itm_mesh* mesh, itm_stream stream);
+/* number of components, the number of union rounds the labelling took (1 unless its final check asked for more; 0 for an empty index)
+ * and the three device arrays (uint32 per vertex, uint32 per triangle, itm_mesh_component per component; NULL where empty);
+ * synchronises `stream`.  Any output pointer may be NULL.  Stale or missing labelling: ITM_ERR_INVALID. */
+int ITM_FN(mesh_components_info)(const itm_mesh* mesh, uint32_t* noComponents, uint32_t* rounds, const uint32_t** vertexComponent,
+                                 const uint32_t** triangleComponent, const itm_mesh_component** components, itm_stream stream);
+/* copies min(count, capacity) entries of each array to host memory; any pointer may be NULL.  Stale or missing labelling:
+ * ITM_ERR_INVALID.  Synchronises `stream`. */
+int ITM_FN(mesh_download_components)(const itm_mesh* mesh, uint32_t* vertexComponent_host, uint32_t capacityVertices,
+                                     uint32_t* triangleComponent_host, uint32_t capacityTriangles, itm_mesh_component* components_host,
+                                     uint32_t capacityComponents, uint32_t* noComponents, itm_stream stream);
+/* Drops fragments: component c is kept iff components[c].noTriangles >= minTriangles and (keep_host == NULL or keep_host[c] != 0);
+ * noKeep must equal noComponents when keep_host is given (ITM_ERR_INVALID otherwise).  The call rewrites the TRIANGLE BUFFER: the kept
+ * triangles, in their buffer order, packed to the front; keptTriangles / keptComponents (either may be NULL) receive the counts.  It
+ * needs a current labelling (ITM_ERR_INVALID otherwise).  Afterwards the mesh behaves in every respect as if itm_mesh_scene /
+ * itm_mesh_volume had generated exactly those triangles: itm_mesh_info reports the kept count, and the soup's attributes, the index, the
+ * indexed attributes and the components are stale.  Keeping nothing leaves a valid empty mesh.  Synchronises `stream`. */
+int ITM_FN(mesh_filter_components)(itm_mesh* mesh, uint32_t minTriangles, const uint8_t* keep_host, uint32_t noKeep,
+                                   uint32_t* keptTriangles, uint32_t* keptComponents, itm_stream stream);
 
 /* ---- multi-stream exchange (BASELINE configs[3]) ------------------------------------------------------------------
  * One depth stream per GPU; fusion needs no collective.  Per frame every rank publishes the record of itm_export_visible_record

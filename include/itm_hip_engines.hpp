@@ -1136,6 +1136,19 @@ class ITMMainEngine_HIP {
     check(itm_mesh_indexed_attributes(scene.handle, exportMesh, ITM_MESH_NORMALS | (colour ? ITM_MESH_COLOURS : 0), nullptr), "itm_mesh_indexed_attributes");
     check(itm_mesh_write_ply_indexed(exportMesh, fileName, nullptr), "WriteIndexedPLY");
   }
+  // SaveSceneToIndexedPLY without the floating fragments: the mesh is indexed, its connected components are labelled
+  // (itm_mesh_components) and those with fewer than minTriangles triangles dropped (itm_mesh_filter_components); what is left is
+  // indexed again and written with its attributes
+  void SaveSceneToCleanPLY(const char* fileName, uint32_t minTriangles) {
+    const bool colour = TVoxel::kType == ITM_VOXEL_S_RGB || TVoxel::kType == ITM_VOXEL_F_RGB;
+    MeshForExport(0);
+    check(itm_mesh_index(exportMesh, nullptr), "itm_mesh_index");
+    check(itm_mesh_components(exportMesh, nullptr), "itm_mesh_components");
+    check(itm_mesh_filter_components(exportMesh, minTriangles, nullptr, 0, nullptr, nullptr, nullptr), "itm_mesh_filter_components");
+    check(itm_mesh_index(exportMesh, nullptr), "itm_mesh_index");
+    check(itm_mesh_indexed_attributes(scene.handle, exportMesh, ITM_MESH_NORMALS | (colour ? ITM_MESH_COLOURS : 0), nullptr), "itm_mesh_indexed_attributes");
+    check(itm_mesh_write_ply_indexed(exportMesh, fileName, nullptr), "WriteIndexedPLY");
+  }
 
  private:
   void MeshForExport(int attributes) {
@@ -1183,6 +1196,18 @@ class ITMMesh {
   void ComputeIndexedAttributes(const ITMScene<TVoxel, TIndex>* scene, int what) { check(itm_mesh_indexed_attributes(scene->handle, handle, what, stream), "ComputeIndexedAttributes"); }
   void WriteIndexedPLY(const char* fileName) const { check(itm_mesh_write_ply_indexed(handle, fileName, stream), "WriteIndexedPLY"); }
   void WriteIndexedOBJ(const char* fileName) const { check(itm_mesh_write_obj_indexed(handle, fileName, stream), "WriteIndexedOBJ"); }
+  // the connected components of the present index; stale after the next MeshScene, Index or FilterComponents
+  uint32_t noComponents = 0;
+  void Components() {
+    check(itm_mesh_components(handle, stream), "Components");
+    check(itm_mesh_components_info(handle, &noComponents, nullptr, nullptr, nullptr, nullptr, stream), "itm_mesh_components_info");
+  }
+  // keeps the components with at least minTriangles triangles and, keep given (noKeep == noComponents entries), a non-zero entry there;
+  // the kept triangles are packed to the front of the buffer.  Attributes, index and components are stale afterwards.
+  void FilterComponents(uint32_t minTriangles, const uint8_t* keep = nullptr, uint32_t noKeep = 0) {
+    check(itm_mesh_filter_components(handle, minTriangles, keep, noKeep, &noTotalTriangles, nullptr, stream), "FilterComponents");
+    noVertices = 0; noComponents = 0;
+  }
 };
 
 // ITMMeshingEngine<TVoxel,TIndex>::MeshScene (Engine/ITMMeshingEngine.h:19-26)

@@ -163,6 +163,17 @@ class AccelCensus(C.Structure):
                 ("page_counter", C.c_int32), ("mirror_form", C.c_int32), ("has_directory", C.c_int32), ("reserved", C.c_int32)]
 
 
+class MeshComponent(C.Structure):
+    """itm_mesh_component (include/itm_hip.h, itm_mesh_components): 40 bytes."""
+    _fields_ = [("firstVertex", C.c_uint32), ("noVertices", C.c_uint32), ("noTriangles", C.c_uint32), ("reserved", C.c_uint32),
+                ("bbMin", C.c_float * 3), ("bbMax", C.c_float * 3)]
+
+
+# the same record as a numpy dtype (Mesh.components)
+MESH_COMPONENT_DTYPE = np.dtype([("firstVertex", np.uint32), ("noVertices", np.uint32), ("noTriangles", np.uint32), ("reserved", np.uint32),
+                                 ("bbMin", np.float32, 3), ("bbMax", np.float32, 3)])
+
+
 class MergeStats(C.Structure):
     """itm_merge_stats (include/itm_hip.h, itm_scene_merge)."""
     _fields_ = [(n, C.c_int32) for n in ("rounds", "considered", "alreadyPresent", "allocated", "combined", "unserved",
@@ -405,6 +416,12 @@ _HOST_IO_SIGS = {
     "mesh_download_indexed_attributes": (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(C.c_uint32), _P]),
     "mesh_write_ply_indexed": (C.c_int, [_P, C.c_char_p, _P]),
     "mesh_write_obj_indexed": (C.c_int, [_P, C.c_char_p, _P]),
+    # connected components of the indexed mesh and the fragment filter (product only)
+    "mesh_components": (C.c_int, [_P, _P]),
+    "mesh_components_info": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P]),
+    "mesh_download_components": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint32), _P]),
+    "mesh_filter_components": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _P]),
+    "debug_mesh_components": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _P]),
     # the mesh of either index type: dense volumes brick by brick (product only: the reference's dense MeshScene is empty)
     "mesh_volume": (C.c_int, [_P, _P, _P]),
     # colour maps of the display path (product only: host loops in the reference, Engine/ITMVisualisationEngine.cpp:7-107)
@@ -1142,6 +1159,58 @@ class Mesh:
 
     def WriteIndexedOBJ(self, path: str, stream=None):
         self.scene.be.check(self.scene.be.fn["mesh_write_obj_indexed"](_P(self.h), path.encode(), _P(stream)), "mesh_write_obj_indexed")
+
+    def Components(self, stream=None):
+        """Labels the connected components of the present index (vertices are linked iff a triangle names both)."""
+        self.scene.be.check(self.scene.be.fn["mesh_components"](_P(self.h), _P(stream)), "mesh_components")
+
+    def components_info(self, stream=None):
+        """(number of components, union rounds the labelling took)"""
+        nc, rounds = C.c_uint32(), C.c_uint32()
+        self.scene.be.check(self.scene.be.fn["mesh_components_info"](_P(self.h), C.byref(nc), C.byref(rounds), None, None, None, _P(stream)),
+                            "mesh_components_info")
+        return nc.value, rounds.value
+
+    def _components(self, which: int, stream):
+        nc, _ = self.components_info(stream)
+        nv, nt = self.index_info(stream)
+        out = (np.zeros(nv, np.uint32), np.zeros(nt, np.uint32), np.zeros(nc, MESH_COMPONENT_DTYPE))[which]
+        p = [None, None, None]
+        p[which] = out.ctypes.data_as(_P)
+        self.scene.be.check(self.scene.be.fn["mesh_download_components"](_P(self.h), p[0], nv, p[1], nt, p[2], nc, None, _P(stream)),
+                            "mesh_download_components")
+        return out
+
+    def vertex_component(self, stream=None) -> np.ndarray:
+        """(noVertices,) uint32: the component number of every unique vertex."""
+        return self._components(0, stream)
+
+    def triangle_component(self, stream=None) -> np.ndarray:
+        """(noTotalTriangles,) uint32: the component of every triangle's first corner."""
+        return self._components(1, stream)
+
+    def components(self, stream=None) -> np.ndarray:
+        """(noComponents,) MESH_COMPONENT_DTYPE: firstVertex (the root), noVertices, noTriangles, reserved, bbMin, bbMax."""
+        return self._components(2, stream)
+
+    def FilterComponents(self, min_triangles: int = 0, keep=None, stream=None):
+        """Keeps the triangles of the components with at least min_triangles triangles and, keep given (one entry per component), a
+        non-zero entry there; the kept triangles are packed to the front of the buffer in their order.  Attributes, index and components
+        are stale afterwards.  Returns (kept triangles, kept components)."""
+        kt, kc = C.c_uint32(), C.c_uint32()
+        mask = None if keep is None else np.ascontiguousarray(np.asarray(keep) != 0, np.uint8).reshape(-1)
+        buf = mask if mask is None or len(mask) else np.zeros(1, np.uint8)       # an empty mask is still a mask: never a null pointer
+        rc = self.scene.be.fn["mesh_filter_components"](_P(self.h), int(min_triangles), None if mask is None else buf.ctypes.data_as(_P),
+                                                        0 if mask is None else len(mask), C.byref(kt), C.byref(kc), _P(stream))
+        self.scene.be.check(rc, "mesh_filter_components")
+        return kt.value, kc.value
+
+    def KeepLargest(self, n: int = 1, stream=None):
+        """FilterComponents keeping the n components with the most triangles; ties go to the lower component number."""
+        tri = self.components(stream)["noTriangles"].astype(np.int64)
+        keep = np.zeros(len(tri), np.uint8)
+        keep[np.argsort(-tri, kind="stable")[:max(int(n), 0)]] = 1
+        return self.FilterComponents(0, keep, stream)
 
     def close(self):
         if self.h:

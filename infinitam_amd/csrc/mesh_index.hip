@@ -182,6 +182,7 @@ int itm_mesh_index(itm_mesh* m, itm_stream stream) {
   if (rc) return rc;
   m->indexCurrent = false;
   m->indexedAttrCurrent = 0;                                           // attributes of the unique vertices belong to the index that is replaced
+  m->componentsCurrent = false;                                        // and so do its components
   m->noVertices = 0; m->noIndexedTriangles = n;
   if (n == 0) { m->indexCurrent = true; return ITM_OK; }               // nothing meshed, or a dense scene: an empty index
   const size_t nSoup = (size_t)n * 3;                                  // < 2^32: the buffer holds less than 2^32 / 36 triangles

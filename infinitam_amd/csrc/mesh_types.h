@@ -1,9 +1,29 @@
 // mesh_types.h -- the mesh handle shared by meshing.hip (triangles), mesh_attributes.hip (per-vertex normals and colours) and
-// mesh_index.hip (the indexed form: shared vertices and faces).
+// mesh_index.hip (the indexed form: shared vertices and faces) and mesh_components.hip (its connected components, the fragment filter).
 #pragma once
 
 #include "itm_internal.h"
 #include "volume_device.h"
+
+namespace itm {
+
+// What a labelling (mesh_components.hip) leaves in device memory, and its scratch: owned by the mesh, or by one call of the test hook.
+struct ComponentBuffers {
+  DeviceBuffer<uint32_t> parent;             // per vertex: the union-find link, always to a smaller index; the root once labelled
+  DeviceBuffer<uint32_t> vertexComponent;    // per vertex: its component's number
+  DeviceBuffer<uint32_t> triangleComponent;  // per triangle: the component of its first corner
+  DeviceBuffer<itm_mesh_component> components;
+  DeviceBuffer<uint8_t> flags;               // per vertex: a root?  (the filter: per triangle: kept?)
+  DeviceBuffer<int32_t> chunkCount;          // flags per chunk of kSweepChunk
+  DeviceBuffer<int32_t> ids;                 // the roots, ascending  (the filter: the kept triangles, ascending)
+  DeviceBuffer<int32_t> counters;            // [0] flags set, [1] the same after the cap, [2] what the check launch found, [3] kept components
+  void reset() {
+    parent.reset(); vertexComponent.reset(); triangleComponent.reset(); components.reset(); flags.reset(); chunkCount.reset(); ids.reset();
+    counters.reset();
+  }
+};
+
+}  // namespace itm
 
 struct itm_mesh {
   const itm_scene* scene = nullptr;
@@ -40,6 +60,12 @@ struct itm_mesh {
   itm::DeviceBuffer<float> vertexNormals;    // 3 floats per unique vertex
   itm::DeviceBuffer<uchar4> vertexColours;   // one per unique vertex
   uint32_t indexedAttrCurrent = 0;   // ITM_MESH_* bits computed for the present index; itm_mesh_scene and itm_mesh_index clear it
+  // connected components of the present index (mesh_components.hip); allocated / grown by itm_mesh_components, sized from the counts
+  itm::ComponentBuffers comp;
+  itm::DeviceBuffer<uint8_t> componentKeep;  // per component: kept by itm_mesh_filter_components? (the host's mask, then the verdict)
+  itm::DeviceBuffer<float> packed;           // the kept triangles, packed, before they replace the buffer's contents
+  uint32_t noComponents = 0, componentRounds = 0;
+  bool componentsCurrent = false;    // the labelling describes the present index; itm_mesh_scene, itm_mesh_index and the filter clear it
 };
 
 namespace itm {

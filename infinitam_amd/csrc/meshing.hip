@@ -118,6 +118,7 @@ int itm_mesh_scene(const itm_scene* s, itm_mesh* m, itm_stream stream) {
   hipStream_t st = as_stream(stream);
   m->attrCurrent = 0;                                          // vertex attributes belong to the mesh that is being replaced
   m->indexCurrent = false; m->indexedAttrCurrent = 0;          // and so does the indexed form
+  m->componentsCurrent = false;                                // with its components
   m->fromVolume = false;
   // mesh->triangles->Clear()
   ITM_HIP(hipMemsetAsync(m->triangles, 0, (size_t)m->maxTriangles * 36, st));
