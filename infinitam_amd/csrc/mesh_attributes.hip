@@ -21,11 +21,6 @@
 // so the unique vertices whose first occurrence lies in block b's triangles are one contiguous range [blockVertex[b], blockVertex
 // [b + 1]) -- vertices of that block's cells, for which the staged planes hold as they do for the soup.  One evaluation per distinct
 // position instead of one per occurrence.
-#include <cstdio>
-#include <cstring>
-#include <string>
-#include <vector>
-
 #include "itm_internal.h"
 #include "mesh_types.h"
 #include "sample_device.h"
@@ -147,6 +142,16 @@ __global__ void __launch_bounds__(256) mesh_attr_block_kernel(VolumeView vol, co
   }
 }
 
+// what both attribute entry points ask of their arguments
+static int check_attribute_request(const itm_scene* s, const itm_mesh* m, int what) {
+  if (!s || !m) return set_error(ITM_ERR_INVALID, "null argument");
+  if (m->scene != s) return set_error(ITM_ERR_INVALID, "mesh belongs to another scene");
+  if (what <= 0 || (what & ~(ITM_MESH_NORMALS | ITM_MESH_COLOURS))) return set_error(ITM_ERR_INVALID, "what: ITM_MESH_NORMALS, ITM_MESH_COLOURS or both");
+  if ((what & ITM_MESH_COLOURS) && !voxel_has_colour(s->cfg.voxelType))
+    return set_error(ITM_ERR_INVALID, "the scene's voxel type stores no colour: the mesh has no colour attribute");
+  return ITM_OK;
+}
+
 }  // namespace itm
 
 using namespace itm;
@@ -154,15 +159,11 @@ using namespace itm;
 extern "C" {
 
 int itm_mesh_attributes(const itm_scene* s, itm_mesh* m, int what, itm_stream stream) {
-  if (!s || !m) return set_error(ITM_ERR_INVALID, "null argument");
-  if (m->scene != s) return set_error(ITM_ERR_INVALID, "mesh belongs to another scene");
-  if (what <= 0 || (what & ~(ITM_MESH_NORMALS | ITM_MESH_COLOURS))) return set_error(ITM_ERR_INVALID, "what: ITM_MESH_NORMALS, ITM_MESH_COLOURS or both");
-  if ((what & ITM_MESH_COLOURS) && !voxel_has_colour(s->cfg.voxelType))
-    return set_error(ITM_ERR_INVALID, "the scene's voxel type stores no colour: the mesh has no colour attribute");
+  { const int rc = check_attribute_request(s, m, what); if (rc) return rc; }
   { const int rc = enter_scene(s, nullptr); if (rc) return rc; }
   hipStream_t st = as_stream(stream);
   const bool dense = s->cfg.indexType != ITM_INDEX_HASH;
-  if (dense && !m->fromVolume) { m->attrCurrent |= (uint32_t)what; return ITM_OK; }   // a dense scene that itm_mesh_volume has not meshed: nothing meshed, empty attributes
+  if (dense && !m->holds_volume_mesh()) { m->attributes_current(false, (uint32_t)what); return ITM_OK; }   // a dense scene that itm_mesh_volume has not meshed: nothing meshed, empty attributes
   const bool newNormals = (what & ITM_MESH_NORMALS) && !m->normals;
   if (newNormals) {
     const hipError_t e = m->normals.alloc((size_t)m->maxTriangles * 9);
@@ -185,48 +186,35 @@ int itm_mesh_attributes(const itm_scene* s, itm_mesh* m, int what, itm_stream st
   });
   if (rc) return rc;
   ITM_LAUNCH_CHECK();
-  m->attrCurrent |= (uint32_t)what;
+  m->attributes_current(false, (uint32_t)what);
   return ITM_OK;
 }
 
 int itm_mesh_download_attributes(const itm_mesh* m, float* normals_host, uint8_t* colours_host, uint32_t capacityTriangles,
                                  uint32_t* noTotalTriangles, itm_stream stream) {
   if (!m || !noTotalTriangles) return set_error(ITM_ERR_INVALID, "null argument");
-  if (normals_host && !(m->attrCurrent & ITM_MESH_NORMALS))
-    return set_error(ITM_ERR_INVALID, "no normals for this mesh: itm_mesh_attributes has not computed them since the last itm_mesh_scene");
-  if (colours_host && !(m->attrCurrent & ITM_MESH_COLOURS))
-    return set_error(ITM_ERR_INVALID, "no colours for this mesh: itm_mesh_attributes has not computed them since the last itm_mesh_scene");
+  { const int rc = m->require_attributes(normals_host != nullptr, colours_host != nullptr, false); if (rc) return rc; }
   { const int rc = enter_scene(m->scene, nullptr); if (rc) return rc; }
   int rc = itm_mesh_info(m, noTotalTriangles, nullptr, nullptr, stream);
   if (rc) return rc;
-  const uint32_t n = *noTotalTriangles < capacityTriangles ? *noTotalTriangles : capacityTriangles;
   hipStream_t st = as_stream(stream);
-  if (n && normals_host) ITM_HIP(hipMemcpyAsync(normals_host, m->normals, (size_t)n * 36, hipMemcpyDeviceToHost, st));
-  if (n && colours_host) ITM_HIP(hipMemcpyAsync(colours_host, m->colours, (size_t)n * 12, hipMemcpyDeviceToHost, st));
+  ITM_HIP(copy_out(normals_host, m->normals, *noTotalTriangles, capacityTriangles, 36, st));
+  ITM_HIP(copy_out(colours_host, m->colours, *noTotalTriangles, capacityTriangles, 12, st));
   ITM_HIP(hipStreamSynchronize(st));
   return ITM_OK;
 }
 
 // the attributes of the unique vertices of the indexed mesh: one evaluation per distinct position, through the staged kernel
 int itm_mesh_indexed_attributes(const itm_scene* s, itm_mesh* m, int what, itm_stream stream) {
-  if (!s || !m) return set_error(ITM_ERR_INVALID, "null argument");
-  if (m->scene != s) return set_error(ITM_ERR_INVALID, "mesh belongs to another scene");
-  if (what <= 0 || (what & ~(ITM_MESH_NORMALS | ITM_MESH_COLOURS))) return set_error(ITM_ERR_INVALID, "what: ITM_MESH_NORMALS, ITM_MESH_COLOURS or both");
-  if ((what & ITM_MESH_COLOURS) && !voxel_has_colour(s->cfg.voxelType))
-    return set_error(ITM_ERR_INVALID, "the scene's voxel type stores no colour: the mesh has no colour attribute");
-  if (!m->indexCurrent) return set_error(ITM_ERR_INVALID, "no index for this mesh: itm_mesh_index has not built it since the last itm_mesh_scene");
+  { const int rc = check_attribute_request(s, m, what); if (rc) return rc; }
+  { const int rc = m->require_index(); if (rc) return rc; }
   { const int rc = enter_scene(s, nullptr); if (rc) return rc; }
   hipStream_t st = as_stream(stream);
-  if (m->noVertices == 0) { m->indexedAttrCurrent |= (uint32_t)what; return ITM_OK; }   // an empty index (dense scenes, nothing meshed): empty attributes
+  if (m->noVertices == 0) { m->attributes_current(true, (uint32_t)what); return ITM_OK; }   // an empty index (dense scenes, nothing meshed): empty attributes
+  // (only a stale attribute's buffer can fail to grow: one that is current for this index already holds noVertices elements)
   hipError_t e;
-  if ((what & ITM_MESH_NORMALS) && (e = m->vertexNormals.reserve((size_t)m->noVertices * 3)) != hipSuccess) {
-    m->indexedAttrCurrent &= ~(uint32_t)ITM_MESH_NORMALS;
-    return hip_fail(e, "vertex normals", __FILE__, __LINE__);
-  }
-  if ((what & ITM_MESH_COLOURS) && (e = m->vertexColours.reserve((size_t)m->noVertices)) != hipSuccess) {
-    m->indexedAttrCurrent &= ~(uint32_t)ITM_MESH_COLOURS;
-    return hip_fail(e, "vertex colours", __FILE__, __LINE__);
-  }
+  if ((what & ITM_MESH_NORMALS) && (e = m->vertexNormals.reserve((size_t)m->noVertices * 3)) != hipSuccess) return hip_fail(e, "vertex normals", __FILE__, __LINE__);
+  if ((what & ITM_MESH_COLOURS) && (e = m->vertexColours.reserve((size_t)m->noVertices)) != hipSuccess) return hip_fail(e, "vertex colours", __FILE__, __LINE__);
   const VolumeView vol = make_volume(s);
   const int grid = 256 * 8;
   const int rc = dispatch_volume(s, [&](auto vx, auto isDense) {
@@ -240,65 +228,30 @@ int itm_mesh_indexed_attributes(const itm_scene* s, itm_mesh* m, int what, itm_s
   });
   if (rc) return rc;
   ITM_LAUNCH_CHECK();
-  m->indexedAttrCurrent |= (uint32_t)what;
+  m->attributes_current(true, (uint32_t)what);
   return ITM_OK;
 }
 
 int itm_mesh_download_indexed_attributes(const itm_mesh* m, float* normals_host, uint8_t* colours_host, uint32_t capacityVertices,
                                          uint32_t* noVertices, itm_stream stream) {
   if (!m || !noVertices) return set_error(ITM_ERR_INVALID, "null argument");
-  if (!m->indexCurrent) return set_error(ITM_ERR_INVALID, "no index for this mesh: itm_mesh_index has not built it since the last itm_mesh_scene");
-  if (normals_host && !(m->indexedAttrCurrent & ITM_MESH_NORMALS))
-    return set_error(ITM_ERR_INVALID, "no normals for the indexed mesh: itm_mesh_indexed_attributes has not computed them since the last itm_mesh_index");
-  if (colours_host && !(m->indexedAttrCurrent & ITM_MESH_COLOURS))
-    return set_error(ITM_ERR_INVALID, "no colours for the indexed mesh: itm_mesh_indexed_attributes has not computed them since the last itm_mesh_index");
+  { const int rc = m->require_attributes(normals_host != nullptr, colours_host != nullptr, true); if (rc) return rc; }
   { const int rc = enter_scene(m->scene, nullptr); if (rc) return rc; }
   *noVertices = m->noVertices;
-  const uint32_t n = m->noVertices < capacityVertices ? m->noVertices : capacityVertices;
   hipStream_t st = as_stream(stream);
-  if (n && normals_host) ITM_HIP(hipMemcpyAsync(normals_host, m->vertexNormals, (size_t)n * 12, hipMemcpyDeviceToHost, st));
-  if (n && colours_host) ITM_HIP(hipMemcpyAsync(colours_host, m->vertexColours, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  ITM_HIP(copy_out(normals_host, m->vertexNormals, m->noVertices, capacityVertices, 12, st));
+  ITM_HIP(copy_out(colours_host, m->vertexColours, m->noVertices, capacityVertices, 4, st));
   ITM_HIP(hipStreamSynchronize(st));
   return ITM_OK;
 }
 
-// binary_little_endian PLY: positions, then the attributes that are current; faces with WriteOBJ's winding
+// binary_little_endian PLY of the soup with the attributes that are current (mesh_files.h)
 int itm_mesh_write_ply(const itm_mesh* m, const char* path, itm_stream stream) {
   if (!m || !path) return set_error(ITM_ERR_INVALID, "null argument");
   { const int rc = enter_scene(m->scene, nullptr); if (rc) return rc; }
-  uint32_t n = 0;
-  int rc = itm_mesh_info(m, &n, nullptr, nullptr, stream);
-  if (rc) return rc;
-  const bool withNormals = (m->attrCurrent & ITM_MESH_NORMALS) != 0, withColours = (m->attrCurrent & ITM_MESH_COLOURS) != 0;
-  std::vector<float> tri((size_t)n * 9), nrm(withNormals ? (size_t)n * 9 : 0);
-  std::vector<uint8_t> col(withColours ? (size_t)n * 12 : 0);
-  if ((rc = itm_mesh_download(m, tri.data(), n, &n, stream))) return rc;
-  if (withNormals || withColours)
-    if ((rc = itm_mesh_download_attributes(m, withNormals ? nrm.data() : nullptr, withColours ? col.data() : nullptr, n, &n, stream))) return rc;
-  std::string head = "ply\nformat binary_little_endian 1.0\ncomment itm-hip mesh\nelement vertex " + std::to_string((unsigned long long)n * 3ull) +
-                     "\nproperty float x\nproperty float y\nproperty float z\n";
-  if (withNormals) head += "property float nx\nproperty float ny\nproperty float nz\n";
-  if (withColours) head += "property uchar red\nproperty uchar green\nproperty uchar blue\n";
-  head += "element face " + std::to_string(n) + "\nproperty list uchar int vertex_indices\nend_header\n";
-  const size_t vertexBytes = 12 + (withNormals ? 12 : 0) + (withColours ? 3 : 0);
-  std::vector<uint8_t> body((size_t)n * 3 * vertexBytes + (size_t)n * 13);
-  uint8_t* o = body.data();
-  for (size_t v = 0; v < (size_t)n * 3; ++v) {
-    memcpy(o, &tri[v * 3], 12); o += 12;
-    if (withNormals) { memcpy(o, &nrm[v * 3], 12); o += 12; }
-    if (withColours) { memcpy(o, &col[v * 4], 3); o += 3; }
-  }
-  for (uint32_t i = 0; i < n; ++i) {
-    const int32_t idx[3] = {(int32_t)(i * 3 + 2), (int32_t)(i * 3 + 1), (int32_t)(i * 3)};
-    *o++ = 3;
-    memcpy(o, idx, 12); o += 12;
-  }
-  FILE* f = fopen(path, "wb");
-  if (!f) return set_error(ITM_ERR_INVALID, std::string("cannot create ") + path);
-  bool ok = fwrite(head.data(), 1, head.size(), f) == head.size();
-  ok = (body.empty() || fwrite(body.data(), 1, body.size(), f) == body.size()) && ok;
-  ok = (fclose(f) == 0) && ok;
-  return ok ? ITM_OK : set_error(ITM_ERR_INVALID, std::string("short write to ") + path);
+  FetchedMesh h;
+  const int rc = fetch_soup(m, true, h, stream);
+  return rc ? rc : file_status(write_ply(h.view, path));
 }
 
 }  // extern "C"

@@ -34,8 +34,6 @@
 // per-block starts of a hash mesh: blockTriangles[b] = pos(min(start, count)); totals = {kept, kept}, so that the last block ends at
 // the kept count for the attribute and index paths exactly as after itm_mesh_scene.
 #include <algorithm>
-#include <cstring>
-#include <vector>
 
 #include "itm_internal.h"
 #include "mesh_types.h"
@@ -320,12 +318,7 @@ __global__ void __launch_bounds__(256) components_blocks_kernel(const RenderCoun
   if (b >= nBlocks) return;
   uint32_t t0 = (uint32_t)blockTriangles[b];
   t0 = t0 < count ? t0 : count;
-  uint32_t lo = 0u, hi = (uint32_t)counters[1];
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if ((uint32_t)kept[mid] < t0) lo = mid + 1u; else hi = mid;
-  }
-  blockTriangles[b] = (int32_t)lo;
+  blockTriangles[b] = (int32_t)lower_bound(kept, (uint32_t)counters[1], t0);
 }
 
 static int grid_for(size_t n) { return (int)std::min<size_t>(std::max<size_t>((n + 255) / 256, 1), 2048); }
@@ -383,12 +376,6 @@ static int label_components(ComponentBuffers& b, const uint32_t* faces, uint32_t
   return ITM_OK;
 }
 
-static int components_are_current(const itm_mesh* m) {
-  if (!m->indexCurrent || !m->componentsCurrent)
-    return set_error(ITM_ERR_INVALID, "no components for this mesh: itm_mesh_components has not labelled the present index");
-  return ITM_OK;
-}
-
 }  // namespace itm
 
 using namespace itm;
@@ -397,21 +384,21 @@ extern "C" {
 
 int itm_mesh_components(itm_mesh* m, itm_stream stream) {
   if (!m) return set_error(ITM_ERR_INVALID, "null mesh");
-  if (!m->indexCurrent) return set_error(ITM_ERR_INVALID, "no index for this mesh: itm_mesh_index has not built it since the last itm_mesh_scene");
-  m->componentsCurrent = false;
+  { const int rc = m->require_index(); if (rc) return rc; }
+  m->components_recomputing();
   m->noComponents = 0; m->componentRounds = 0;
-  if (m->noVertices == 0) { m->componentsCurrent = true; return ITM_OK; }       // an empty index: no components
+  if (m->noVertices == 0) { m->components_current(); return ITM_OK; }           // an empty index: no components
   const int rc = label_components(m->comp, m->faces, m->noIndexedTriangles, m->noVertices, (const uint32_t*)m->vertices.get(), as_stream(stream), &m->noComponents,
                                   &m->componentRounds);
   if (rc) { m->noComponents = 0; return rc; }
-  m->componentsCurrent = true;
+  m->components_current();
   return ITM_OK;
 }
 
 int itm_mesh_components_info(const itm_mesh* m, uint32_t* noComponents, uint32_t* rounds, const uint32_t** vertexComponent_dev,
                              const uint32_t** triangleComponent_dev, const itm_mesh_component** components_dev, itm_stream stream) {
   if (!m) return set_error(ITM_ERR_INVALID, "null mesh");
-  { const int rc = components_are_current(m); if (rc) return rc; }
+  { const int rc = m->require_components(); if (rc) return rc; }
   ITM_HIP(hipStreamSynchronize(as_stream(stream)));
   const bool any = m->noComponents != 0;
   if (noComponents) *noComponents = m->noComponents;
@@ -426,15 +413,13 @@ int itm_mesh_download_components(const itm_mesh* m, uint32_t* vertexComponent_ho
                                  uint32_t capacityTriangles, itm_mesh_component* components_host, uint32_t capacityComponents, uint32_t* noComponents,
                                  itm_stream stream) {
   if (!m) return set_error(ITM_ERR_INVALID, "null mesh");
-  { const int rc = components_are_current(m); if (rc) return rc; }
+  { const int rc = m->require_components(); if (rc) return rc; }
   if (noComponents) *noComponents = m->noComponents;
   const bool any = m->noComponents != 0;
-  const uint32_t nv = any ? std::min(m->noVertices, capacityVertices) : 0u, nt = any ? std::min(m->noIndexedTriangles, capacityTriangles) : 0u;
-  const uint32_t nc = std::min(m->noComponents, capacityComponents);
-  hipStream_t st = as_stream(stream);
-  if (nv && vertexComponent_host) ITM_HIP(hipMemcpyAsync(vertexComponent_host, m->comp.vertexComponent, (size_t)nv * 4, hipMemcpyDeviceToHost, st));
-  if (nt && triangleComponent_host) ITM_HIP(hipMemcpyAsync(triangleComponent_host, m->comp.triangleComponent, (size_t)nt * 4, hipMemcpyDeviceToHost, st));
-  if (nc && components_host) ITM_HIP(hipMemcpyAsync(components_host, m->comp.components, (size_t)nc * sizeof(itm_mesh_component), hipMemcpyDeviceToHost, st));
+  hipStream_t st = as_stream(stream);                                  // (an empty index has no labelling buffers: nothing is copied)
+  ITM_HIP(copy_out(vertexComponent_host, m->comp.vertexComponent, any ? m->noVertices : 0u, capacityVertices, 4, st));
+  ITM_HIP(copy_out(triangleComponent_host, m->comp.triangleComponent, any ? m->noIndexedTriangles : 0u, capacityTriangles, 4, st));
+  ITM_HIP(copy_out(components_host, m->comp.components, m->noComponents, capacityComponents, sizeof(itm_mesh_component), st));
   ITM_HIP(hipStreamSynchronize(st));
   return ITM_OK;
 }
@@ -442,13 +427,12 @@ int itm_mesh_download_components(const itm_mesh* m, uint32_t* vertexComponent_ho
 int itm_mesh_filter_components(itm_mesh* m, uint32_t minTriangles, const uint8_t* keep_host, uint32_t noKeep, uint32_t* keptTriangles,
                                uint32_t* keptComponents, itm_stream stream) {
   if (!m) return set_error(ITM_ERR_INVALID, "null mesh");
-  { const int rc = components_are_current(m); if (rc) return rc; }
+  { const int rc = m->require_components(); if (rc) return rc; }
   if (keep_host && noKeep != m->noComponents) return set_error(ITM_ERR_INVALID, "the keep mask needs one entry per component");
   hipStream_t st = as_stream(stream);
   const uint32_t n = m->noIndexedTriangles, nC = m->noComponents;      // the index is current: n is the buffer's count
-  auto stale = [&] { m->attrCurrent = 0; m->indexCurrent = false; m->indexedAttrCurrent = 0; m->componentsCurrent = false; };
   if (n == 0) {                                                        // nothing to drop: an empty mesh stays one
-    stale();
+    m->soup_rewritten();
     if (keptTriangles) *keptTriangles = 0;
     if (keptComponents) *keptComponents = 0;
     return ITM_OK;
@@ -468,7 +452,7 @@ int itm_mesh_filter_components(itm_mesh* m, uint32_t minTriangles, const uint8_t
     m->comp.flags = std::move(flags); m->comp.chunkCount = std::move(chunkCount); m->comp.ids = std::move(ids);
   }
   ComponentBuffers& b = m->comp;
-  stale();                                                             // from here on the buffer is being rewritten
+  m->soup_rewritten();                                                 // from here on the buffer is being rewritten
   ITM_HIP(hipMemsetAsync(b.counters, 0, 16, st));
   if (keep_host) ITM_HIP(hipMemcpyAsync(m->componentKeep, keep_host, nC, hipMemcpyHostToDevice, st));
   components_keep_kernel<<<grid_for(nC), 256, 0, st>>>(b.components, nC, minTriangles, keep_host ? 1 : 0, m->componentKeep, b.counters);
@@ -511,9 +495,8 @@ int itm_debug_mesh_components(const uint32_t* faces_host, uint32_t noTriangles, 
   if (noTriangles) ITM_HIP(hipMemcpyAsync(faces, faces_host, (size_t)noTriangles * 12, hipMemcpyHostToDevice, st));
   const int rc = label_components(b, faces, noTriangles, noVertices, nullptr, st, noComponents, rounds);
   if (rc) return rc;
-  const uint32_t nc = std::min(*noComponents, capComponents);
-  if (vertexComponent_host) ITM_HIP(hipMemcpyAsync(vertexComponent_host, b.vertexComponent, (size_t)noVertices * 4, hipMemcpyDeviceToHost, st));
-  if (nc && components_host) ITM_HIP(hipMemcpyAsync(components_host, b.components, (size_t)nc * sizeof(itm_mesh_component), hipMemcpyDeviceToHost, st));
+  ITM_HIP(copy_out(vertexComponent_host, b.vertexComponent, noVertices, noVertices, 4, st));
+  ITM_HIP(copy_out(components_host, b.components, *noComponents, capComponents, sizeof(itm_mesh_component), st));
   ITM_HIP(hipStreamSynchronize(st));
   return ITM_OK;
 }

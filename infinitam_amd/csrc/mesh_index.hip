@@ -27,11 +27,6 @@
 //      vertices first seen in block b are the range [blockVertex[b], blockVertex[b + 1]) (itm_mesh_indexed_attributes stages per block).
 // ITM_DEBUG_MESH_INDEX_WEAK_HASH cuts the hash to 8 bits (256 start slots spread over the table, the last one 64 slots before its
 // end), so that probe chains hundreds of slots long and the wrap-around are exercised on small scenes.
-#include <cstdio>
-#include <cstring>
-#include <string>
-#include <vector>
-
 #include "itm_internal.h"
 #include "mesh_types.h"
 #include "ordered_device.h"
@@ -152,20 +147,20 @@ __global__ void __launch_bounds__(256) mesh_index_blocks_kernel(const RenderCoun
     const uint32_t count = totals[1];
     uint32_t t0 = (uint32_t)blockTriangles[b];
     t0 = t0 < count ? t0 : count;
-    const uint32_t j0 = 3u * t0;                                       // lower bound of j0 in first[]
-    uint32_t hi = nUnique;
-    lo = 0u;
-    while (lo < hi) {
-      const uint32_t mid = lo + ((hi - lo) >> 1);
-      if (first[mid] < j0) lo = mid + 1u; else hi = mid;
-    }
+    lo = lower_bound(first, nUnique, 3u * t0);                         // the unique vertices first seen before soup vertex 3 t0
   }
   blockVertex[b] = (int32_t)lo;
 }
 
-static int index_is_current(const itm_mesh* m) {
-  if (!m->indexCurrent) return set_error(ITM_ERR_INVALID, "no index for this mesh: itm_mesh_index has not built it since the last itm_mesh_scene");
-  return ITM_OK;
+// the indexed mesh on the host, with the attributes of the unique vertices that are current where the writer carries them
+int fetch_indexed(const itm_mesh* m, bool withAttributes, FetchedMesh& out, itm_stream stream) {
+  int rc;
+  if ((rc = m->require_index()) || (rc = enter_scene(m->scene, nullptr))) return rc;
+  uint32_t nv = m->noVertices, nt = m->noIndexedTriangles;
+  const uint32_t have = withAttributes ? m->attributes(true) : 0u;
+  out.resize(nv, nt, true, have & ITM_MESH_NORMALS, have & ITM_MESH_COLOURS);
+  if ((rc = itm_mesh_download_indexed(m, out.positions.data(), nullptr, nv, out.faces.data(), nt, nullptr, nullptr, stream)) || !have) return rc;
+  return itm_mesh_download_indexed_attributes(m, out.normals_or_null(), out.colours_or_null(), nv, &nv, stream);
 }
 
 }  // namespace itm
@@ -180,11 +175,9 @@ int itm_mesh_index(itm_mesh* m, itm_stream stream) {
   uint32_t n = 0;
   int rc = itm_mesh_info(m, &n, nullptr, nullptr, stream);
   if (rc) return rc;
-  m->indexCurrent = false;
-  m->indexedAttrCurrent = 0;                                           // attributes of the unique vertices belong to the index that is replaced
-  m->componentsCurrent = false;                                        // and so do its components
+  m->index_rebuilding();                                               // its attributes and components belong to the index that is replaced
   m->noVertices = 0; m->noIndexedTriangles = n;
-  if (n == 0) { m->indexCurrent = true; return ITM_OK; }               // nothing meshed, or a dense scene: an empty index
+  if (n == 0) { m->index_current(); return ITM_OK; }                   // nothing meshed, or a dense scene: an empty index
   const size_t nSoup = (size_t)n * 3;                                  // < 2^32: the buffer holds less than 2^32 / 36 triangles
   if (nSoup >= 0x7fffffffull) return set_error(ITM_ERR_INVALID, "mesh too large to index");
   size_t tableSize = kIndexMinTable;
@@ -223,14 +216,14 @@ int itm_mesh_index(itm_mesh* m, itm_stream stream) {
   }
   ITM_LAUNCH_CHECK();
   m->noVertices = nV;
-  m->indexCurrent = true;
+  m->index_current();
   return ITM_OK;
 }
 
 int itm_mesh_index_info(const itm_mesh* m, uint32_t* noVertices, uint32_t* noTriangles, const float** vertices_dev, const uint32_t** faces_dev,
                         const uint32_t** first_dev, itm_stream stream) {
   if (!m) return set_error(ITM_ERR_INVALID, "null mesh");
-  { const int rc = index_is_current(m); if (rc) return rc; }
+  { const int rc = m->require_index(); if (rc) return rc; }
   ITM_HIP(hipStreamSynchronize(as_stream(stream)));
   if (noVertices) *noVertices = m->noVertices;
   if (noTriangles) *noTriangles = m->noIndexedTriangles;
@@ -243,85 +236,30 @@ int itm_mesh_index_info(const itm_mesh* m, uint32_t* noVertices, uint32_t* noTri
 int itm_mesh_download_indexed(const itm_mesh* m, float* vertices_host, uint32_t* first_host, uint32_t capacityVertices, uint32_t* faces_host,
                               uint32_t capacityTriangles, uint32_t* noVertices, uint32_t* noTriangles, itm_stream stream) {
   if (!m) return set_error(ITM_ERR_INVALID, "null mesh");
-  { const int rc = index_is_current(m); if (rc) return rc; }
+  { const int rc = m->require_index(); if (rc) return rc; }
   if (noVertices) *noVertices = m->noVertices;
   if (noTriangles) *noTriangles = m->noIndexedTriangles;
-  const uint32_t nv = m->noVertices < capacityVertices ? m->noVertices : capacityVertices;
-  const uint32_t nt = m->noIndexedTriangles < capacityTriangles ? m->noIndexedTriangles : capacityTriangles;
   hipStream_t st = as_stream(stream);
-  if (nv && vertices_host) ITM_HIP(hipMemcpyAsync(vertices_host, m->vertices, (size_t)nv * 12, hipMemcpyDeviceToHost, st));
-  if (nv && first_host) ITM_HIP(hipMemcpyAsync(first_host, m->first, (size_t)nv * 4, hipMemcpyDeviceToHost, st));
-  if (nt && faces_host) ITM_HIP(hipMemcpyAsync(faces_host, m->faces, (size_t)nt * 12, hipMemcpyDeviceToHost, st));
+  ITM_HIP(copy_out(vertices_host, m->vertices, m->noVertices, capacityVertices, 12, st));
+  ITM_HIP(copy_out(first_host, m->first, m->noVertices, capacityVertices, 4, st));
+  ITM_HIP(copy_out(faces_host, m->faces, m->noIndexedTriangles, capacityTriangles, 12, st));
   ITM_HIP(hipStreamSynchronize(st));
   return ITM_OK;
 }
 
-// the indexed mesh on the host, with the attributes of the unique vertices that are current
-static int fetch_indexed(const itm_mesh* m, std::vector<float>& vtx, std::vector<uint32_t>& faces, std::vector<float>* nrm, std::vector<uint8_t>* col,
-                         itm_stream stream) {
-  { const int rc = index_is_current(m); if (rc) return rc; }
-  { const int rc = enter_scene(m->scene, nullptr); if (rc) return rc; }
-  uint32_t nv = m->noVertices, nt = m->noIndexedTriangles;
-  vtx.resize((size_t)nv * 3); faces.resize((size_t)nt * 3);
-  int rc = itm_mesh_download_indexed(m, vtx.data(), nullptr, nv, faces.data(), nt, nullptr, nullptr, stream);
-  if (rc) return rc;
-  const bool withNormals = nrm && (m->indexedAttrCurrent & ITM_MESH_NORMALS), withColours = col && (m->indexedAttrCurrent & ITM_MESH_COLOURS);
-  if (withNormals) nrm->resize((size_t)nv * 3);
-  if (withColours) col->resize((size_t)nv * 4);
-  if (withNormals || withColours)
-    if ((rc = itm_mesh_download_indexed_attributes(m, withNormals ? nrm->data() : nullptr, withColours ? col->data() : nullptr, nv, &nv, stream))) return rc;
-  return ITM_OK;
-}
-
-// binary_little_endian PLY as itm_mesh_write_ply writes it, with one vertex per distinct position and the faces through the index
+// the PLY and OBJ of the triangle buffer (mesh_files.h) with one vertex per distinct position and the faces through the index
 int itm_mesh_write_ply_indexed(const itm_mesh* m, const char* path, itm_stream stream) {
   if (!m || !path) return set_error(ITM_ERR_INVALID, "null argument");
-  std::vector<float> vtx, nrm;
-  std::vector<uint32_t> faces;
-  std::vector<uint8_t> col;
-  const int rc = fetch_indexed(m, vtx, faces, &nrm, &col, stream);
-  if (rc) return rc;
-  const size_t nv = m->noVertices, nt = m->noIndexedTriangles;
-  const bool withNormals = (m->indexedAttrCurrent & ITM_MESH_NORMALS) != 0, withColours = (m->indexedAttrCurrent & ITM_MESH_COLOURS) != 0;
-  std::string head = "ply\nformat binary_little_endian 1.0\ncomment itm-hip mesh\nelement vertex " + std::to_string((unsigned long long)nv) +
-                     "\nproperty float x\nproperty float y\nproperty float z\n";
-  if (withNormals) head += "property float nx\nproperty float ny\nproperty float nz\n";
-  if (withColours) head += "property uchar red\nproperty uchar green\nproperty uchar blue\n";
-  head += "element face " + std::to_string((unsigned long long)nt) + "\nproperty list uchar int vertex_indices\nend_header\n";
-  const size_t vertexBytes = 12 + (withNormals ? 12 : 0) + (withColours ? 3 : 0);
-  std::vector<uint8_t> body(nv * vertexBytes + nt * 13);
-  uint8_t* o = body.data();
-  for (size_t v = 0; v < nv; ++v) {
-    memcpy(o, &vtx[v * 3], 12); o += 12;
-    if (withNormals) { memcpy(o, &nrm[v * 3], 12); o += 12; }
-    if (withColours) { memcpy(o, &col[v * 4], 3); o += 3; }
-  }
-  for (size_t i = 0; i < nt; ++i) {
-    const int32_t idx[3] = {(int32_t)faces[i * 3 + 2], (int32_t)faces[i * 3 + 1], (int32_t)faces[i * 3]};
-    *o++ = 3;
-    memcpy(o, idx, 12); o += 12;
-  }
-  FILE* f = fopen(path, "wb");
-  if (!f) return set_error(ITM_ERR_INVALID, std::string("cannot create ") + path);
-  bool ok = fwrite(head.data(), 1, head.size(), f) == head.size();
-  ok = (body.empty() || fwrite(body.data(), 1, body.size(), f) == body.size()) && ok;
-  ok = (fclose(f) == 0) && ok;
-  return ok ? ITM_OK : set_error(ITM_ERR_INVALID, std::string("short write to ") + path);
+  FetchedMesh h;
+  const int rc = fetch_indexed(m, true, h, stream);
+  return rc ? rc : file_status(write_ply(h.view, path));
 }
 
-// the format of ITMMesh::WriteOBJ (Objects/ITMMesh.h:34-62) with one "v" line per unique vertex; faces 1-based, winding reversed
 int itm_mesh_write_obj_indexed(const itm_mesh* m, const char* path, itm_stream stream) {
   if (!m || !path) return set_error(ITM_ERR_INVALID, "null argument");
-  std::vector<float> vtx;
-  std::vector<uint32_t> faces;
-  const int rc = fetch_indexed(m, vtx, faces, nullptr, nullptr, stream);
-  if (rc) return rc;
-  FILE* f = fopen(path, "w+");
-  if (!f) return set_error(ITM_ERR_INVALID, std::string("cannot create ") + path);
-  for (size_t v = 0; v < m->noVertices; ++v) fprintf(f, "v %f %f %f\n", vtx[v * 3], vtx[v * 3 + 1], vtx[v * 3 + 2]);
-  for (size_t i = 0; i < m->noIndexedTriangles; ++i) fprintf(f, "f %u %u %u\n", faces[i * 3 + 2] + 1u, faces[i * 3 + 1] + 1u, faces[i * 3] + 1u);
-  const bool ok = fclose(f) == 0;
-  return ok ? ITM_OK : set_error(ITM_ERR_INVALID, std::string("short write to ") + path);
+  FetchedMesh h;
+  const int rc = fetch_indexed(m, false, h, stream);
+  return rc ? rc : file_status(write_obj(h.view, path));
 }
 
 }  // extern "C"

@@ -1,8 +1,10 @@
 // mesh_types.h -- the mesh handle shared by meshing.hip (triangles), mesh_attributes.hip (per-vertex normals and colours) and
 // mesh_index.hip (the indexed form: shared vertices and faces) and mesh_components.hip (its connected components, the fragment filter).
+// The handle's state -- which of those products are current -- is kept here and nowhere else.
 #pragma once
 
 #include "itm_internal.h"
+#include "mesh_files.h"
 #include "volume_device.h"
 
 namespace itm {
@@ -17,10 +19,7 @@ struct ComponentBuffers {
   DeviceBuffer<int32_t> chunkCount;          // flags per chunk of kSweepChunk
   DeviceBuffer<int32_t> ids;                 // the roots, ascending  (the filter: the kept triangles, ascending)
   DeviceBuffer<int32_t> counters;            // [0] flags set, [1] the same after the cap, [2] what the check launch found, [3] kept components
-  void reset() {
-    parent.reset(); vertexComponent.reset(); triangleComponent.reset(); components.reset(); flags.reset(); chunkCount.reset(); ids.reset();
-    counters.reset();
-  }
+  void reset() { *this = ComponentBuffers(); }
 };
 
 }  // namespace itm
@@ -41,11 +40,9 @@ struct itm_mesh {
   itm::DeviceBuffer<unsigned long long> brickBase;   // per brick: triangles generated before it
   itm::DeviceBuffer<int32_t> brickList;      // the bricks that have triangles, ascending
   itm::DeviceBuffer<int32_t> brickCounters;  // [0] number of listed bricks; [2..3] triangles generated (64 bits)
-  bool fromVolume = false;           // the buffer holds the mesh itm_mesh_volume made of a dense scene; itm_mesh_scene clears it
-  // vertex attributes of the triangles the last itm_mesh_scene left in the buffer (mesh_attributes.hip); allocated on first use
+  // vertex attributes of the triangles in the buffer (mesh_attributes.hip); allocated on first use
   itm::DeviceBuffer<float> normals;          // 3 floats per vertex, 3 vertices per triangle, buffer order
   itm::DeviceBuffer<uchar4> colours;         // one per vertex
-  uint32_t attrCurrent = 0;          // ITM_MESH_* bits computed for the buffer's present contents; itm_mesh_scene clears it
   // indexed form of the buffer's present contents (mesh_index.hip); allocated / grown by itm_mesh_index, sized from the counts
   itm::DeviceBuffer<float> vertices;         // 3 floats per unique vertex, in the order of first occurrence in the buffer
   itm::DeviceBuffer<uint32_t> faces;         // 3 vertex indices per triangle, buffer order
@@ -55,21 +52,67 @@ struct itm_mesh {
   itm::DeviceBuffer<uint32_t> indexChunks;   // per chunk of soup vertices: unique vertices first seen there, then exclusive prefix, closed by nV
   itm::DeviceBuffer<int32_t> blockVertex;    // per listed block: its first unique vertex (the vertices first seen in block b are [b], [b + 1])
   uint32_t noVertices = 0, noIndexedTriangles = 0;
-  bool indexCurrent = false;         // the index describes the buffer's present contents; itm_mesh_scene clears it
   // attributes of the unique vertices (itm_mesh_indexed_attributes), independent of the soup's
   itm::DeviceBuffer<float> vertexNormals;    // 3 floats per unique vertex
   itm::DeviceBuffer<uchar4> vertexColours;   // one per unique vertex
-  uint32_t indexedAttrCurrent = 0;   // ITM_MESH_* bits computed for the present index; itm_mesh_scene and itm_mesh_index clear it
   // connected components of the present index (mesh_components.hip); allocated / grown by itm_mesh_components, sized from the counts
   itm::ComponentBuffers comp;
   itm::DeviceBuffer<uint8_t> componentKeep;  // per component: kept by itm_mesh_filter_components? (the host's mask, then the verdict)
   itm::DeviceBuffer<float> packed;           // the kept triangles, packed, before they replace the buffer's contents
   uint32_t noComponents = 0, componentRounds = 0;
-  bool componentsCurrent = false;    // the labelling describes the present index; itm_mesh_scene, itm_mesh_index and the filter clear it
+
+  // ---- which products describe the buffer's present contents ------------------------------------------------------------------------
+  //   soup (the triangle buffer) -+- soup attributes (normals, colours)
+  //                               +- index -+- indexed attributes
+  //                                         +- components
+  // A product is current once the call that computes it has succeeded (empty cases included: they need no device work) and stale from
+  // the moment something above it is rewritten; a call that fails leaves its product stale.  Who rewrites what: itm_mesh_scene /
+  // itm_mesh_volume and, once it starts rewriting, itm_mesh_filter_components the soup; itm_mesh_index the index; itm_mesh_components
+  // the components.  Each function below clears its own row and calls the one for the rows beneath it.
+  void soup_rewritten() { attrCurrent = 0; index_rebuilding(); }
+  void soup_remeshed() { soup_rewritten(); fromVolume = false; }       // itm_mesh_scene: the buffer holds a dense volume's mesh no more
+  void index_rebuilding() { indexCurrent = false; indexedAttrCurrent = 0; components_recomputing(); }
+  void components_recomputing() { componentsCurrent = false; }
+  void meshed_from_volume() { fromVolume = true; }                     // itm_mesh_volume has meshed a dense scene into the buffer
+  void attributes_current(bool indexed, uint32_t what) { (indexed ? indexedAttrCurrent : attrCurrent) |= what; }
+  void index_current() { indexCurrent = true; }
+  void components_current() { componentsCurrent = true; }
+  bool holds_volume_mesh() const { return fromVolume; }
+  uint32_t attributes(bool indexed) const { return indexed ? indexedAttrCurrent : attrCurrent; }   // the ITM_MESH_* bits that are current
+  int require_index() const { return indexCurrent ? ITM_OK : itm::set_error(ITM_ERR_INVALID, "no index for this mesh: itm_mesh_index has not built it since the last itm_mesh_scene"); }
+  int require_components() const {
+    return indexCurrent && componentsCurrent ? ITM_OK : itm::set_error(ITM_ERR_INVALID, "no components for this mesh: itm_mesh_components has not labelled the present index");
+  }
+  // the attributes a download names (by a destination that is not null) are current: the soup's, or those of the present index
+  int require_attributes(bool normals, bool colours, bool indexed) const {
+    if (indexed) { const int rc = require_index(); if (rc) return rc; }
+    const uint32_t missing = ((normals ? ITM_MESH_NORMALS : 0) | (colours ? ITM_MESH_COLOURS : 0)) & ~attributes(indexed);
+    if (!missing) return ITM_OK;
+    return itm::set_error(ITM_ERR_INVALID, std::string(missing & ITM_MESH_NORMALS ? "no normals" : "no colours") +
+        (indexed ? " for the indexed mesh: itm_mesh_indexed_attributes has not computed them since the last itm_mesh_index"
+                 : " for this mesh: itm_mesh_attributes has not computed them since the last itm_mesh_scene"));
+  }
+ private:
+  bool fromVolume = false;           // the buffer holds the mesh itm_mesh_volume made of a dense scene
+  uint32_t attrCurrent = 0;          // ITM_MESH_* bits computed for the soup
+  bool indexCurrent = false;         // vertices / faces / first describe the soup
+  uint32_t indexedAttrCurrent = 0;   // ITM_MESH_* bits computed for the index
+  bool componentsCurrent = false;    // the labelling describes the index
 };
 
 namespace itm {
 
 int launch_mesh_volume_dense(const itm_scene* s, itm_mesh* m, hipStream_t st);   // mesh_dense.hip
+
+// The clamped download: min(count, capacity) elements of `src` to the host, nothing where that is 0 or `dst` is null (the caller synchronises)
+inline hipError_t copy_out(void* dst, const void* src, size_t count, size_t capacity, size_t bytesPerElement, hipStream_t st) {
+  const size_t n = count < capacity ? count : capacity;
+  return (n && dst) ? hipMemcpyAsync(dst, src, n * bytesPerElement, hipMemcpyDeviceToHost, st) : hipSuccess;
+}
+
+// The file writers' two fetchers (meshing.hip, mesh_index.hip; withAttributes: and the attributes that are current); a writer's answer as the library's
+int fetch_soup(const itm_mesh* m, bool withAttributes, FetchedMesh& out, itm_stream stream);
+int fetch_indexed(const itm_mesh* m, bool withAttributes, FetchedMesh& out, itm_stream stream);
+inline int file_status(const std::string& error) { return error.empty() ? ITM_OK : set_error(ITM_ERR_INVALID, error); }
 
 }  // namespace itm

@@ -18,10 +18,7 @@
 //   2. mesh_scan_kernel: exclusive scan of the per-block totals (one workgroup; meshing is an export step, not a frame step).
 //   3. mesh_cells_kernel<WRITE>: the same staging, then every lane interpolates its cell's vertices with the reference's float
 //      operations and writes its triangles at base(block) + offset(cell), i.e. in the reference's order.
-#include <cstdio>
-#include <cstring>
 #include <new>
-#include <vector>
 
 #include "itm_internal.h"
 #include "mc_device.h"
@@ -80,6 +77,17 @@ __global__ void __launch_bounds__(1024) mesh_scan_kernel(int32_t* __restrict__ b
   if (threadIdx.x == 0) store_triangle_totals(totals, generated, maxTriangles);
 }
 
+// the soup on the host, with the attributes that are current where the writer carries them
+int fetch_soup(const itm_mesh* m, bool withAttributes, FetchedMesh& out, itm_stream stream) {
+  uint32_t n = 0;
+  int rc = itm_mesh_info(m, &n, nullptr, nullptr, stream);
+  if (rc) return rc;
+  const uint32_t have = withAttributes ? m->attributes(false) : 0u;
+  out.resize((size_t)n * 3, n, false, have & ITM_MESH_NORMALS, have & ITM_MESH_COLOURS);
+  if ((rc = itm_mesh_download(m, out.positions.data(), n, &n, stream)) || !have) return rc;
+  return itm_mesh_download_attributes(m, out.normals_or_null(), out.colours_or_null(), n, &n, stream);
+}
+
 }  // namespace itm
 
 using namespace itm;
@@ -116,10 +124,7 @@ int itm_mesh_scene(const itm_scene* s, itm_mesh* m, itm_stream stream) {
   if (m->scene != s) return set_error(ITM_ERR_INVALID, "mesh belongs to another scene");
   { const int rc = enter_scene(s, nullptr); if (rc) return rc; }
   hipStream_t st = as_stream(stream);
-  m->attrCurrent = 0;                                          // vertex attributes belong to the mesh that is being replaced
-  m->indexCurrent = false; m->indexedAttrCurrent = 0;          // and so does the indexed form
-  m->componentsCurrent = false;                                // with its components
-  m->fromVolume = false;
+  m->soup_remeshed();                                          // attributes, index and components belong to the mesh that is being replaced
   // mesh->triangles->Clear()
   ITM_HIP(hipMemsetAsync(m->triangles, 0, (size_t)m->maxTriangles * 36, st));
   ITM_HIP(hipMemsetAsync(m->totals, 0, 8, st));
@@ -150,7 +155,7 @@ int itm_mesh_volume(const itm_scene* s, itm_mesh* m, itm_stream stream) {
   if (rc) return rc;
   const int rv = launch_mesh_volume_dense(s, m, as_stream(stream));
   if (rv) return rv;
-  m->fromVolume = true;
+  m->meshed_from_volume();
   return ITM_OK;
 }
 
@@ -170,53 +175,26 @@ int itm_mesh_download(const itm_mesh* m, float* dst_host, uint32_t capacityTrian
   if (!m || !noTotalTriangles) return set_error(ITM_ERR_INVALID, "null argument");
   int rc = itm_mesh_info(m, noTotalTriangles, nullptr, nullptr, stream);
   if (rc) return rc;
-  const uint32_t n = *noTotalTriangles < capacityTriangles ? *noTotalTriangles : capacityTriangles;
-  if (n && !dst_host) return set_error(ITM_ERR_INVALID, "null destination");
+  if (*noTotalTriangles && capacityTriangles && !dst_host) return set_error(ITM_ERR_INVALID, "null destination");
   hipStream_t st = as_stream(stream);
-  if (n) ITM_HIP(hipMemcpyAsync(dst_host, m->triangles, (size_t)n * 36, hipMemcpyDeviceToHost, st));
+  ITM_HIP(copy_out(dst_host, m->triangles, *noTotalTriangles, capacityTriangles, 36, st));
   ITM_HIP(hipStreamSynchronize(st));
   return ITM_OK;
 }
 
-// ITMMesh::WriteOBJ (Objects/ITMMesh.h:34-62): three "v" lines per triangle, then the faces with the winding reversed
+// ITMMesh::WriteOBJ and ITMMesh::WriteSTL of the triangle buffer (mesh_files.h)
 int itm_mesh_write_obj(const itm_mesh* m, const char* path, itm_stream stream) {
   if (!m || !path) return set_error(ITM_ERR_INVALID, "null argument");
-  uint32_t n = 0;
-  int rc = itm_mesh_info(m, &n, nullptr, nullptr, stream);
-  if (rc) return rc;
-  std::vector<float> tri((size_t)n * 9);
-  if ((rc = itm_mesh_download(m, tri.data(), n, &n, stream))) return rc;
-  FILE* f = fopen(path, "w+");
-  if (!f) return set_error(ITM_ERR_INVALID, std::string("cannot create ") + path);
-  for (uint32_t i = 0; i < n; ++i)
-    for (int k = 0; k < 3; ++k) fprintf(f, "v %f %f %f\n", tri[(size_t)i * 9 + 3 * k], tri[(size_t)i * 9 + 3 * k + 1], tri[(size_t)i * 9 + 3 * k + 2]);
-  for (uint32_t i = 0; i < n; ++i) fprintf(f, "f %d %d %d\n", i * 3 + 2 + 1, i * 3 + 1 + 1, i * 3 + 0 + 1);
-  const bool ok = fclose(f) == 0;
-  return ok ? ITM_OK : set_error(ITM_ERR_INVALID, std::string("short write to ") + path);
+  FetchedMesh h;
+  const int rc = fetch_soup(m, false, h, stream);
+  return rc ? rc : file_status(write_obj(h.view, path));
 }
 
-// ITMMesh::WriteSTL (:64-110): binary STL, 80 spaces of header, zero normals, vertices in the order p2, p1, p0
 int itm_mesh_write_stl(const itm_mesh* m, const char* path, itm_stream stream) {
   if (!m || !path) return set_error(ITM_ERR_INVALID, "null argument");
-  uint32_t n = 0;
-  int rc = itm_mesh_info(m, &n, nullptr, nullptr, stream);
-  if (rc) return rc;
-  std::vector<float> tri((size_t)n * 9);
-  if ((rc = itm_mesh_download(m, tri.data(), n, &n, stream))) return rc;
-  FILE* f = fopen(path, "wb+");
-  if (!f) return set_error(ITM_ERR_INVALID, std::string("cannot create ") + path);
-  for (int i = 0; i < 80; ++i) fwrite(" ", 1, 1, f);
-  fwrite(&n, 4, 1, f);
-  const float zero[3] = {0.0f, 0.0f, 0.0f};
-  const short attribute = 0;
-  for (uint32_t i = 0; i < n; ++i) {
-    const float* t = &tri[(size_t)i * 9];
-    fwrite(zero, 4, 3, f);
-    fwrite(t + 6, 4, 3, f); fwrite(t + 3, 4, 3, f); fwrite(t, 4, 3, f);
-    fwrite(&attribute, 2, 1, f);
-  }
-  const bool ok = fclose(f) == 0;
-  return ok ? ITM_OK : set_error(ITM_ERR_INVALID, std::string("short write to ") + path);
+  FetchedMesh h;
+  const int rc = fetch_soup(m, false, h, stream);
+  return rc ? rc : file_status(write_stl(h.view, path));
 }
 
 }  // extern "C"

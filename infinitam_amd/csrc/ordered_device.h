@@ -10,6 +10,8 @@
 //
 // CARRY SCAN.  carry_scan: the exclusive prefix of an array of any length by ONE workgroup (mesh_index.hip, meshing.hip).
 //
+// LOWER BOUND.  lower_bound: the position of a value in an ascending array, where a block's run starts after a compaction.
+//
 // (The one-launch visible list and the allocation sweep -- visible_list_kernel, sweep_chunk, merge_sweep_kernel -- spell the same
 // steps out between their own early loads and look-backs and do not go through this header.)
 #pragma once
@@ -115,6 +117,18 @@ __device__ inline Carry carry_scan(int n, Load&& load, Store&& store) {
     carry += (Carry)total;
   }
   return carry;
+}
+
+// The lower bound of `value` in the ascending a[0 .. n), T = uint32_t or int32_t holding non-negative numbers: how many elements are
+// below it.  (Block starts after a compaction: mesh_index_blocks_kernel, components_blocks_kernel.)
+template <class T>
+__device__ inline uint32_t lower_bound(const T* __restrict__ a, uint32_t n, uint32_t value) {
+  uint32_t lo = 0u, hi = n;
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if ((uint32_t)a[mid] < value) lo = mid + 1u; else hi = mid;
+  }
+  return lo;
 }
 
 // The ordered compaction as a launch, F = uint8_t or int32_t: ids[0 .. min(total, cap)) = the indices i < n with flags[i] != 0, ascending;
