@@ -76,8 +76,11 @@ def test_the_stager_refuses_what_would_lose_or_reorder_a_frame(hip):
         hip.check(hip.fn["depth_stager_destroy"](g), "destroy")
 
 
+CALIBS = [(1, 0.001, 0.0), (1, 0.0005, 0.01), (0, 1135.09, 0.0819141)]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("calib", [(1, 0.001, 0.0), (1, 0.0005, 0.01), (0, 1135.09, 0.0819141)], ids=["affine mm", "affine with offset", "kinect disparity"])
+@pytest.mark.parametrize("calib", CALIBS, ids=["affine mm", "affine with offset", "kinect disparity"])
 @pytest.mark.parametrize("pinned", [True, False], ids=["page-locked host memory (copy kernel)", "pageable host memory (runtime copy)"])
 def test_the_copy_that_also_converts_gives_update_views_depth_image(hip, calib, pinned):
     """itm_depth_stager_set_conversion: the float depth image a slot carries must be, bit for bit, what itm_update_view makes of the same raw
@@ -90,6 +93,39 @@ def test_the_copy_that_also_converts_gives_update_views_depth_image(hip, calib, 
         r.reshape(-1)[idx] = rng.choice(np.array([0, -5, 32001, 32767, -32768, 1, 32000], np.int16), 400)
         if calib_type == 0:
             r.reshape(-1)[idx[:50]] = 1135      # c0 - raw == 0.09: huge depths; and the exact zero of the denominator cannot occur for integers
+    converting_copy(hip, calib, pinned, W, H, raws, intr, W * H // 2 if calib_type == 1 else 1000, 50)
+
+
+def every_int16_frames(w, h, n):
+    """n frames that run through the int16 values with an odd stride (every value, where the frame has 65 536 samples), the samples the
+    conversions reject, clamp or divide by nearly nothing in front"""
+    special = np.array([0, -5, 32001, 32767, -32768, 1, 32000, 1135, 1134, 1136], np.int16)
+    out = []
+    for k in range(n):
+        r = ((np.arange(w * h, dtype=np.int64) * (2 * k + 1) + 7919 * k) & 0xffff).astype(np.uint16).view(np.int16).copy()
+        r[:min(special.size, r.size)] = special[:r.size]
+        out.append(np.ascontiguousarray(r.reshape(h, w)))
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("size", [(8, 8), (256, 256), (328, 101), (640, 480), (37, 23)], ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("pinned", [True, False], ids=["page-locked host memory", "pageable host memory"])
+def test_the_copy_that_also_converts_at_every_length_of_its_unrolled_loop(hip, pinned, size):
+    """The copy kernel moves 16-byte vectors, 16 workgroups x 256 lanes x 8 rounds at a stride of 4 096: 8 x 8 is 8 vectors (less than a
+    wave), 256 x 256 is 8 192 (rounds 0 and 1, both full), 328 x 101 is 4 141 (round 1 for 45 lanes of the first workgroup), 640 x 480
+    is 38 400 (all eight rounds and a second trip, the last partly), and 37 x 23 is 1 702 bytes, no multiple of 16: page-locked
+    memory takes the runtime's copy.  Same assertion as above, every calibration."""
+    w, h = size
+    if (w, h) == (37, 23):
+        assert (w * h * 2) % 16 != 0
+    intr = synth.intrinsics_for(w, h)
+    for calib in CALIBS:
+        converting_copy(hip, calib, pinned, w, h, every_int16_frames(w, h, 3), intr, 4, 3)
+
+
+def converting_copy(hip, calib, pinned, W, H, raws, intr, min_valid, min_rejected):
+    calib_type, c0, c1 = calib
     intr_c = (C.c_float * 4)(*intr)
     g = C.c_void_p()
     hip.check(hip.fn["depth_stager_create"](W, H, 3, C.byref(g)), "create")
@@ -123,7 +159,7 @@ def test_the_copy_that_also_converts_gives_update_views_depth_image(hip, calib, 
             want = direct.numpy()
             assert np.array_equal(got_raw, raws[k]), k
             assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (k, np.nonzero(got != want)[0][:5])
-            assert np.count_nonzero(got > 0) > (W * H // 2 if calib_type == 1 else 1000) and np.count_nonzero(got == -1.0) >= 50
+            assert np.count_nonzero(got > 0) > min_valid and np.count_nonzero(got == -1.0) >= min_rejected
         # a conversion cannot be changed under frames that wait in the ring
         hip.check(hip.fn["depth_stager_upload"](g, host[0]), "upload")
         assert hip.fn["depth_stager_set_conversion"](g, 1, 0.001, 0.0, intr[0]) == capi.ERR_INVALID

@@ -115,7 +115,7 @@ def test_filter_hip_vs_oracle(hip, oracle):
     a, b = run_filter(hip, img), run_filter(oracle, img)
     assert np.array_equal(a <= 0, b <= 0)                      # holes and border identical
     m = b > 0
-    assert np.abs(a[m] - b[m]).max() <= 1e-6 * np.abs(b[m]).max()
+    assert (np.abs(a[m] - b[m]) <= 1e-6 * np.abs(b[m])).all()      # of the pixel's own value (test_viewbuilder_terms.py: 8 ulp and a proof bound)
 
 
 @pytest.mark.gpu
