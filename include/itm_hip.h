@@ -800,6 +800,57 @@ typedef struct itm_merge_stats {
 } itm_merge_stats;
 int ITM_FN(scene_merge)(itm_scene* dst, const itm_scene* src, const int32_t* srcSlots_dev, int n, itm_merge_stats* stats, itm_stream stream);
 
+/* ---- level of detail: resamples scene `src` into scene `dst` of TWICE the voxel size on the same GPU ---------------------------------
+ * The reference has no counterpart (it has one resolution per scene and decimates nothing).  A TSDF is low-passed and every second
+ * sample kept; whatever reads a scene -- meshing, ray cast, queries, the distance field, save, the exchange -- then works on the coarse
+ * scene unchanged.  Defined on integers and a fixed tap order: the kernels reproduce it bit for bit.
+ * Requirements, else ITM_ERR_INVALID with the reason in itm_last_error and dst untouched: neither scene NULL, dst != src, same device,
+ * same voxelType and indexType, dst's voxelSize bit-equal to 2.0f * src's, mu bit-equal (sdf is stored as a fraction of mu: values carry
+ * over only if it is the same; maxW may differ: dst's is used), dst not holding the block requests of a frame issued ahead, and the
+ * slot-list rules of itm_scene_merge (srcSlots_dev: NULL = every table slot of src, else a DEVICE list of n slots in any order,
+ * duplicates count once; an id outside src's table, n < 0, or a list with dense scenes: ITM_ERR_INVALID).  Dense scenes need NOT agree in
+ * denseSize / denseOffset.  Recorded calls of both scenes are launched first; src is never written.
+ *
+ * Geometry.  A voxel at integer coordinate p stands for the point p * voxelSize, so coarse voxel q stands for fine voxel 2q, and fine
+ * block b belongs to coarse block B = b >> 1 per component (arithmetic shift: -1 -> -1, -3 -> -2).
+ *
+ * The coarse voxel at q, for both index types.  Taps k = (kx, ky, kz) in {-1, 0, 1}^3, taken with kz outermost and kx innermost, each
+ * ascending; c_k = (2 - |kx|)(2 - |ky|)(2 - |kz|) (they sum to 64); t_k = readVoxel(src, 2q + k) (DeviceAgnostic/
+ * ITMRepresentationAccess.h:85-142) over the WHOLE of src, whatever the slot list selects; an absent voxel, an entry with ptr < 0 or a
+ * block pointer outside src's pool reads as TVoxel() with weight 0.
+ *   depth   a_k = c_k * w_depth(t_k), A = sum a_k.  A == 0: sdf = the initial value (32767 / 1.0f), w_depth = 0.  Otherwise
+ *           w_depth' = min(dst maxW, 255, max(1, (A + 32) div 64)) and
+ *             short sdf: S = sum a_k * sdf_k (fits int32: 64 * 255 * 32767 < 2^31), sdf' = sgn(S) * ((2|S| + A) div 2A) -- to nearest,
+ *                        halves away from zero;
+ *             float sdf: S = sum (double)a_k * (double)sdf_k, summed in double in the tap order above starting from +0.0 (every product
+ *                        is exact, so contraction cannot change a bit), sdf' = (float)(S / (double)A).
+ *   colour  (the two types that store it) b_k = c_k * w_color(t_k), Bc = sum b_k.  Bc == 0: clr = 0, w_color = 0.  Otherwise each channel
+ *           is (2 * sum b_k * clr_k + Bc) div 2Bc and w_color' = min(dst maxW, 255, max(1, (Bc + 32) div 64)).
+ * Property: where the 27 taps have equal weight and sdf is affine in the coordinates, sdf' = sdf(2q) and w' = w exactly.
+ *
+ * Hash index, sequential definition:
+ *  1. Participants as in itm_scene_merge step 1: the selected entries of src with ptr >= 0, in ascending src slot order; selected entries
+ *     with ptr == -1 count in srcWithoutBlock.
+ *  2. Rounds: itm_scene_merge step 2 word for word, with the participant's COARSE position b >> 1 in the place of its position.  Up to
+ *     eight participants share a position: one wins the target, the others find the entry in the next round.  rounds, considered,
+ *     alreadyPresent, allocated and unserved mean what they mean there.
+ *  3. D = the set of dst entries that hold the coarse position of at least one participant.  Those with ptr == -1 count in dstSwappedOut
+ *     and are left alone; for the others all 512 voxels are OVERWRITTEN with the coarse voxel above, `written` is their number (an entry
+ *     whose block pointer lies outside dst's pool -- only an uploaded table can name one -- is left alone and not counted).  Every other
+ *     block of dst keeps its content.  Overwrite, not combine: CombineVoxelInformation with an empty partner is not the identity in
+ *     float.  A coarse block is allocated only through b >> 1: coarse voxel 8B + 7 of a block reaches half a voxel into the fine blocks
+ *     beyond, but a coarse block that no participant maps to is not created for that half voxel of dilation -- it is dropped.
+ *  4. The occupancy bits, the directories and the sdf mirror of dst are what itm_upload of the same table and voxels would rebuild; the
+ *     request keys are zero again.  dst's render states, visible lists and swap states are not touched.
+ * Dense index: every cell of dst is overwritten with the coarse voxel at q = cell + dst's denseOffset; taps go through the dense
+ * readVoxel of src, outside src's array a tap is absent; considered = written = 1.
+ * Other factors: call it again through a third scene.  Synchronises `stream` once per round and once for the statistics; the resampling
+ * launch itself is enqueued.  `stats` (host) may be NULL. */
+typedef struct itm_coarsen_stats {
+  int32_t rounds, considered, alreadyPresent, allocated, written, unserved, srcWithoutBlock, dstSwappedOut;
+} itm_coarsen_stats;
+int ITM_FN(scene_coarsen)(itm_scene* dst, const itm_scene* src, const int32_t* srcSlots_dev, int n, itm_coarsen_stats* stats, itm_stream stream);
+
 /* ---- scene queries: the volume asked at caller-supplied points and along caller-supplied rays -------------------------------------
  * The reference makes these reads only from inside its engines, per pixel; here the work item is the caller's.  Both calls launch the
  * scene's recorded calls first, read the scene only, take DEVICE pointers and enqueue one launch on `stream` (no synchronisation).

@@ -313,6 +313,28 @@ class ITMSceneMergeEngine_HIP {
   }
 };
 
+// Level of detail (itm_scene_coarsen; no reference class): resamples `src` into `dst`, a scene of TWICE the voxel size and the same mu on
+// the same GPU -- the blocks of dst come from the reference's two-phase allocation with src's block positions halved, every coarse voxel
+// is the weighted 3 x 3 x 3 tent over the fine voxels around it, and the blocks touched are overwritten.  srcVisible: a render state of
+// src whose visible list selects the blocks that take part (nullptr: every block of src).  dst's render states are not touched.
+template <class TVoxel, class TIndex>
+class ITMSceneCoarsenEngine_HIP {
+ public:
+  itm_stream stream = nullptr;
+  void CoarsenScene(ITMScene<TVoxel, TIndex>* dst, const ITMScene<TVoxel, TIndex>* src, const ITMRenderState* srcVisible = nullptr, itm_coarsen_stats* stats = nullptr) {
+    const int32_t* slots = nullptr;
+    int n = 0;
+    if (srcVisible) {
+      itm_counters c;
+      check(itm_get_counters(src->handle, srcVisible->handle, &c, stream), "CoarsenScene (visible list)");
+      slots = (const int32_t*)itm_buffer_ptr(src->handle, srcVisible->handle, ITM_BUF_VISIBLE_IDS);
+      n = c.noVisibleEntries;
+      if (!slots) throw std::runtime_error("CoarsenScene: the render state has no visible list");
+    }
+    check(itm_scene_coarsen(dst->handle, src->handle, slots, n, stats, stream), "CoarsenScene");
+  }
+};
+
 // Scene queries (itm_scene_query_points / itm_scene_cast_rays; the reference makes these reads only per pixel, inside its engines):
 // readFromSDF_float_interpolated, computeSingleNormalFromSDF, readFromSDF_color4u_interpolated at caller-supplied points, castRay along
 // caller-supplied segments.  All pointers are DEVICE memory; one launch on `stream`, nothing is synchronised.
@@ -768,6 +790,11 @@ class ITMMainEngine_HIP {
   void *depthBuf = nullptr, *scratchBuf = nullptr, *normalBuf = nullptr, *sigmaBuf = nullptr, *pointsBuf = nullptr, *coloursBuf = nullptr;
   bool fusionActive = true, mainProcessingActive = true;
   itm_mesh* exportMesh = nullptr;      // created by the first SaveSceneTo* call
+  // SaveSceneToCoarsePLY: the scene at twice the voxel size and its mesh, created by the first call
+  int localBlockNum_;
+  ITMSceneParams coarseParams;
+  ITMScene<TVoxel, TIndex>* coarseScene = nullptr;
+  itm_mesh* coarseMesh = nullptr;
   ITMRenderState* renderState_freeview = nullptr;      // created by the first free-camera GetImage
   void* depthImageBuf = nullptr;                       // device uchar4 of the depth size: the coloured depth / uncertainty image of GetImage
   ITMRelocaliser_HIP* relocaliser = nullptr;           // settings.useRelocalisation
@@ -784,7 +811,8 @@ class ITMMainEngine_HIP {
   // calibType / c0 / c1: ITMDisparityCalib (0 = TRAFO_KINECT, 1 = TRAFO_AFFINE); sizes as ITMMainEngine's imgSize_rgb / imgSize_d
   ITMMainEngine_HIP(const ITMLibSettings& settings_, const ITMSceneParams& params, const ITMRGBDCalib& calib, Vector2i imgSize_rgb, Vector2i imgSize_d,
                     int calibType = 1, float c0 = 0.001f, float c1 = 0.0f, int localBlockNum = 0)
-      : settings((check_settings(settings_), settings_)), sceneParams(params), scene(&sceneParams, localBlockNum), visualisationEngine(&scene) {
+      : settings((check_settings(settings_), settings_)), sceneParams(params), scene(&sceneParams, localBlockNum), visualisationEngine(&scene),
+        localBlockNum_(localBlockNum), coarseParams(params.mu, params.maxW, 2.0f * params.voxelSize, params.viewFrustum_min, params.viewFrustum_max, params.stopIntegratingAtMaxW != 0) {
     view.calib = calib;
     view.depthSize = imgSize_d; view.rgbSize = imgSize_rgb;
     const size_t P = (size_t)imgSize_d.x * imgSize_d.y;
@@ -830,6 +858,7 @@ class ITMMainEngine_HIP {
     delete poseQuality;
     delete relocaliser;
     itm_mesh_destroy(exportMesh);
+    itm_mesh_destroy(coarseMesh); delete coarseScene;
     delete renderState_freeview; itm_dev_free(depthImageBuf);
     delete renderState_live; delete trackingController; delete tracker; delete depthTracker; delete colourTracker; delete renTracker; delete wicpTracker; delete viewBuilder;
     for (void* p : {depthBuf, scratchBuf, normalBuf, sigmaBuf, pointsBuf, coloursBuf}) itm_dev_free(p);
@@ -850,6 +879,11 @@ class ITMMainEngine_HIP {
   // states and `other` stay as they are: the merged blocks are seen by the next ProcessFrame whose view holds them.
   void MergeSceneFrom(const ITMMainEngine_HIP& other, itm_merge_stats* stats = nullptr) {
     ITMSceneMergeEngine_HIP<TVoxel, TIndex>().MergeScene(&scene, &other.scene, nullptr, stats);
+  }
+  // Resamples this engine's scene into `coarse`, a scene of twice the voxel size and the same mu (itm_scene_coarsen).  This engine's
+  // scene, tracking state and render states stay as they are.
+  void CoarsenSceneInto(ITMScene<TVoxel, TIndex>* coarse, itm_coarsen_stats* stats = nullptr) {
+    ITMSceneCoarsenEngine_HIP<TVoxel, TIndex>().CoarsenScene(coarse, &scene, nullptr, stats);
   }
   // The fused volume asked at the caller's own points / along the caller's own rays (ITMSceneQueryEngine_HIP; device pointers)
   void QueryPoints(const float* points, uint32_t n, const itm_query_out& out, int units = ITM_QUERY_METRES) const {
@@ -1148,6 +1182,20 @@ class ITMMainEngine_HIP {
     check(itm_mesh_index(exportMesh, nullptr), "itm_mesh_index");
     check(itm_mesh_indexed_attributes(scene.handle, exportMesh, ITM_MESH_NORMALS | (colour ? ITM_MESH_COLOURS : 0), nullptr), "itm_mesh_indexed_attributes");
     check(itm_mesh_write_ply_indexed(exportMesh, fileName, nullptr), "WriteIndexedPLY");
+  }
+  // A lower level of detail of SaveSceneToIndexedPLY: the scene is resampled into one of twice the voxel size that the engine owns
+  // (created by the first call with the same mu, maxW and index configuration; reset and refilled by every call), and THAT scene is
+  // meshed (itm_mesh_volume), indexed and written with the attributes read from it
+  void SaveSceneToCoarsePLY(const char* fileName) {
+    const bool colour = TVoxel::kType == ITM_VOXEL_S_RGB || TVoxel::kType == ITM_VOXEL_F_RGB;
+    if (!coarseScene) coarseScene = new ITMScene<TVoxel, TIndex>(&coarseParams, localBlockNum_);
+    ITMSceneReconstructionEngine_HIP<TVoxel, TIndex>().ResetScene(coarseScene);
+    CoarsenSceneInto(coarseScene);
+    if (!coarseMesh) check(itm_mesh_create(coarseScene->handle, 0, &coarseMesh), "itm_mesh_create");
+    check(itm_mesh_volume(coarseScene->handle, coarseMesh, nullptr), "MeshVolume");
+    check(itm_mesh_index(coarseMesh, nullptr), "itm_mesh_index");
+    check(itm_mesh_indexed_attributes(coarseScene->handle, coarseMesh, ITM_MESH_NORMALS | (colour ? ITM_MESH_COLOURS : 0), nullptr), "itm_mesh_indexed_attributes");
+    check(itm_mesh_write_ply_indexed(coarseMesh, fileName, nullptr), "WriteIndexedPLY");
   }
 
  private:

@@ -183,6 +183,15 @@ class MergeStats(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class CoarsenStats(C.Structure):
+    """itm_coarsen_stats (include/itm_hip.h, itm_scene_coarsen)."""
+    _fields_ = [(n, C.c_int32) for n in ("rounds", "considered", "alreadyPresent", "allocated", "written", "unserved",
+                                         "srcWithoutBlock", "dstSwappedOut")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class QueryOut(C.Structure):
     """itm_query_out (include/itm_hip.h, itm_scene_query_points): device pointers, NULL = not wanted."""
     _fields_ = [(n, C.c_void_p) for n in ("sdf", "sdf_nearest", "gradient", "normal", "colour", "weight", "flags")]
@@ -430,6 +439,8 @@ _HOST_IO_SIGS = {
     "normal_to_uchar4": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     # scene merge (product only: no reference engine merges scenes)
     "scene_merge": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(MergeStats), _P]),
+    # level of detail (product only: the reference has one resolution per scene)
+    "scene_coarsen": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(CoarsenStats), _P]),
     # scene queries at caller-supplied points / along caller-supplied rays (product only: the reference reads per pixel, inside its engines)
     "scene_query_points": (C.c_int, [_P, _P, C.c_uint32, C.c_int, C.POINTER(QueryOut), _P]),
     "scene_cast_rays": (C.c_int, [_P, _P, C.c_uint32, _P, _P]),
@@ -728,25 +739,34 @@ class Scene:
         self.be.check(self.be.fn["global_cache_get"](_P(self.h), int(entry), out.ctypes.data_as(_P), C.byref(has)), "global_cache_get")
         return out if has.value else None
 
-    def merge_from(self, src: "Scene", slots=None, stream=None) -> dict:
-        """itm_scene_merge: fuses `src` into this scene on the GPU and returns the statistics.  slots: None (every slot of src's
-        table), a DevBuffer of int32 table slots of src, or a numpy array of them (uploaded first)."""
-        keep = None
+    def _slot_list(self, slots, stream):
+        """(device pointer, count, buffer to close afterwards) of a slot list: None, a DevBuffer of int32 or a numpy array (uploaded)."""
         if slots is None:
-            ptr, n = None, 0
-        elif isinstance(slots, DevBuffer):
-            ptr, n = slots.ptr, slots.nbytes // 4
-        else:
-            arr = np.ascontiguousarray(np.asarray(slots, np.int32).reshape(-1))
-            keep = self.be.to_backend(arr, stream)
-            ptr, n = keep.ptr, len(arr)
-        st = MergeStats()
-        rc = self.be.fn["scene_merge"](_P(self.h), _P(src.h), _P(ptr), n, C.byref(st), _P(stream))
+            return None, 0, None
+        if isinstance(slots, DevBuffer):
+            return slots.ptr, slots.nbytes // 4, None
+        arr = np.ascontiguousarray(np.asarray(slots, np.int32).reshape(-1))
+        keep = self.be.to_backend(arr, stream)
+        return keep.ptr, len(arr), keep
+
+    def _slot_call(self, name, stats, src, slots, stream) -> dict:
+        ptr, n, keep = self._slot_list(slots, stream)
+        rc = self.be.fn[name](_P(self.h), _P(src.h), _P(ptr), n, C.byref(stats), _P(stream))
         if keep is not None:
             self.be.sync(stream)
             keep.close()
-        self.be.check(rc, "scene_merge")
-        return st.as_dict()
+        self.be.check(rc, name)
+        return stats.as_dict()
+
+    def merge_from(self, src: "Scene", slots=None, stream=None) -> dict:
+        """itm_scene_merge: fuses `src` into this scene on the GPU and returns the statistics.  slots: None (every slot of src's
+        table), a DevBuffer of int32 table slots of src, or a numpy array of them (uploaded first)."""
+        return self._slot_call("scene_merge", MergeStats(), src, slots, stream)
+
+    def coarsen_from(self, src: "Scene", slots=None, stream=None) -> dict:
+        """itm_scene_coarsen: resamples `src` into this scene, which has twice src's voxel size, on the GPU and returns the statistics.
+        slots: as merge_from."""
+        return self._slot_call("scene_coarsen", CoarsenStats(), src, slots, stream)
 
     def query_points(self, points, units="metres", want=("sdf", "gradient"), stream=None) -> dict:
         """itm_scene_query_points: the outputs named in `want` (QUERY_OUTPUTS) at float32 points [n, 3] in "metres" or "voxels", as a
