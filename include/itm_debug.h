@@ -41,6 +41,7 @@ extern "C" {
 #define ITM_DEBUG_FAIL_ALLOCATION 28             /* n > 0: the n-th allocation the library attempts from now on (device or pinned memory) fails with out-of-memory before the runtime is called, then the key clears itself; 0 = off */
 #define ITM_DEBUG_POSE_QUALITY_ROWS 29            /* itm_pose_quality_evaluate: a wave covers 64 x 1 pixels of a row instead of an 8 x 8 tile (same counts and residual image; the sums are added in another order) */
 #define ITM_DEBUG_MESH_COMPONENTS_PER_LANE 30      /* itm_mesh_components: the statistics with one atomic per lane instead of one per wave segment (lanes of a wave that share a component aggregate first) */
+#define ITM_DEBUG_MESH_SMOOTH_SCATTER 31            /* itm_mesh_smooth: every pass as a scatter -- one lane per proper triangle adds its corners into per-vertex int64 accumulators with 64-bit integer atomics, a second kernel applies the step -- instead of the gather over the adjacency rows (same bits by construction) */
 int ITM_FN(debug_set)(int key, int value);
 /* Everything the library allocates passes through one pair of functions (csrc/device_memory.h): out = {live allocations, live bytes,
  * allocations attempted since the library was loaded}, device and pinned memory together, process-wide.  Memory handed out by
@@ -79,6 +80,17 @@ int ITM_FN(debug_ordered_compact)(const void* flags_host, int elemBytes, int n, 
 int ITM_FN(debug_mesh_components)(const uint32_t* faces_host, uint32_t noTriangles, uint32_t noVertices, uint32_t* vertexComponent_host,
                                   itm_mesh_component* components_host, uint32_t capComponents, uint32_t* noComponents, uint32_t* rounds,
                                   itm_stream stream);
+/* itm_mesh_smooth on caller-supplied arrays (the triangle buffer cannot be uploaded): vertices_host holds noVertices x float[3],
+ * faces_host noTriangles x 3 vertex indices < noVertices (an index >= noVertices: ITM_ERR_INVALID); the product's adjacency / topology /
+ * quantise / pass / dequantise kernels run on them.  vertices_out_host receives the noVertices smoothed positions, flags_out_host (may be
+ * NULL) one byte per vertex: bit 0 irregular, bit 1 isolated.  A refused call (also a coordinate out of range or not finite) writes
+ * nothing into either.  With cfg->steps == 0 vertices_out_host receives the input.  All pointers are HOST memory.
+ * Cost: the multiplicity count of a row of n entries is n^2 comparisons, by one lane up to 128 entries and by one wave (n^2 / 64 per
+ * lane) above.  Marching-cubes meshes stay at or below 40 entries; a hand-made apex of 10 000 entries is 10^8 comparisons, some
+ * milliseconds, and the time grows with the square: keep the rows handed to this hook below some 10^5 entries. */
+int ITM_FN(debug_mesh_smooth)(const float* vertices_host, uint32_t noVertices, const uint32_t* faces_host, uint32_t noTriangles,
+                              const itm_mesh_smooth_config* cfg, float* vertices_out_host, uint8_t* flags_out_host,
+                              itm_mesh_smooth_stats* stats, itm_stream stream);
 
 /* Read-only probes of the acceleration cubes of a hash scene (block directory, slot directory, sdf mirror: itm_types.h).  Both launch
  * the scene's recorded, unflushed engine calls first, as a download does, and only read; a scene without directories, without a mirror

@@ -715,6 +715,63 @@ int ITM_FN(mesh_download_components)(const itm_mesh* mesh, uint32_t* vertexCompo
  * indexed attributes and the components are stale.  Keeping nothing leaves a valid empty mesh.  Synchronises `stream`. */
 int ITM_FN(mesh_filter_components)(itm_mesh* mesh, uint32_t minTriangles, const uint8_t* keep_host, uint32_t noKeep,
                                    uint32_t* keptTriangles, uint32_t* keptComponents, itm_stream stream);
+/* Mesh smoothing: lambda|mu (Taubin) or plain Laplacian passes over the present index, IN FIXED POINT (the reference has none; a float
+ * umbrella sum over atomics or an unordered neighbour list would depend on arrival order, see the remark on surface area above).  The
+ * topology does not change: faces, first, the per-block ranges, all counts and itm_mesh_info stay what they are; only positions move.
+ * Defined on the present index, noVertices vertices v[k] (float[3]) and noTriangles faces (a, b, c), by this sequential definition:
+ *   entries   a triangle whose three indices are pairwise distinct gives each of its corners one ENTRY for each of its other two
+ *             corners; a triangle with two equal indices (welding produces them; they have no area) gives nothing.  L(k) = the multiset
+ *             of the entries of vertex k, n(k) = |L(k)| = twice the number of its proper triangles.
+ *   irregular k is irregular iff some vertex occurs in L(k) a number of times other than 2: k lies on an edge named by one triangle (a
+ *             border) or by three or more (non-manifold).
+ *   isolated  k is isolated iff n(k) == 0.
+ *   moving    k is moving iff it is not isolated and not (ITM_MESH_SMOOTH_PIN_IRREGULAR set and k irregular).  On a moving vertex of a
+ *             pinned run every neighbour has multiplicity 2: the operator there is exactly the uniform umbrella.  With the flag clear,
+ *             border vertices move under the incidence-weighted umbrella.
+ *   quantise  x[k] = (int32) rint((double) v[k] / (double) quantum) per coordinate, ties to even, for EVERY vertex.  A coordinate of any
+ *             vertex that is not finite or has |rint(..)| > 2^30: ITM_ERR_INVALID, the mesh and its state exactly as before.
+ *   pass      with factor f (Q16; pass i = 0 .. steps - 1 uses lambdaQ16 for even i, muQ16 for odd i), all vertices at once from the
+ *             previous iterate (Jacobi).  For a moving k, per coordinate, in int64:
+ *               S = sum over j in L(k) of x[j],  a = S - n * x[k]
+ *               d = floor((2 a + n) / (2 n))                   the mean offset, rounded half up
+ *               s = (f * d + 32768) >> 16                      an arithmetic shift: floor, half up
+ *               x'[k] = clamp(x[k] + s, -2^30, 2^30)
+ *             (no intermediate reaches 2^63 for any n < 2^32).  A vertex that is not moving keeps x.
+ *   result    a moving vertex gets (float)((double) x * (double) quantum); every other vertex keeps its own 96 bits (-0.0f included).
+ *             Then the triangle buffer is rewritten, soup[3 i + j] = vertices[faces[i][j]] for the noTriangles indexed triangles, so
+ *             "vertices[faces] is the soup bit for bit" still holds.
+ *   steps==0  the statistics only: positions are not read (no range check) and nothing is changed, the state included.
+ * Everything is an integer or rounded once from one: the result does not depend on the order in which lanes ran, on the order inside an
+ * adjacency row or on the kernel form, and is compared bit for bit.
+ * stats (may be NULL): noVertices; noMoving, noIrregular, noIsolated = the numbers of vertices with that property (irregular counted
+ * whether or not the flag pins them); maxEntries = max n(k); steps = the passes run.  An empty index: zero stats and no error.
+ * Refusals (ITM_ERR_INVALID, the mesh untouched): steps > ITM_MESH_SMOOTH_MAX_STEPS (every pass is a launch queued before the call's
+ * one wait: the cap keeps a garbage word from queueing billions); |lambdaQ16| or |muQ16| > 65536; a quantum that is not finite or not
+ * > 0; non-zero reserved words; unknown flag bits; a stale or missing index.  A call that cannot get its memory (ITM_ERR_DEVICE) keeps
+ * none of it and leaves vertices, triangle buffer and state as they were.  A call that fails on the device AFTER its passes were queued
+ * (ITM_ERR_DEVICE) may have moved the positions: the state is then that of a call that succeeded.
+ * State after a call with steps > 0 that succeeded: the index STAYS current -- it is the mesh's topology, and first[k] still names a
+ * soup vertex that holds vertices[k] -- but two distinct vertices may now coincide in position, so a fresh itm_mesh_index could weld them
+ * (and number the vertices anew).  The soup's attributes, the indexed attributes and the components (their boxes are no longer true)
+ * are stale; whether the buffer holds a dense volume's mesh is unchanged.  itm_mesh_attributes / itm_mesh_indexed_attributes serve the
+ * moved vertices (a vertex that has left its block's neighbourhood reads through the hash).  Synchronises `stream`, as itm_mesh_index. */
+#define ITM_MESH_SMOOTH_PIN_IRREGULAR 1
+#define ITM_MESH_SMOOTH_MAX_STEPS 65536
+typedef struct itm_mesh_smooth_config {
+  uint32_t steps;       /* single passes, at most ITM_MESH_SMOOTH_MAX_STEPS; pass i uses lambdaQ16 for even i, muQ16 for odd i */
+  int32_t lambdaQ16;    /* factor * 65536, |factor| <= 1 */
+  int32_t muQ16;        /* Taubin: negative, |mu| > lambda; plain Laplacian: muQ16 == lambdaQ16 */
+  float quantum;        /* metres per fixed-point unit, > 0 and finite */
+  uint32_t flags;       /* ITM_MESH_SMOOTH_PIN_IRREGULAR */
+  uint32_t reserved[3]; /* 0 */
+} itm_mesh_smooth_config; /* 32 bytes */
+typedef struct itm_mesh_smooth_stats {
+  uint32_t noVertices, noMoving, noIrregular, noIsolated, maxEntries, steps, reserved[2];
+} itm_mesh_smooth_stats;  /* 32 bytes */
+/* host only: steps 20, lambda 0.5 (32768), mu -0.53 (-34734), quantum = voxelSize / 1024, ITM_MESH_SMOOTH_PIN_IRREGULAR set.
+ * voxelSize not finite or not > 0: ITM_ERR_INVALID. */
+int ITM_FN(mesh_smooth_default_config)(float voxelSize, itm_mesh_smooth_config* out);
+int ITM_FN(mesh_smooth)(itm_mesh* mesh, const itm_mesh_smooth_config* cfg, itm_mesh_smooth_stats* stats, itm_stream stream);
 
 /* ---- multi-stream exchange (BASELINE configs[3]) ------------------------------------------------------------------
  * One depth stream per GPU; fusion needs no collective.  Per frame every rank publishes the record of itm_export_visible_record

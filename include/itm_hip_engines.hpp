@@ -14,6 +14,7 @@
 // errors become std::runtime_error (the reference prints and exit(-1)s: ORUtils/CUDADefines.h:27-36).
 #pragma once
 
+#include <cmath>
 #include <cstring>
 #include <stdexcept>
 #include <string>
@@ -1173,15 +1174,14 @@ class ITMMainEngine_HIP {
   // SaveSceneToIndexedPLY without the floating fragments: the mesh is indexed, its connected components are labelled
   // (itm_mesh_components) and those with fewer than minTriangles triangles dropped (itm_mesh_filter_components); what is left is
   // indexed again and written with its attributes
-  void SaveSceneToCleanPLY(const char* fileName, uint32_t minTriangles) {
-    const bool colour = TVoxel::kType == ITM_VOXEL_S_RGB || TVoxel::kType == ITM_VOXEL_F_RGB;
-    MeshForExport(0);
-    check(itm_mesh_index(exportMesh, nullptr), "itm_mesh_index");
-    check(itm_mesh_components(exportMesh, nullptr), "itm_mesh_components");
-    check(itm_mesh_filter_components(exportMesh, minTriangles, nullptr, 0, nullptr, nullptr, nullptr), "itm_mesh_filter_components");
-    check(itm_mesh_index(exportMesh, nullptr), "itm_mesh_index");
-    check(itm_mesh_indexed_attributes(scene.handle, exportMesh, ITM_MESH_NORMALS | (colour ? ITM_MESH_COLOURS : 0), nullptr), "itm_mesh_indexed_attributes");
-    check(itm_mesh_write_ply_indexed(exportMesh, fileName, nullptr), "WriteIndexedPLY");
+  void SaveSceneToCleanPLY(const char* fileName, uint32_t minTriangles) { SaveCleanPLY(fileName, minTriangles, nullptr); }
+  // SaveSceneToCleanPLY with a smoothing step (itm_mesh_smooth: `steps` Taubin passes at the default factors and quantum, border and
+  // non-manifold vertices pinned) between the second index and the indexed attributes, which are read at the smoothed positions
+  void SaveSceneToSmoothPLY(const char* fileName, uint32_t minTriangles, uint32_t steps) {
+    itm_mesh_smooth_config cfg;
+    check(itm_mesh_smooth_default_config(sceneParams.voxelSize, &cfg), "itm_mesh_smooth_default_config");
+    cfg.steps = steps;
+    SaveCleanPLY(fileName, minTriangles, &cfg);
   }
   // A lower level of detail of SaveSceneToIndexedPLY: the scene is resampled into one of twice the voxel size that the engine owns
   // (created by the first call with the same mu, maxW and index configuration; reset and refilled by every call), and THAT scene is
@@ -1199,6 +1199,18 @@ class ITMMainEngine_HIP {
   }
 
  private:
+  // the clean export; smooth given: itm_mesh_smooth between the second index and the indexed attributes
+  void SaveCleanPLY(const char* fileName, uint32_t minTriangles, const itm_mesh_smooth_config* smooth) {
+    const bool colour = TVoxel::kType == ITM_VOXEL_S_RGB || TVoxel::kType == ITM_VOXEL_F_RGB;
+    MeshForExport(0);
+    check(itm_mesh_index(exportMesh, nullptr), "itm_mesh_index");
+    check(itm_mesh_components(exportMesh, nullptr), "itm_mesh_components");
+    check(itm_mesh_filter_components(exportMesh, minTriangles, nullptr, 0, nullptr, nullptr, nullptr), "itm_mesh_filter_components");
+    check(itm_mesh_index(exportMesh, nullptr), "itm_mesh_index");
+    if (smooth) check(itm_mesh_smooth(exportMesh, smooth, nullptr, nullptr), "itm_mesh_smooth");
+    check(itm_mesh_indexed_attributes(scene.handle, exportMesh, ITM_MESH_NORMALS | (colour ? ITM_MESH_COLOURS : 0), nullptr), "itm_mesh_indexed_attributes");
+    check(itm_mesh_write_ply_indexed(exportMesh, fileName, nullptr), "WriteIndexedPLY");
+  }
   void MeshForExport(int attributes) {
     if (!exportMesh) check(itm_mesh_create(scene.handle, 0, &exportMesh), "itm_mesh_create");
     check(itm_mesh_scene(scene.handle, exportMesh, nullptr), "MeshScene");
@@ -1213,11 +1225,13 @@ class ITMMesh {
  public:
   itm_mesh* handle = nullptr;
   uint32_t noTotalTriangles = 0, noMaxTriangles = 0;
+  float voxelSize = 0.0f;                // of the scene the mesh was created for: Smooth's default quantum
   itm_stream stream = nullptr;
   template <class TVoxel, class TIndex>
   explicit ITMMesh(const ITMScene<TVoxel, TIndex>* scene, uint32_t maxTriangles = 0) {
     check(itm_mesh_create(scene->handle, maxTriangles, &handle), "itm_mesh_create");
     check(itm_mesh_info(handle, nullptr, &noMaxTriangles, nullptr, nullptr), "itm_mesh_info");
+    voxelSize = scene->sceneParams->voxelSize;
   }
   ~ITMMesh() { itm_mesh_destroy(handle); }
   ITMMesh(const ITMMesh&) = delete;
@@ -1255,6 +1269,23 @@ class ITMMesh {
   void FilterComponents(uint32_t minTriangles, const uint8_t* keep = nullptr, uint32_t noKeep = 0) {
     check(itm_mesh_filter_components(handle, minTriangles, keep, noKeep, &noTotalTriangles, nullptr, stream), "FilterComponents");
     noVertices = 0; noComponents = 0;
+  }
+  // Fixed-point smoothing of the present index (itm_mesh_smooth): `steps` single passes with the factors lambda (even passes) and mu
+  // (odd passes; mu == lambda: plain Laplacian) on positions quantised to `quantum` metres (0: voxelSize / 1024); pinIrregular keeps
+  // border and non-manifold vertices where they are.  Vertices and triangle buffer move together, the index stays current; the
+  // attributes (ComputeAttributes, ComputeIndexedAttributes) and the components are stale afterwards.
+  itm_mesh_smooth_stats Smooth(uint32_t steps = 20, float lambda = 0.5f, float mu = -0.53f, float quantum = 0.0f, bool pinIrregular = true) {
+    itm_mesh_smooth_config cfg;
+    check(itm_mesh_smooth_default_config(voxelSize, &cfg), "itm_mesh_smooth_default_config");
+    cfg.steps = steps;
+    cfg.lambdaQ16 = (int32_t)std::lround((double)lambda * 65536.0);
+    cfg.muQ16 = (int32_t)std::lround((double)mu * 65536.0);
+    if (quantum != 0.0f) cfg.quantum = quantum;
+    cfg.flags = pinIrregular ? ITM_MESH_SMOOTH_PIN_IRREGULAR : 0u;
+    itm_mesh_smooth_stats stats;
+    check(itm_mesh_smooth(handle, &cfg, &stats, stream), "Smooth");
+    noComponents = 0;
+    return stats;
   }
 };
 

@@ -174,6 +174,30 @@ MESH_COMPONENT_DTYPE = np.dtype([("firstVertex", np.uint32), ("noVertices", np.u
                                  ("bbMin", np.float32, 3), ("bbMax", np.float32, 3)])
 
 
+MESH_SMOOTH_PIN_IRREGULAR = 1
+
+
+class MeshSmoothConfig(C.Structure):
+    """itm_mesh_smooth_config (include/itm_hip.h, itm_mesh_smooth): 32 bytes."""
+    _fields_ = [("steps", C.c_uint32), ("lambdaQ16", C.c_int32), ("muQ16", C.c_int32), ("quantum", C.c_float), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 3)]
+
+
+class MeshSmoothStats(C.Structure):
+    """itm_mesh_smooth_stats (include/itm_hip.h, itm_mesh_smooth): 32 bytes."""
+    _fields_ = [(n, C.c_uint32) for n in ("noVertices", "noMoving", "noIrregular", "noIsolated", "maxEntries", "steps")] + [("reserved", C.c_uint32 * 2)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
+def mesh_smooth_config(quantum, steps=20, lam=0.5, mu=-0.53, pin_irregular=True) -> MeshSmoothConfig:
+    """The factors as Q16 integers, rounded to the nearest (lam = mu: plain Laplacian passes).  quantum: metres per fixed-point unit;
+    it has no default here, since a good one follows the scene's voxel size (itm_mesh_smooth_default_config: voxelSize / 1024)."""
+    return MeshSmoothConfig(int(steps), int(round(lam * 65536)), int(round(mu * 65536)), float(quantum),
+                            MESH_SMOOTH_PIN_IRREGULAR if pin_irregular else 0)
+
+
 class MergeStats(C.Structure):
     """itm_merge_stats (include/itm_hip.h, itm_scene_merge)."""
     _fields_ = [(n, C.c_int32) for n in ("rounds", "considered", "alreadyPresent", "allocated", "combined", "unserved",
@@ -431,6 +455,10 @@ _HOST_IO_SIGS = {
     "mesh_download_components": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint32), _P]),
     "mesh_filter_components": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _P]),
     "debug_mesh_components": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _P]),
+    # fixed-point smoothing of the indexed mesh (product only); default_config is host-only
+    "mesh_smooth_default_config": (C.c_int, [C.c_float, C.POINTER(MeshSmoothConfig)]),
+    "mesh_smooth": (C.c_int, [_P, C.POINTER(MeshSmoothConfig), C.POINTER(MeshSmoothStats), _P]),
+    "debug_mesh_smooth": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, C.POINTER(MeshSmoothConfig), _P, _P, C.POINTER(MeshSmoothStats), _P]),
     # the mesh of either index type: dense volumes brick by brick (product only: the reference's dense MeshScene is empty)
     "mesh_volume": (C.c_int, [_P, _P, _P]),
     # colour maps of the display path (product only: host loops in the reference, Engine/ITMVisualisationEngine.cpp:7-107)
@@ -1231,6 +1259,20 @@ class Mesh:
         keep = np.zeros(len(tri), np.uint8)
         keep[np.argsort(-tri, kind="stable")[:max(int(n), 0)]] = 1
         return self.FilterComponents(0, keep, stream)
+
+    def Smooth(self, steps: int = 20, lam: float = 0.5, mu: float = -0.53, quantum=None, pin_irregular: bool = True, stream=None) -> dict:
+        """Fixed-point Taubin (lam, mu) or Laplacian (mu = lam) passes over the present index: positions move, faces / first / counts
+        stay; vertices() and triangles() change together.  quantum None: voxelSize / 1024.  The soup's and the indexed attributes and
+        the components are stale afterwards; the index stays current.  Returns the statistics."""
+        be = self.scene.be
+        cfg = MeshSmoothConfig()
+        if quantum is None:
+            be.check(be.fn["mesh_smooth_default_config"](float(self.scene.params.voxelSize), C.byref(cfg)), "mesh_smooth_default_config")
+            quantum = cfg.quantum
+        cfg = mesh_smooth_config(quantum, steps, lam, mu, pin_irregular)
+        stats = MeshSmoothStats()
+        be.check(be.fn["mesh_smooth"](_P(self.h), C.byref(cfg), C.byref(stats), _P(stream)), "mesh_smooth")
+        return stats.as_dict()
 
     def close(self):
         if self.h:

@@ -227,6 +227,7 @@ extern int g_debug_exchange_device_copy, g_debug_exchange_corrupt_word;      // 
 extern int g_debug_mesh_attr_per_vertex;                                     // mesh_attributes.hip
 extern int g_debug_mesh_index_weak_hash;                                     // mesh_index.hip
 extern int g_debug_mesh_components_per_lane;                                 // mesh_components.hip
+extern int g_debug_mesh_smooth_scatter;                                      // mesh_smooth.hip
 extern int g_debug_pose_quality_rows;                                        // pose_quality.hip
 // true when rs holds the block requests of a frame issued ahead (itm_process_frame_ahead): `what` is refused with ITM_ERR_INVALID
 int refuse_while_ahead(const itm_scene* s, const itm_render_state* rs, const char* what);

@@ -1,5 +1,6 @@
 // mesh_types.h -- the mesh handle shared by meshing.hip (triangles), mesh_attributes.hip (per-vertex normals and colours) and
-// mesh_index.hip (the indexed form: shared vertices and faces) and mesh_components.hip (its connected components, the fragment filter).
+// mesh_index.hip (the indexed form: shared vertices and faces), mesh_components.hip (its connected components, the fragment filter) and
+// mesh_smooth.hip (fixed-point smoothing passes over the index).
 // The handle's state -- which of those products are current -- is kept here and nowhere else.
 #pragma once
 
@@ -20,6 +21,20 @@ struct ComponentBuffers {
   DeviceBuffer<int32_t> ids;                 // the roots, ascending  (the filter: the kept triangles, ascending)
   DeviceBuffer<int32_t> counters;            // [0] flags set, [1] the same after the cap, [2] what the check launch found, [3] kept components
   void reset() { *this = ComponentBuffers(); }
+};
+
+// The scratch of a smoothing call (mesh_smooth.hip), sized from the counts: owned by the mesh, or by one call of the test hook.
+struct SmoothBuffers {
+  DeviceBuffer<uint32_t> rowCount;           // per vertex: its neighbour entries n(k); the row's fill cursor while the rows are written
+  DeviceBuffer<uint32_t> rowStart;           // per vertex: where its row starts in `entries` (exclusive prefix of rowCount)
+  DeviceBuffer<uint32_t> chunkSum;           // entries per chunk of vertices, then their exclusive prefix
+  DeviceBuffer<uint32_t> entries;            // the adjacency rows (CSR); the order inside a row is arbitrary
+  DeviceBuffer<uint32_t> heavy;              // the vertices whose rows are long enough for a wave of their own, in no particular order
+  DeviceBuffer<uint8_t> vertexFlags;         // per vertex: bit 0 irregular, bit 1 isolated, bit 2 moving
+  DeviceBuffer<int4> xa, xb;                 // the two iterates: x, y, z in fixed point (w unused), 16 bytes per vertex
+  DeviceBuffer<long long> sums;              // scatter form only: per vertex the sums S.x, S.y, S.z (and a word of padding)
+  DeviceBuffer<uint32_t> counters;           // [0] moving [1] irregular [2] isolated [3] max entries [4] input out of range or not finite [5] listed long rows
+  void reset() { *this = SmoothBuffers(); }
 };
 
 }  // namespace itm
@@ -60,6 +75,8 @@ struct itm_mesh {
   itm::DeviceBuffer<uint8_t> componentKeep;  // per component: kept by itm_mesh_filter_components? (the host's mask, then the verdict)
   itm::DeviceBuffer<float> packed;           // the kept triangles, packed, before they replace the buffer's contents
   uint32_t noComponents = 0, componentRounds = 0;
+  // scratch of itm_mesh_smooth (mesh_smooth.hip); allocated / grown by the call, sized from the counts
+  itm::SmoothBuffers smooth;
 
   // ---- which products describe the buffer's present contents ------------------------------------------------------------------------
   //   soup (the triangle buffer) -+- soup attributes (normals, colours)
@@ -69,6 +86,10 @@ struct itm_mesh {
   // the moment something above it is rewritten; a call that fails leaves its product stale.  Who rewrites what: itm_mesh_scene /
   // itm_mesh_volume and, once it starts rewriting, itm_mesh_filter_components the soup; itm_mesh_index the index; itm_mesh_components
   // the components.  Each function below clears its own row and calls the one for the rows beneath it.
+  // itm_mesh_smooth moves positions and nothing else: vertices and soup are rewritten TOGETHER, through the faces, so the index goes on
+  // describing the soup (vertices[faces] is the soup, first[k] names a soup vertex that holds vertices[k]) and stays current -- although
+  // two distinct vertices may now hold one position, which a fresh itm_mesh_index would weld.  Everything computed FROM positions is stale.
+  void vertices_moved() { attrCurrent = 0; indexedAttrCurrent = 0; components_recomputing(); }
   void soup_rewritten() { attrCurrent = 0; index_rebuilding(); }
   void soup_remeshed() { soup_rewritten(); fromVolume = false; }       // itm_mesh_scene: the buffer holds a dense volume's mesh no more
   void index_rebuilding() { indexCurrent = false; indexedAttrCurrent = 0; components_recomputing(); }

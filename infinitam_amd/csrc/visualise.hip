@@ -661,6 +661,7 @@ int itm_debug_set(int key, int value) {
   if (key == ITM_DEBUG_MESH_ATTR_PER_VERTEX) { g_debug_mesh_attr_per_vertex = value; return ITM_OK; }
   if (key == ITM_DEBUG_MESH_INDEX_WEAK_HASH) { g_debug_mesh_index_weak_hash = value; return ITM_OK; }
   if (key == ITM_DEBUG_MESH_COMPONENTS_PER_LANE) { g_debug_mesh_components_per_lane = value; return ITM_OK; }
+  if (key == ITM_DEBUG_MESH_SMOOTH_SCATTER) { g_debug_mesh_smooth_scatter = value; return ITM_OK; }
   if (key == ITM_DEBUG_POSE_QUALITY_ROWS) { g_debug_pose_quality_rows = value; return ITM_OK; }
   if (key == ITM_DEBUG_FAIL_ALLOCATION) { memory_stats().failAt.store(value > 0 ? value : 0); return ITM_OK; }
   return set_error(ITM_ERR_INVALID, "unknown debug key");
