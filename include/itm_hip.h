@@ -908,6 +908,78 @@ typedef struct itm_coarsen_stats {
 } itm_coarsen_stats;
 int ITM_FN(scene_coarsen)(itm_scene* dst, const itm_scene* src, const int32_t* srcSlots_dev, int n, itm_coarsen_stats* stats, itm_stream stream);
 
+/* ---- scene merge under a rigid transform: resamples scene `src` into the frame of scene `dst` and fuses it there, on the same GPU ----
+ * itm_scene_merge needs one world frame, voxel for voxel; the maps of several sessions or robots have one each.  With the relative pose
+ * (a relocalisation, the poses the exchange gathers) src is resampled at dst's voxels and combined into dst.  The reference has no
+ * counterpart.  The transform is quantised once on the host; from there on everything is defined on integers and a fixed tap order,
+ * so the kernels reproduce it bit for bit.
+ *
+ * itm_rigid_quantise.  dstFromSrc: column-major like every matrix here, in metres: x_dst = R x_src + t.  In double:
+ *   fwd = llrint(R * 2^30)   fwdT = llrint(t / voxelSize * 2^30)   inv = llrint(R^T * 2^30)   invT = llrint(-(R^T t) / voxelSize * 2^30)
+ * where R is the rotation next to the matrix's upper 3 x 3: three steps of R <- R (3 I - R^T R) / 2 in double.  A float matrix is
+ * orthonormal to 1e-7 at best, some 50 units of Q30, and inv = R^T is the inverse of fwd only as far as R is orthonormal; after the
+ * steps inv * fwd is within a few units of 2^60 I.  The identity and the turns by 90 degrees pass through bit for bit (+-2^30 and 0).
+ * ITM_ERR_INVALID with the reason in itm_last_error: a null pointer, a voxelSize that is not positive and finite, a non-finite entry, a
+ * bottom row other than (0, 0, 0, 1), an entry of R^T R - I above 1e-4 in magnitude, det R < 0, |t| / voxelSize >= 2^18 on an axis.
+ * Q30, not Q16: block coordinates are shorts, voxel coordinates reach 2^18, where the rounding of fwd against inv stays below 1e-3 voxel. */
+typedef struct itm_rigid_q {      /* Q30, row-major [3i + j]; voxel units */
+  int32_t inv[9];  int64_t invT[3];   /* src voxel coordinate of dst voxel q:  p = inv * q + invT */
+  int32_t fwd[9];  int64_t fwdT[3];   /* dst voxel coordinate of src voxel p:  q = fwd * p + fwdT */
+} itm_rigid_q;
+int ITM_FN(rigid_quantise)(const float dstFromSrc[16], float voxelSize, itm_rigid_q* out);
+
+/* itm_scene_resample.  Requirements, else ITM_ERR_INVALID with the reason in itm_last_error and dst untouched: those of itm_scene_coarsen
+ * (neither scene NULL, dst != src, same device, voxelType and indexType, dst not holding the block requests of a frame issued ahead, the
+ * slot-list rules) with voxelSize bit-equal instead of doubled and mu bit-equal (maxW may differ: dst's is used); q not NULL; every row of
+ * q->inv and of q->fwd has sum |entry| <= 1.75 * 2^30 (a rotation has at most sqrt(3)) and every |T| < 2^48.  The call does not ask q to
+ * be a rotation: the definition below holds for whatever passes.  Recorded calls of both scenes are launched first; src is never written.
+ *
+ * The resampled voxel at dst voxel q, for both index types.  Per axis p = inv * q + invT (int64, Q30); P = (p + 2^23) >> 24 (arithmetic
+ * shift: Q6, the position to the nearest 1/64 voxel, halves up); cell f = P >> 6, fraction u = P & 63.  Eight taps k in {0, 1}^3, taken
+ * with kz outermost and kx innermost; c_k = prod_i (k_i ? u_i : 64 - u_i) (they sum to 2^18); t_k = readVoxel(src, f + k) over the WHOLE
+ * of src, whatever the slot list selects; an absent voxel, an entry with ptr < 0 or a block pointer outside src's pool reads as TVoxel()
+ * with weight 0, as in itm_scene_coarsen.
+ *   depth   a_k = c_k * w_depth(t_k), A = sum a_k (int64; below 2^26).  A == 0: r carries no depth (w_depth 0) and dst's sdf and w_depth
+ *           stay as they are.  Otherwise w' = min(255, max(1, (A + 2^17) >> 18)) and
+ *             short sdf: S = sum a_k * sdf_k (int64), sdf' = sgn(S) * ((2|S| + A) div 2A) -- to nearest, halves away from zero;
+ *             float sdf: S = sum (double)a_k * (double)sdf_k, summed in double in the tap order from +0.0 (every product is exact:
+ *                        26 + 24 bits < 53), sdf' = (float)(S / (double)A).
+ *   colour  (the two types that store it) b_k = c_k * w_color(t_k), Bc = sum b_k.  Bc == 0: r carries no colour (clr 0, w_color 0) and
+ *           dst's stay as they are.  Otherwise each channel is (2 * sum b_k * clr_k + Bc) div 2Bc (int64) and
+ *           w_color' = min(255, max(1, (Bc + 2^17) >> 18)).  The two parts are independent, as they are in the combine.
+ *   fuse    dst = CombineVoxelInformation(r, dst, dst's maxW) with r = (sdf', w', clr', w_color') in the role of the stored block: the
+ *           combine of itm_scene_merge step 3.  dst's maxW clamps there; r's own weights are clamped at 255 only.
+ * Properties: inv the identity and invT whole voxels: u = 0, r is src's voxel at the shifted position (with zero translation every
+ * voxel of dst comes out as itm_scene_merge leaves it; more BLOCKS exist, see below).  A rotation by a multiple of 90 degrees about an
+ * axis with a whole-voxel translation permutes the voxels exactly.
+ *
+ * Hash index, sequential definition (box(M, T, [lo3, hi3]) is, per axis i, lo = T_i + sum_j min(M_ij lo3_j, M_ij hi3_j) and hi the same
+ * with max; the voxels such a Q30 box can touch with a trilinear footprint are [(lo >> 30) - 1, (hi >> 30) + 2]):
+ *  1. Participants as in itm_scene_merge step 1; `considered` is their number, selected entries with ptr == -1 count in srcWithoutBlock.
+ *  2. Candidate list C.  The participants in ascending src slot order, each at block b: the forward box of its dilated cube
+ *     box(fwd, fwdT, [8b - 1, 8b + 8]) gives a dst voxel range and, >> 3, a block range (at most 4 blocks per axis under the row bound).
+ *     Its blocks B are walked with Bz outermost and Bx innermost, ascending; B is a candidate iff the voxel range of its inverse box
+ *     box(inv, invT, [8B, 8B + 7]) meets [8b_i, 8b_i + 7] on every axis.  A candidate whose coordinates do not fit a short is dropped
+ *     and counted in outOfRange; `candidates` = |C|.  One block is a candidate of every participant near it: C holds it that often.
+ *     The two tests are the axis-aligned halves of a box-overlap check: what they over-allocate stays allocated and empty, as the
+ *     blocks that ray-step allocation leaves beside a surface.
+ *  3. Rounds: itm_scene_merge step 2 word for word, with C in the place of the participants and the index in C in the place of the
+ *     src slot (the highest index wins a target).  alreadyPresent, allocated and unserved count candidates.
+ *  4. D = the set of dst entries that hold the position of at least one candidate.  Those with ptr == -1 count in dstSwappedOut and
+ *     are left alone; for the others all 512 voxels take the rule above, `resampled` is their number (an entry whose block pointer lies
+ *     outside dst's pool -- only an uploaded table can name one -- is left alone and not counted).  Under the row bound every tap of
+ *     a block of D lies in the 3 x 3 x 3 src blocks from ((lo >> 30) - 1) >> 3 of the block's inverse box on.
+ *  5. Derived structures as in itm_scene_merge step 4.  A dst whose cubes nothing has placed yet gets them around the block that holds
+ *     the image (fwd, fwdT, >> 30, >> 3) of the centre of src's.
+ * Dense index: every cell of dst takes the voxel rule at q = cell + dst's denseOffset; taps go through the dense readVoxel of src, outside
+ * src's array a tap is absent; denseSize / denseOffset need not agree; a slot list is refused; considered = resampled = 1, the rest 0.
+ * Synchronises `stream` once for the candidate count (twice when the scratch has to grow), once per round and once for the statistics;
+ * the resampling launch itself is enqueued.  `stats` (host) may be NULL. */
+typedef struct itm_resample_stats {
+  int32_t rounds, considered, candidates, alreadyPresent, allocated, resampled, unserved, srcWithoutBlock, dstSwappedOut, outOfRange;
+} itm_resample_stats;
+int ITM_FN(scene_resample)(itm_scene* dst, const itm_scene* src, const itm_rigid_q* q, const int32_t* srcSlots_dev, int n, itm_resample_stats* stats, itm_stream stream);
+
 /* ---- scene queries: the volume asked at caller-supplied points and along caller-supplied rays -------------------------------------
  * The reference makes these reads only from inside its engines, per pixel; here the work item is the caller's.  Both calls launch the
  * scene's recorded calls first, read the scene only, take DEVICE pointers and enqueue one launch on `stream` (no synchronisation).

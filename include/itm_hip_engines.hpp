@@ -39,6 +39,12 @@ struct ITMPlainVoxelArray { static constexpr int kType = ITM_INDEX_DENSE; };
 struct Vector2i { int x, y; };
 struct Vector2f { float x, y; };
 struct Vector4u { uint8_t x, y, z, w; };
+// ORUtils::Matrix4<float> as far as the path needs it: 16 floats, column-major (m[4 * column + row]), like every matrix of the C-ABI
+struct Matrix4f {
+  float m[16];
+  Matrix4f() { std::memset(m, 0, sizeof m); m[0] = m[5] = m[10] = m[15] = 1.0f; }
+  explicit Matrix4f(const float* values) { std::memcpy(m, values, sizeof m); }
+};
 
 // ITMUChar4Image (Utils/ITMLibDefines.h, ORUtils/Image.h) as far as ITMMainEngine::GetImage needs it: a host image of Vector4u
 class ITMUChar4Image {
@@ -333,6 +339,31 @@ class ITMSceneCoarsenEngine_HIP {
       if (!slots) throw std::runtime_error("CoarsenScene: the render state has no visible list");
     }
     check(itm_scene_coarsen(dst->handle, src->handle, slots, n, stats, stream), "CoarsenScene");
+  }
+};
+
+// Scene merge under a rigid transform (itm_rigid_quantise + itm_scene_resample; no reference class): `src` is resampled at dst's voxels
+// through dstFromSrc (x_dst = dstFromSrc x_src, metres: a relocalisation's relative pose, the poses the exchange gathers) and fused into
+// `dst` as MergeScene fuses.  Same voxel type, index type, voxelSize and mu; both scenes on one device.  srcVisible: a render state of src
+// whose visible list selects the blocks that take part (nullptr: every block of src).  dst's render states are not touched.
+template <class TVoxel, class TIndex>
+class ITMSceneResampleEngine_HIP {
+ public:
+  itm_stream stream = nullptr;
+  void ResampleScene(ITMScene<TVoxel, TIndex>* dst, const ITMScene<TVoxel, TIndex>* src, const Matrix4f& dstFromSrc, const ITMRenderState* srcVisible = nullptr,
+                     itm_resample_stats* stats = nullptr) {
+    itm_rigid_q q;
+    check(itm_rigid_quantise(dstFromSrc.m, dst->sceneParams->voxelSize, &q), "ResampleScene (itm_rigid_quantise)");
+    const int32_t* slots = nullptr;
+    int n = 0;
+    if (srcVisible) {
+      itm_counters c;
+      check(itm_get_counters(src->handle, srcVisible->handle, &c, stream), "ResampleScene (visible list)");
+      slots = (const int32_t*)itm_buffer_ptr(src->handle, srcVisible->handle, ITM_BUF_VISIBLE_IDS);
+      n = c.noVisibleEntries;
+      if (!slots) throw std::runtime_error("ResampleScene: the render state has no visible list");
+    }
+    check(itm_scene_resample(dst->handle, src->handle, &q, slots, n, stats, stream), "ResampleScene");
   }
 };
 
@@ -880,6 +911,11 @@ class ITMMainEngine_HIP {
   // states and `other` stay as they are: the merged blocks are seen by the next ProcessFrame whose view holds them.
   void MergeSceneFrom(const ITMMainEngine_HIP& other, itm_merge_stats* stats = nullptr) {
     ITMSceneMergeEngine_HIP<TVoxel, TIndex>().MergeScene(&scene, &other.scene, nullptr, stats);
+  }
+  // The same for an `other` that lives in a frame of its own: thisFromOther maps its world to this engine's (x_this = thisFromOther
+  // x_other, metres).  The scene of `other` is resampled at this scene's voxels and fused (itm_scene_resample).
+  void MergeSceneFrom(const ITMMainEngine_HIP& other, const Matrix4f& thisFromOther, itm_resample_stats* stats = nullptr) {
+    ITMSceneResampleEngine_HIP<TVoxel, TIndex>().ResampleScene(&scene, &other.scene, thisFromOther, nullptr, stats);
   }
   // Resamples this engine's scene into `coarse`, a scene of twice the voxel size and the same mu (itm_scene_coarsen).  This engine's
   // scene, tracking state and render states stay as they are.

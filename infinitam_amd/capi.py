@@ -216,6 +216,45 @@ class CoarsenStats(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class RigidQ(C.Structure):
+    """itm_rigid_q (include/itm_hip.h): a rigid transform in Q30 and voxel units, row-major [3i + j], both directions."""
+    _fields_ = [("inv", C.c_int32 * 9), ("invT", C.c_int64 * 3), ("fwd", C.c_int32 * 9), ("fwdT", C.c_int64 * 3)]
+
+    def as_dict(self):
+        return {n: [int(v) for v in getattr(self, n)] for n, _ in self._fields_}
+
+    @classmethod
+    def from_dict(cls, d):
+        q = cls()
+        for n, _ in cls._fields_:
+            for i, v in enumerate(d[n]):
+                getattr(q, n)[i] = int(v)
+        return q
+
+
+class ResampleStats(C.Structure):
+    """itm_resample_stats (include/itm_hip.h, itm_scene_resample)."""
+    _fields_ = [(n, C.c_int32) for n in ("rounds", "considered", "candidates", "alreadyPresent", "allocated", "resampled", "unserved",
+                                         "srcWithoutBlock", "dstSwappedOut", "outOfRange")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+def rigid_quantise(M, voxelSize, be=None) -> RigidQ:
+    """itm_rigid_quantise: the rigid transform M (4 x 4, x_dst = M x_src, metres; or its 16 floats column-major) in Q30 and voxel
+    units.  be: the Backend whose library does it (default: the product library; host only, no device is touched).  Raises ItmError
+    with the library's reason for a matrix that is refused."""
+    if be is None:
+        from . import load
+        be = load()
+    arr = np.asarray(M, np.float32)
+    flat = np.ascontiguousarray(arr.T if arr.ndim == 2 else arr).reshape(16)
+    q = RigidQ()
+    be.check(be.fn["rigid_quantise"](flat.ctypes.data_as(C.POINTER(C.c_float)), float(voxelSize), C.byref(q)), "rigid_quantise")
+    return q
+
+
 class QueryOut(C.Structure):
     """itm_query_out (include/itm_hip.h, itm_scene_query_points): device pointers, NULL = not wanted."""
     _fields_ = [(n, C.c_void_p) for n in ("sdf", "sdf_nearest", "gradient", "normal", "colour", "weight", "flags")]
@@ -469,6 +508,9 @@ _HOST_IO_SIGS = {
     "scene_merge": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(MergeStats), _P]),
     # level of detail (product only: the reference has one resolution per scene)
     "scene_coarsen": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(CoarsenStats), _P]),
+    # scene merge under a rigid transform (product only)
+    "rigid_quantise": (C.c_int, [C.POINTER(C.c_float), C.c_float, C.POINTER(RigidQ)]),
+    "scene_resample": (C.c_int, [_P, _P, C.POINTER(RigidQ), _P, C.c_int, C.POINTER(ResampleStats), _P]),
     # scene queries at caller-supplied points / along caller-supplied rays (product only: the reference reads per pixel, inside its engines)
     "scene_query_points": (C.c_int, [_P, _P, C.c_uint32, C.c_int, C.POINTER(QueryOut), _P]),
     "scene_cast_rays": (C.c_int, [_P, _P, C.c_uint32, _P, _P]),
@@ -795,6 +837,19 @@ class Scene:
         """itm_scene_coarsen: resamples `src` into this scene, which has twice src's voxel size, on the GPU and returns the statistics.
         slots: as merge_from."""
         return self._slot_call("scene_coarsen", CoarsenStats(), src, slots, stream)
+
+    def resample_from(self, src: "Scene", q_or_matrix, slots=None, stream=None) -> dict:
+        """itm_scene_resample: resamples `src` into this scene's frame and fuses it here, on the GPU; returns the statistics.
+        q_or_matrix: a RigidQ, or the 4 x 4 matrix dstFromSrc in metres (quantised with this scene's voxel size).  slots: as merge_from."""
+        q = q_or_matrix if isinstance(q_or_matrix, RigidQ) else rigid_quantise(q_or_matrix, float(self.params.voxelSize), self.be)
+        ptr, n, keep = self._slot_list(slots, stream)
+        stats = ResampleStats()
+        rc = self.be.fn["scene_resample"](_P(self.h), _P(src.h), C.byref(q), _P(ptr), n, C.byref(stats), _P(stream))
+        if keep is not None:
+            self.be.sync(stream)
+            keep.close()
+        self.be.check(rc, "scene_resample")
+        return stats.as_dict()
 
     def query_points(self, points, units="metres", want=("sdf", "gradient"), stream=None) -> dict:
         """itm_scene_query_points: the outputs named in `want` (QUERY_OUTPUTS) at float32 points [n, 3] in "metres" or "voxels", as a

@@ -79,46 +79,6 @@ struct CoarseVoxel {
 
 __device__ inline int tent(int k) { return 2 - (k < 0 ? -k : k); }
 
-// voxel index of the first voxel of src's block (bx, by, bz), -1 where readVoxel finds none: directory where it covers, else a table
-// walk that is bounded and stays inside the table (an uploaded table may hold anything); a block outside the pool counts as none
-__device__ inline long long fine_block_base(const VolumeView& vol, int noTotalEntries, size_t numVoxels, int bx, int by, int bz) {
-  if ((int)(int16_t)bx != bx || (int)(int16_t)by != by || (int)(int16_t)bz != bz) return -1;      // beyond the table's short coordinates
-  int ptr = -1;
-  const uint32_t ux = (uint32_t)(bx - vol.org.dx), uy = (uint32_t)(by - vol.org.dy), uz = (uint32_t)(bz - vol.org.dz);
-  if (vol.dirPtr && dir_covers(ux, uy, uz)) ptr = vol.dirPtr[dir_cell(ux, uy, uz)];
-  else {
-    HashEntry e = unpack_entry(vol.hash[hash_index(bx, by, bz, vol.mask)]);
-    for (int steps = 0; steps <= noTotalEntries - vol.bucketNum; ++steps) {
-      if (e.px == bx && e.py == by && e.pz == bz && e.ptr >= 0) { ptr = e.ptr; break; }
-      if (e.offset < 1) break;
-      const int next = vol.bucketNum + e.offset - 1;
-      if (next >= noTotalEntries) break;
-      e = unpack_entry(vol.hash[next]);
-    }
-  }
-  if (ptr < 0 || (size_t)ptr * kBlockVoxels + kBlockVoxels > numVoxels) return -1;
-  return (long long)ptr * kBlockVoxels;
-}
-
-// The set D: one lane per src slot; a participant with a place in dst claims that slot's request key, the first claimer lists the slot.
-__global__ void __launch_bounds__(256) coarsen_claim_kernel(int srcEntries, const int32_t* __restrict__ where, const uint4* __restrict__ dstHash, size_t dstVoxels,
-                                                            uint32_t* __restrict__ allocKey, int32_t* __restrict__ list, int32_t* __restrict__ stats) {
-  const int slot = blockIdx.x * blockDim.x + threadIdx.x;
-  const int w = slot < srcEntries ? where[slot] : kWhereNot;
-  bool first = false;
-  int dp = -2;
-  if (w >= 0) {
-    first = atomicExch(&allocKey[w], 1u) == 0u;
-    if (first) {
-      dp = (int)dstHash[w].w;
-      list[atomicAdd(&stats[kMsListCount], 1)] = w;      // (every claimed slot: the resampling launch zeroes its key again)
-    }
-  }
-  // (a voxel block outside dst's pool: only an uploaded table can name one; it is left alone)
-  tally(stats, kMsDstSwappedOut, (first && dp == -1) ? 1 : 0);
-  tally(stats, kMsCombined, (first && dp >= 0 && (size_t)dp * kBlockVoxels + kBlockVoxels <= dstVoxels) ? 1 : 0);
-}
-
 template <class VX>
 __global__ void __launch_bounds__(512) coarsen_block_kernel(const int32_t* __restrict__ list, VolumeView src, int srcEntries, size_t srcVoxels, const uint4* __restrict__ dstHash,
                                                             void* __restrict__ dstVba, size_t dstVoxels, int maxW, uint32_t* __restrict__ allocKey, AccelWriter aw) {
@@ -244,7 +204,7 @@ int itm_scene_coarsen(itm_scene* dst, const itm_scene* src, const int32_t* srcSl
   MergePlacement pl;
   { const int rc = place_participants<1>(dst, src, srcSlots_dev, n, st, "scene coarsen", pl); if (rc) return rc; }
   out.rounds = pl.rounds; out.allocated = pl.allocated; out.unserved = pl.unserved;
-  coarsen_claim_kernel<<<(src->noTotalEntries + 255) / 256, 256, 0, st>>>(src->noTotalEntries, pl.where, dst->hash, dst->numVoxels, dst->allocKey, pl.list, pl.dStats);
+  claim_blocks_kernel<<<(src->noTotalEntries + 255) / 256, 256, 0, st>>>(src->noTotalEntries, pl.where, dst->hash, dst->numVoxels, dst->allocKey, pl.list, pl.dStats);
   ITM_LAUNCH_CHECK();
   { const int rc = pl.read_stats(); if (rc) return rc; }
   const int32_t* h = pl.h;

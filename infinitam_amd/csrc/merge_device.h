@@ -3,6 +3,8 @@
 // (include/itm_hip.h, itm_scene_merge steps 1 and 2).  SHIFT is what distinguishes the two callers: a participant at block b asks for
 // the position b >> SHIFT per component (arithmetic shift) -- 0: its own position (merge), 1: the block of twice the voxel size that
 // holds it (coarsen), where up to eight participants share a position: one wins the target, the others find the entry next round.
+// The rounds run over a POSITION SOURCE, any device array of packed entries (place_positions): merge and coarsen pass src's table
+// (place_participants), itm_scene_resample (resample.hip) the list of candidate blocks it builds, packed as entries with ptr 0.
 //
 // Reference building blocks: buildHashAllocAndVisibleTypePP's probe (DeviceAgnostic/ITMSceneReconstructionEngine.h:186-241) with block
 // positions in the place of ray steps, and the ascending sweep of DeviceSpecific/CPU/ITMSceneReconstructionEngine_CPU.cpp:175-227.
@@ -24,7 +26,7 @@ namespace itm {
 
 // device-side tallies of a call (ints); the host reads them after every round
 enum { kMsConsidered = 0, kMsSrcWithoutBlock, kMsPresentFirst, kMsPending, kMsTargets, kMsServedBlocks, kMsServedExcess, kMsCombined, kMsDstSwappedOut,
-       kMsListCount, kMsBadSlot, kMsCount = 16 };
+       kMsListCount, kMsBadSlot, kMsRsParticipants, kMsRsNoBlock, kMsRsOutOfRange, kMsRsCandidates /* (itm_scene_resample's own) */, kMsCount = 16 };
 constexpr int kWhereNot = -2, kWherePending = -1;      // per src slot: not a participant / still without a place in dst / (>= 0) its dst slot
 
 __device__ inline void tally(int32_t* __restrict__ stats, int which, int flag) {      // one atomic per wave; every lane of the wave calls
@@ -180,6 +182,27 @@ static __global__ void merge_commit_kernel(SceneCounters* __restrict__ counters,
   counters->lastFreeExcessListId -= stats[kMsServedExcess];
 }
 
+// The set D of itm_scene_coarsen and itm_scene_resample: one lane per entry of the position source; an entry with a place in dst claims
+// that slot's request key (zero between calls), the first claimer lists the slot -- built without a sort, in no particular order.  The
+// caller's voxel launch zeroes the keys again.
+static __global__ void __launch_bounds__(256) claim_blocks_kernel(int srcEntries, const int32_t* __restrict__ where, const uint4* __restrict__ dstHash, size_t dstVoxels,
+                                                                  uint32_t* __restrict__ allocKey, int32_t* __restrict__ list, int32_t* __restrict__ stats) {
+  const int slot = blockIdx.x * blockDim.x + threadIdx.x;
+  const int w = slot < srcEntries ? where[slot] : kWhereNot;
+  bool first = false;
+  int dp = -2;
+  if (w >= 0) {
+    first = atomicExch(&allocKey[w], 1u) == 0u;
+    if (first) {
+      dp = (int)dstHash[w].w;
+      list[atomicAdd(&stats[kMsListCount], 1)] = w;      // (every claimed slot: the resampling launch zeroes its key again)
+    }
+  }
+  // (a voxel block outside dst's pool: only an uploaded table can name one; it is left alone)
+  tally(stats, kMsDstSwappedOut, (first && dp == -1) ? 1 : 0);
+  tally(stats, kMsCombined, (first && dp >= 0 && (size_t)dp * kBlockVoxels + kBlockVoxels <= dstVoxels) ? 1 : 0);
+}
+
 static inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 // ---- host side: steps 1 and 2 of a call ------------------------------------------------------------------------------------------------
@@ -196,8 +219,57 @@ struct MergePlacement {
   }
 };
 
+// The rounds of step 2 over any device array of packed entries: `posHash[0 .. posEntries)` names the positions (an entry with ptr >= 0
+// takes part, `sel` -- may be null -- narrows that to the selected slots), `p.where` has one int per entry.  itm_scene_merge and
+// itm_scene_coarsen pass src's table, itm_scene_resample its candidate list (resample.hip).  chunkCnt: one int2 per chunk of dst's table.
+template <int SHIFT>
+inline int place_positions(itm_scene* dst, const uint4* posHash, int posEntries, const uint8_t* sel, int2* chunkCnt, hipStream_t st, MergePlacement& p) {
+  const MergeTable table{dst->hash, g_debug_no_directory ? nullptr : dst->dirSlot, dst->org, (uint32_t)(dst->cfg.bucketNum - 1), dst->cfg.bucketNum, dst->noTotalEntries};
+  const int reqGrid = (posEntries + 255) / 256;
+  for (int round = 1;; ++round) {
+    ITM_HIP(hipMemsetAsync(chunkCnt, 0, (size_t)dst->numChunks * 8, st));
+    ITM_HIP(hipMemsetAsync(p.dStats + kMsPending, 0, 4 * 4, st));      // pending, targets, served blocks, served excess entries: per round
+    if (round == 1) merge_request_kernel<true, SHIFT><<<reqGrid, 256, 0, st>>>(posHash, posEntries, sel, p.where, table, dst->allocKey, chunkCnt, p.dStats);
+    else merge_request_kernel<false, SHIFT><<<reqGrid, 256, 0, st>>>(posHash, posEntries, sel, p.where, table, dst->allocKey, chunkCnt, p.dStats);
+    ITM_LAUNCH_CHECK();
+    merge_sweep_kernel<SHIFT><<<dst->numChunks, 256, 0, st>>>(dst->allocKey, chunkCnt, dst->hash, dst->noTotalEntries, dst->cfg.bucketNum, dst->excessList, dst->allocList, dst->counters,
+                                                              accel_writer(dst), posHash, p.where, p.dStats);
+    ITM_LAUNCH_CHECK();
+    merge_commit_kernel<<<1, 1, 0, st>>>(dst->counters, p.dStats);
+    ITM_LAUNCH_CHECK();
+    { const int rc = p.read_stats(); if (rc) return rc; }
+    p.rounds = round;
+    p.allocated += p.h[kMsServedBlocks];
+    if (p.h[kMsTargets] == 0) break;
+    if (p.h[kMsServedBlocks] == 0) { p.unserved = p.h[kMsPending]; break; }
+  }
+  return ITM_OK;
+}
+
+// A dst that no frame or upload has placed its cubes for: they are empty wherever they lie; the entries a call records in them fix the
+// placement (src's where the cubes are alike, around the same centre in dst's blocks), which a later view moves like any other.
+// toDst(c, out): the block of dst that holds the centre c (a block of src) of one of src's cubes.
+template <class ToDst>
+inline void place_cubes_like(itm_scene* dst, const itm_scene* src, ToDst&& toDst) {
+  if (dst->orgPlaced) return;
+  if (src->orgPlaced) {
+    auto centred = [&](int cx, int cy, int cz, int half, int& ox, int& oy, int& oz) {
+      const int c[3] = {cx + half, cy + half, cz + half};
+      int o[3];
+      toDst(c, o);
+      ox = o[0] - half; oy = o[1] - half; oz = o[2] - half;
+    };
+    centred(src->org.dx, src->org.dy, src->org.dz, kDirHalf, dst->org.dx, dst->org.dy, dst->org.dz);
+    if (dst->org.mMaxPages == src->org.mMaxPages || (dst->org.mMaxPages > 0 && src->org.mMaxPages > 0)) {
+      const int half = src->org.mMaxPages < 0 ? (1 << mirror_dense_bits(src->org)) / 2 : kMirrorHalf;
+      centred(src->org.mx, src->org.my, src->org.mz, half, dst->org.mx, dst->org.my, dst->org.mz);
+    }
+  }
+  dst->orgPlaced = true;
+}
+
 // Marks the selected slots (a slot outside src's table: ITM_ERR_INVALID, dst untouched), places dst's cubes if nothing has yet, and runs
-// the rounds.  `what`: the entry point's name for messages.
+// the rounds over src's table.  `what`: the entry point's name for messages.
 template <int SHIFT>
 inline int place_participants(itm_scene* dst, const itm_scene* src, const int32_t* srcSlots_dev, int n, hipStream_t st, const char* what, MergePlacement& p) {
   const size_t S = (size_t)src->noTotalEntries;
@@ -217,40 +289,9 @@ inline int place_participants(itm_scene* dst, const itm_scene* src, const int32_
     { const int rc = p.read_stats(); if (rc) return rc; }
     if (p.h[kMsBadSlot]) return set_error(ITM_ERR_INVALID, std::string(what) + ": a slot of the list is outside src's table");      // dst is untouched
   }
-  // A dst that no frame or upload has placed its cubes for: they are empty wherever they lie; the entries this call records in them
-  // fix the placement (src's where the cubes are alike, around the same centre in dst's blocks), which a later view moves like any other.
-  if (!dst->orgPlaced) {
-    if (src->orgPlaced) {
-      // (c + half) >> SHIFT is the centre of src's cube in dst's blocks; SHIFT == 0 leaves c as it is
-      auto centred = [](int c, int halfSrc, int halfDst) { return ((c + halfSrc) >> SHIFT) - halfDst; };
-      dst->org.dx = centred(src->org.dx, kDirHalf, kDirHalf); dst->org.dy = centred(src->org.dy, kDirHalf, kDirHalf); dst->org.dz = centred(src->org.dz, kDirHalf, kDirHalf);
-      if (dst->org.mMaxPages == src->org.mMaxPages || (dst->org.mMaxPages > 0 && src->org.mMaxPages > 0)) {
-        const int half = src->org.mMaxPages < 0 ? (1 << mirror_dense_bits(src->org)) / 2 : kMirrorHalf;
-        dst->org.mx = centred(src->org.mx, half, half); dst->org.my = centred(src->org.my, half, half); dst->org.mz = centred(src->org.mz, half, half);
-      }
-    }
-    dst->orgPlaced = true;
-  }
-  const MergeTable table{dst->hash, g_debug_no_directory ? nullptr : dst->dirSlot, dst->org, (uint32_t)(dst->cfg.bucketNum - 1), dst->cfg.bucketNum, dst->noTotalEntries};
-  const int reqGrid = (src->noTotalEntries + 255) / 256;
-  for (int round = 1;; ++round) {
-    ITM_HIP(hipMemsetAsync(chunkCnt, 0, (size_t)dst->numChunks * 8, st));
-    ITM_HIP(hipMemsetAsync(p.dStats + kMsPending, 0, 4 * 4, st));      // pending, targets, served blocks, served excess entries: per round
-    if (round == 1) merge_request_kernel<true, SHIFT><<<reqGrid, 256, 0, st>>>(src->hash, src->noTotalEntries, sel, p.where, table, dst->allocKey, chunkCnt, p.dStats);
-    else merge_request_kernel<false, SHIFT><<<reqGrid, 256, 0, st>>>(src->hash, src->noTotalEntries, sel, p.where, table, dst->allocKey, chunkCnt, p.dStats);
-    ITM_LAUNCH_CHECK();
-    merge_sweep_kernel<SHIFT><<<dst->numChunks, 256, 0, st>>>(dst->allocKey, chunkCnt, dst->hash, dst->noTotalEntries, dst->cfg.bucketNum, dst->excessList, dst->allocList, dst->counters,
-                                                              accel_writer(dst), src->hash, p.where, p.dStats);
-    ITM_LAUNCH_CHECK();
-    merge_commit_kernel<<<1, 1, 0, st>>>(dst->counters, p.dStats);
-    ITM_LAUNCH_CHECK();
-    { const int rc = p.read_stats(); if (rc) return rc; }
-    p.rounds = round;
-    p.allocated += p.h[kMsServedBlocks];
-    if (p.h[kMsTargets] == 0) break;
-    if (p.h[kMsServedBlocks] == 0) { p.unserved = p.h[kMsPending]; break; }
-  }
-  return ITM_OK;
+  // (c >> SHIFT is the centre of src's cube in dst's blocks; SHIFT == 0 leaves c as it is)
+  place_cubes_like(dst, src, [](const int c[3], int o[3]) { for (int i = 0; i < 3; ++i) o[i] = c[i] >> SHIFT; });
+  return place_positions<SHIFT>(dst, src->hash, src->noTotalEntries, sel, chunkCnt, st, p);
 }
 
 }  // namespace itm

@@ -417,6 +417,27 @@ __device__ inline int block_base(const VolumeView& vol, int bx, int by, int bz) 
   return resolve_block(vol, unpack_entry(vol.hash[hash_index(bx, by, bz, vol.mask)]), bx, by, bz);
 }
 
+// voxel index of the first voxel of src's block (bx, by, bz), -1 where readVoxel finds none: directory where it covers, else a table
+// walk that is bounded and stays inside the table (an uploaded table may hold anything); a block outside the pool counts as none
+__device__ inline long long fine_block_base(const VolumeView& vol, int noTotalEntries, size_t numVoxels, int bx, int by, int bz) {
+  if ((int)(int16_t)bx != bx || (int)(int16_t)by != by || (int)(int16_t)bz != bz) return -1;      // beyond the table's short coordinates
+  int ptr = -1;
+  const uint32_t ux = (uint32_t)(bx - vol.org.dx), uy = (uint32_t)(by - vol.org.dy), uz = (uint32_t)(bz - vol.org.dz);
+  if (vol.dirPtr && dir_covers(ux, uy, uz)) ptr = vol.dirPtr[dir_cell(ux, uy, uz)];
+  else {
+    HashEntry e = unpack_entry(vol.hash[hash_index(bx, by, bz, vol.mask)]);
+    for (int steps = 0; steps <= noTotalEntries - vol.bucketNum; ++steps) {
+      if (e.px == bx && e.py == by && e.pz == bz && e.ptr >= 0) { ptr = e.ptr; break; }
+      if (e.offset < 1) break;
+      const int next = vol.bucketNum + e.offset - 1;
+      if (next >= noTotalEntries) break;
+      e = unpack_entry(vol.hash[next]);
+    }
+  }
+  if (ptr < 0 || (size_t)ptr * kBlockVoxels + kBlockVoxels > numVoxels) return -1;
+  return (long long)ptr * kBlockVoxels;
+}
+
 // ---- host side: the view of a scene, and the kernel instance that reads it ------------------------------------------------------------
 
 static inline VolumeView make_volume(const itm_scene* s) {
