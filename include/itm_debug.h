@@ -43,6 +43,35 @@ extern "C" {
 #define ITM_DEBUG_MESH_COMPONENTS_PER_LANE 30      /* itm_mesh_components: the statistics with one atomic per lane instead of one per wave segment (lanes of a wave that share a component aggregate first) */
 #define ITM_DEBUG_MESH_SMOOTH_SCATTER 31            /* itm_mesh_smooth: every pass as a scatter -- one lane per proper triangle adds its corners into per-vertex int64 accumulators with 64-bit integer atomics, a second kernel applies the step -- instead of the gather over the adjacency rows (same bits by construction) */
 int ITM_FN(debug_set)(int key, int value);
+/* The forward-only 32-bit counters behind the tagged granules (DESIGN.md "Forward-only counters"): reads one counter of one handle into
+ * *get (may be NULL) and then, when set is not NULL, replaces it with *set -- so that a test can place a handle a few steps before the
+ * roll-over that 2^32 frames of uptime would reach.  Only the number changes: no buffer is touched, no result depends on where a counter
+ * stands, and a process that never calls this runs the code it always ran.  The caller keeps the handle idle during the call (no engine
+ * call of another thread, nothing recorded and unflushed).  Host only, but for the image maps' first use of a stream (below).
+ *   handle            counter
+ *   itm_scene*        LIST_EPOCH    epoch of the last one-launch visible list (stamps of chunkGran / chunkSweepDone / chunkKeptGran)
+ *                     FRAME_PARITY  allocations so far; its lowest bit selects the half of the request counters (set a value of the same parity)
+ *                     TABLE_EPOCH   resets / replacements of the hash table
+ *   itm_tracker*      TRACKER_SEQ   sequence number of the last evaluation (tag of commands and records); NULL = the calling thread's own
+ *                     TRACKER_SESSION  number of the last resident evaluation kernel; where the handle has had a session, the pinned
+ *                                   "exited" word with it, as if that kernel had run and left
+ *                     TRACKER_FALLBACKS, TRACKER_RELAUNCHES  read only: sessions given up for one launch per evaluation / sessions
+ *                                   replaced because the previous one seemed to have left without an answer
+ *   itm_colour_tracker*, itm_ren_tracker*, itm_pose_quality_handle*   COLOUR_SEQ, REN_SEQ, POSE_QUALITY_SEQ: as TRACKER_SEQ
+ *   itm_stream        IMAGE_MAP_EPOCH  epoch of the last image-map call on this stream of the current device (the slot is created if
+ *                                   the stream has none yet; that allocates and zeroes a block of slots exactly as a first GetImage would) */
+#define ITM_COUNTER_LIST_EPOCH 1
+#define ITM_COUNTER_FRAME_PARITY 2
+#define ITM_COUNTER_TABLE_EPOCH 3
+#define ITM_COUNTER_TRACKER_SEQ 4
+#define ITM_COUNTER_TRACKER_SESSION 5
+#define ITM_COUNTER_TRACKER_FALLBACKS 6
+#define ITM_COUNTER_TRACKER_RELAUNCHES 7
+#define ITM_COUNTER_COLOUR_SEQ 8
+#define ITM_COUNTER_REN_SEQ 9
+#define ITM_COUNTER_POSE_QUALITY_SEQ 10
+#define ITM_COUNTER_IMAGE_MAP_EPOCH 11
+int ITM_FN(debug_counter)(int which, void* handle, const uint32_t* set, uint32_t* get);
 /* Everything the library allocates passes through one pair of functions (csrc/device_memory.h): out = {live allocations, live bytes,
  * allocations attempted since the library was loaded}, device and pinned memory together, process-wide.  Memory handed out by
  * itm_dev_malloc / itm_host_malloc is the host's and is not counted.  Host only: touches no GPU state. */

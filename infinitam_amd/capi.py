@@ -329,6 +329,9 @@ class PoseQualityStats(C.Structure):
 TRACKING_FAILED, TRACKING_POOR, TRACKING_GOOD = 0, 1, 2
 POSE_QUALITY_UNKNOWN, POSE_QUALITY_NONE = np.float32(1e30), np.float32(-1e30)
 DEBUG_POSE_QUALITY_ROWS = 29
+# itm_debug_counter (include/itm_debug.h): the forward-only 32-bit counters behind the tagged granules
+(COUNTER_LIST_EPOCH, COUNTER_FRAME_PARITY, COUNTER_TABLE_EPOCH, COUNTER_TRACKER_SEQ, COUNTER_TRACKER_SESSION, COUNTER_TRACKER_FALLBACKS,
+ COUNTER_TRACKER_RELAUNCHES, COUNTER_COLOUR_SEQ, COUNTER_REN_SEQ, COUNTER_POSE_QUALITY_SEQ, COUNTER_IMAGE_MAP_EPOCH) = range(1, 12)
 
 
 class ItmError(RuntimeError):
@@ -432,6 +435,7 @@ _HOST_IO_SIGS = {
     "debug_accel_census": (C.c_int, [_P, C.POINTER(AccelCensus), _P, _P]),
     "debug_ordered_compact": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "debug_memory": (C.c_int, [_P]),
+    "debug_counter": (C.c_int, [C.c_int, _P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "swap_integrate_global_into_local": (C.c_int, [_P, _P, _P]),
     "swap_save_to_global_memory": (C.c_int, [_P, _P, _P]),
     "global_cache_get": (C.c_int, [_P, C.c_int, _P, C.POINTER(C.c_int)]),
@@ -596,6 +600,15 @@ class Backend:
 
     def version(self) -> str:
         return self.fn["version"]().decode()
+
+    def debug_counter(self, which: int, handle, value=None) -> int:
+        """itm_debug_counter: the counter `which` (COUNTER_*) of `handle` (a scene / tracker handle, a stream for the image maps; None where
+        the header allows it) as it stood; `value`, when given, replaces it (taken modulo 2^32)."""
+        h = getattr(handle, "h", handle)
+        old = C.c_uint32()
+        new = None if value is None else C.byref(C.c_uint32(value & 0xffffffff))
+        self.check(self.fn["debug_counter"](which, h if isinstance(h, _P) else _P(h), new, C.byref(old)), "debug_counter")
+        return old.value
 
     # ---- memory in the backend's address space ---------------------------------------------
     def malloc(self, nbytes: int) -> int:

@@ -766,7 +766,17 @@ int launch_sweep_stage(itm_scene* s, const itm_view* v, itm_render_state* rs, bo
   }
   KernelTimer tv(s, ITM_TK_VISIBLE_LIST, st);
   if (onePass) {
-    const uint32_t epoch = ++s->listEpoch;
+    if (++s->listEpoch == 0u) {
+      // 2^32 launches: the stamps start over behind cleared buffers, on this stream ahead of the launch (as image_maps.hip does for
+      // its slot).  0 is never an epoch -- it is what a cell holds that no launch has stamped -- and restarting the count alone would
+      // not do: chunkSweepDone and chunkKeptGran are stamped only by the chunks / launches that had something to say, so a cell could
+      // keep a small epoch of the previous round and match it again.
+      ITM_HIP(hipMemsetAsync(s->chunkGran, 0, (size_t)nChunks * 8, st));
+      ITM_HIP(hipMemsetAsync(s->chunkSweepDone, 0, (size_t)nChunks * 4, st));
+      ITM_HIP(hipMemsetAsync(s->chunkKeptGran, 0, (size_t)nChunks * (kSweepChunk / 32) * 8, st));
+      s->listEpoch = 1u;
+    }
+    const uint32_t epoch = s->listEpoch;
     const SweepArgs sw{s->allocKey, reqNext, s->excessList, s->allocList, accel_writer(s), v->depth, lazy ? 1 : 0, s->chunkSweepDone, s->chunkKeptGran,
                        (int32_t*)s->fatalHost.device(), fusedSweep ? g_debug_force_list_stuck - 1 : -1};
 #define ITM_VL(CM, LZ, SW) visible_list_kernel<CM, LZ, SW><<<nChunks, 256, 0, st>>>(rs->visibleType, s->hash, s->chunkGran, epoch, reqCur, nChunks, s->counters, rs->visibleIds, rs->capIds, rs->counters, p, sw)

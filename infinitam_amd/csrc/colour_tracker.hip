@@ -202,6 +202,16 @@ struct itm_colour_tracker {
 
 namespace itm {
 
+int debug_counter_colour_tracker(int which, void* handle, const uint32_t* set, uint32_t* get) {
+  if (which != ITM_COUNTER_COLOUR_SEQ) return -1;
+  itm_colour_tracker* t = (itm_colour_tracker*)handle;
+  if (!t) return set_error(ITM_ERR_INVALID, "null handle");
+  std::lock_guard<std::mutex> lock(t->mu);
+  if (get) *get = t->ch.seq;
+  if (set) t->ch.seq = *set;
+  return ITM_OK;
+}
+
 static void colour_release(itm_colour_tracker* t) {
   t->ch.release();
   t->totalHost.reset(); t->pyramidMem.reset();

@@ -178,6 +178,7 @@ struct GHChannel {
   PinnedBuffer<GHBlockRecord> rec;   // pinned host records (capacity in workgroups) and their device address
   int device = -1;                   // the device of the last reserve
   unsigned int seq = 0;
+  unsigned int round = 0;            // times the numbers have started over (what a holder of further tagged records compares: tracker.hip)
 
   // the current device is not the one the records were reserved on: the handle's other buffers are of no use here either
   bool moved() const { int dev = 0; (void)hipGetDevice(&dev); return dev != device; }
@@ -192,7 +193,17 @@ struct GHChannel {
     if (e != hipSuccess) return hip_fail(e, "tracker records", __FILE__, __LINE__);
     return ITM_OK;
   }
-  unsigned int begin() { return seq = next_seq(seq); }   // the tag of the next evaluation's records
+  bool wraps() const { return next_seq(seq) < seq; }      // the next evaluation starts the numbers over
+  // The tag of the next evaluation's records.  When the numbers start over the records are cleared (tag 0: no record): the record of a
+  // workgroup that only large evaluations reach keeps the tag of the last one, and the new round hands that number out again.  Nothing
+  // is in flight here: every evaluation before this one has been collected, i.e. every record it sent has arrived.
+  unsigned int begin() {
+    if (wraps()) {
+      if (rec) memset((void*)rec.get(), 0, rec.capacity() * sizeof(GHBlockRecord));
+      ++round;
+    }
+    return seq = next_seq(seq);
+  }
   int collect(size_t blocks, unsigned int tag, hipStream_t st, double sums[kGHValues], int* n) const {
     return collect_records(rec, blocks, tag, st, sums, n);
   }

@@ -166,11 +166,10 @@ struct SlotBlock { int device; DeviceBuffer<ImageLimits> base; int used; };
 std::vector<SlotBlock>& g_slotBlocks = *new std::vector<SlotBlock>();
 }  // namespace
 
-// the slot of this call and its epoch; *words / *epoch are valid on ITM_OK
-static int acquire_limits(hipStream_t st, ImageLimits** words, uint32_t* epoch) {
+// the slot of stream `st` on the current device, created on first use (the caller holds g_slotMutex); *out is valid on ITM_OK
+static int find_slot(hipStream_t st, LimitSlot** out) {
   int device = 0;
   ITM_HIP(hipGetDevice(&device));
-  std::lock_guard<std::mutex> lock(g_slotMutex);
   LimitSlot& slot = g_slots[SlotKey{device, st}];
   if (!slot.words) {
     SlotBlock* blk = nullptr;
@@ -186,11 +185,31 @@ static int acquire_limits(hipStream_t st, ImageLimits** words, uint32_t* epoch) 
     }
     slot.words = blk->base + blk->used++;
   }
+  *out = &slot;
+  return ITM_OK;
+}
+
+// the slot of this call and its epoch; *words / *epoch are valid on ITM_OK
+static int acquire_limits(hipStream_t st, ImageLimits** words, uint32_t* epoch) {
+  std::lock_guard<std::mutex> lock(g_slotMutex);
+  LimitSlot* found = nullptr;
+  { const int rc = find_slot(st, &found); if (rc) return rc; }
+  LimitSlot& slot = *found;
   if (++slot.epoch == 0) {      // 2^32 calls on this stream: the stamps start over behind a cleared slot
     ITM_HIP(hipMemsetAsync(slot.words, 0, sizeof(ImageLimits), st));
     slot.epoch = 1;
   }
   *words = slot.words; *epoch = slot.epoch;
+  return ITM_OK;
+}
+
+int debug_counter_image_maps(int which, void* handle, const uint32_t* set, uint32_t* get) {
+  if (which != ITM_COUNTER_IMAGE_MAP_EPOCH) return -1;
+  std::lock_guard<std::mutex> lock(g_slotMutex);
+  LimitSlot* slot = nullptr;
+  { const int rc = find_slot(as_stream((itm_stream)handle), &slot); if (rc) return rc; }
+  if (get) *get = slot->epoch;
+  if (set) slot->epoch = *set;
   return ITM_OK;
 }
 

@@ -244,6 +244,13 @@ extern int g_debug_tracker_host_command;
 extern int g_debug_tracker_session_unusable;
 extern int g_debug_no_sdf_mirror;
 extern int g_debug_separate_sweep;
+// itm_debug_counter (include/itm_debug.h), one per translation unit that owns a handle type: ITM_OK when `which` is one of its own
+// (*get receives the counter, then *set replaces it), -1 when it is not
+int debug_counter_tracker(int which, void* handle, const uint32_t* set, uint32_t* get);          // tracker.hip
+int debug_counter_colour_tracker(int which, void* handle, const uint32_t* set, uint32_t* get);   // colour_tracker.hip
+int debug_counter_ren_tracker(int which, void* handle, const uint32_t* set, uint32_t* get);      // ren_tracker.hip
+int debug_counter_pose_quality(int which, void* handle, const uint32_t* set, uint32_t* get);     // pose_quality.hip
+int debug_counter_image_maps(int which, void* handle, const uint32_t* set, uint32_t* get);       // image_maps.hip
 int rebuild_sdf_mirror(itm_scene* s, hipStream_t st);
 int launch_swap_after_allocation(itm_scene* s, itm_render_state* rs, hipStream_t st);   // swapping.hip
 void free_swap_state(itm_scene* s);

@@ -123,6 +123,18 @@ struct itm_pose_quality_handle {
   itm::GHChannel ch;      // the pinned records of this handle's launches
 };
 
+namespace itm {
+int debug_counter_pose_quality(int which, void* handle, const uint32_t* set, uint32_t* get) {
+  if (which != ITM_COUNTER_POSE_QUALITY_SEQ) return -1;
+  itm_pose_quality_handle* t = (itm_pose_quality_handle*)handle;
+  if (!t) return set_error(ITM_ERR_INVALID, "null handle");
+  std::lock_guard<std::mutex> lock(t->mu);
+  if (get) *get = t->ch.seq;
+  if (set) t->ch.seq = *set;
+  return ITM_OK;
+}
+}  // namespace itm
+
 extern "C" {
 
 int itm_pose_quality_default_config(float mu, itm_pose_quality_config* cfg) {

@@ -118,6 +118,16 @@ struct itm_ren_tracker {
 
 namespace itm {
 
+int debug_counter_ren_tracker(int which, void* handle, const uint32_t* set, uint32_t* get) {
+  if (which != ITM_COUNTER_REN_SEQ) return -1;
+  itm_ren_tracker* t = (itm_ren_tracker*)handle;
+  if (!t) return set_error(ITM_ERR_INVALID, "null handle");
+  std::lock_guard<std::mutex> lock(t->mu);
+  if (get) *get = t->ch.seq;
+  if (set) t->ch.seq = *set;
+  return ITM_OK;
+}
+
 static void ren_release(itm_ren_tracker* t) {
   t->ch.release();
   t->points.reset();

@@ -467,6 +467,7 @@ struct itm_tracker {
   std::vector<itm::DeviceBuffer<float>> weightPyramid;   // weighted ICP: the sigmaZ pyramid (allocated on first use)
   int sessionUsable = -1;                 // -1 not probed yet, 0 launch per evaluation, 1 resident evaluation kernel
   int sessionFallbacks = 0;
+  unsigned int sessionRelaunches = 0;     // sessions replaced because the previous one had left (or seemed to have left) without an answer
   int debugEvaluations = 0;
   // evaluation session (gh_session_kernel)
   itm::DeviceBuffer<itm::GHBlockRecord> devRec;   // device memory: the workgroups' records of a session's fine levels (kGHGroups)
@@ -476,6 +477,7 @@ struct itm_tracker {
   itm::PinnedBuffer<itm::GHResult> res;              // pinned result + its device address
   itm::DeviceBuffer<unsigned long long> devCmd;   // device memory: republished command granules
   unsigned int session = 0;
+  unsigned int sessionRound = 0;   // ch.round for which the session's own tagged records (devRec, res->segment) were last cleared
   bool sessionOpen = false;
   bool cmdDirect = false;        // the command block is device memory the host writes through the BAR
 };
@@ -532,6 +534,23 @@ static itm_tracker* thread_tracker() {
   static thread_local itm_tracker* mine = nullptr;
   if (!mine) mine = new (std::nothrow) itm_tracker();
   return mine;
+}
+
+int debug_counter_tracker(int which, void* handle, const uint32_t* set, uint32_t* get) {
+  if (which < ITM_COUNTER_TRACKER_SEQ || which > ITM_COUNTER_TRACKER_RELAUNCHES) return -1;
+  itm_tracker* t = handle ? (itm_tracker*)handle : thread_tracker();
+  if (!t) return set_error(ITM_ERR_DEVICE, "out of host memory");
+  std::lock_guard<std::mutex> lock(t->mu);
+  if (which == ITM_COUNTER_TRACKER_SEQ) { if (get) *get = t->ch.seq; if (set) t->ch.seq = *set; return ITM_OK; }
+  if (which == ITM_COUNTER_TRACKER_SESSION) {
+    if (t->sessionOpen) return set_error(ITM_ERR_INVALID, "a session is open");
+    if (get) *get = t->session;
+    if (set) { t->session = *set; if (t->res) t->res->exited = *set; }      // as if session *set had run and left
+    return ITM_OK;
+  }
+  if (set) return set_error(ITM_ERR_INVALID, "read-only counter");
+  if (get) *get = (uint32_t)(which == ITM_COUNTER_TRACKER_FALLBACKS ? t->sessionFallbacks : t->sessionRelaunches);
+  return ITM_OK;
 }
 
 
@@ -612,8 +631,11 @@ static int session_reserve(itm_tracker* t) {
   return ITM_OK;
 }
 
+// 0 is never a session: it is "no session yet" (session_g_and_h) and what GHResult::exited holds before any session has left
+static inline unsigned int next_session(unsigned int s) { return ++s == 0u ? 1u : s; }
+
 static int session_launch(itm_tracker* t, unsigned int firstSeq, hipStream_t st) {
-  ++t->session;
+  t->session = next_session(t->session);
   gh_session_kernel<<<kGHGroups, kGHThreads, 0, st>>>(t->cmdDev, t->devCmd, t->devRec, t->res.device(), t->ch.rec.device(), t->session, firstSeq, t->cmdDirect ? 1 : 0);
   ITM_LAUNCH_CHECK();
   t->sessionOpen = true;
@@ -651,6 +673,12 @@ static int session_g_and_h(itm_tracker* trk, const float* depth, int w, int h, c
   const int tiles = gh_tiling(w, h, kSessionToHostBlocks, tileH);
   const int rounds = (tiles + kGHGroups - 1) / kGHGroups;
   using clock = std::chrono::steady_clock;
+  // The sequence numbers start over with this evaluation (2^32 evaluations on this handle): the session leaves first, so that the
+  // records in device memory and the pinned segment sums can be cleared behind it, as GHChannel::begin clears the workgroups' pinned
+  // records -- a record that only large evaluations write would otherwise meet its old tag again -- and a new session takes over.
+  // (the numbers may also have started over in an evaluation that went through a launch of its own: the rounds then differ)
+  const bool wrapping = trk->ch.wraps() || trk->sessionRound != trk->ch.round;
+  if (wrapping) session_close(trk);
   if (!trk->sessionOpen && trk->session != 0u) {
     // the previous session was told to leave; make sure it has before its exit granule is overwritten (it polls every
     // microsecond, so this is a formality -- but a session that missed its exit would wait out its idle limit)
@@ -663,6 +691,10 @@ static int session_g_and_h(itm_tracker* trk, const float* depth, int w, int h, c
       if (std::chrono::duration<double>(clock::now() - t0).count() > kPollTimeoutSeconds) return set_error(ITM_ERR_DEVICE, "tracker session did not end");
     }
   }
+  if (wrapping) {
+    ITM_HIP(hipMemsetAsync(trk->devRec, 0, kGHGroups * sizeof(GHBlockRecord), st));      // behind the session that left, ahead of the next
+    memset((void*)trk->res->segment, 0, sizeof trk->res->segment);
+  }
   ITM_TT(const auto tt0 = clock::now();)
   GHCommand c;
   memset(&c, 0, sizeof c);
@@ -672,8 +704,9 @@ static int session_g_and_h(itm_tracker* trk, const float* depth, int w, int h, c
   const int nBlocks = c.activeBlocks;
   const bool toHost = nBlocks <= kSessionToHostBlocks;
   c.toHost = toHost ? 1 : 0;
-  c.session = trk->sessionOpen ? trk->session : trk->session + 1u;
+  c.session = trk->sessionOpen ? trk->session : next_session(trk->session);
   const unsigned int seq = trk->ch.begin();
+  trk->sessionRound = trk->ch.round;
   write_command(trk, c, seq);
   ITM_TT(const auto ttA = clock::now();)
   if (!trk->sessionOpen && (rc = session_launch(trk, seq, st))) return rc;
@@ -688,8 +721,9 @@ static int session_g_and_h(itm_tracker* trk, const float* depth, int w, int h, c
       ITM_TT(fprintf(stderr, "[tracker trace] %p session %u left without answering %u: relaunch\n", (void*)trk, trk->session, seq);)
       // a session whose workgroups cannot all be resident (compute units masked or taken by another process) leaves again and
       // again without an answer: after a few replacements the caller takes the launch-per-evaluation path instead
+      ++trk->sessionRelaunches;
       if (++relaunches > 3) { trk->sessionOpen = false; return set_error(kSessionUnusable, "tracker session keeps leaving without an answer"); }
-      c.session = trk->session + 1u;           // addressed to the new session: workgroups of the old one that are still around leave at once
+      c.session = next_session(trk->session);  // addressed to the new session: workgroups of the old one that are still around leave at once
       write_command(trk, c, seq);
       return session_launch(trk, seq, st);
     }

@@ -667,6 +667,26 @@ int itm_debug_set(int key, int value) {
   return set_error(ITM_ERR_INVALID, "unknown debug key");
 }
 
+int itm_debug_counter(int which, void* handle, const uint32_t* set, uint32_t* get) {
+  if (which >= ITM_COUNTER_LIST_EPOCH && which <= ITM_COUNTER_TABLE_EPOCH) {
+    itm_scene* s = (itm_scene*)handle;
+    if (!s) return set_error(ITM_ERR_INVALID, "null scene");
+    if (which == ITM_COUNTER_LIST_EPOCH) { if (get) *get = s->listEpoch; if (set) s->listEpoch = *set; }
+    else if (which == ITM_COUNTER_FRAME_PARITY) {
+      if (set && ((*set ^ s->frameParity) & 1u)) return set_error(ITM_ERR_INVALID, "the frame count keeps its parity");
+      if (get) *get = s->frameParity;
+      if (set) s->frameParity = *set;
+    } else { if (get) *get = s->tableEpoch; if (set) s->tableEpoch = *set; }
+    return ITM_OK;
+  }
+  int rc = debug_counter_tracker(which, handle, set, get);
+  if (rc == -1) rc = debug_counter_colour_tracker(which, handle, set, get);
+  if (rc == -1) rc = debug_counter_ren_tracker(which, handle, set, get);
+  if (rc == -1) rc = debug_counter_pose_quality(which, handle, set, get);
+  if (rc == -1) rc = debug_counter_image_maps(which, handle, set, get);
+  return rc == -1 ? set_error(ITM_ERR_INVALID, "unknown counter") : rc;
+}
+
 int itm_debug_memory(int64_t out[3]) {
   if (!out) return set_error(ITM_ERR_INVALID, "null argument");
   const MemoryStats& m = memory_stats();
