@@ -52,11 +52,15 @@ struct FuseParams {
 // EARLY_OUT: the conservative frustum test in front of the divisions.  It pays where most voxels leave through it (a dense volume: ~70 %
 // of the voxels are outside the image) and costs four products and four comparisons per voxel where hardly any does (the blocks of a
 // visible list: the hash kernels run without it -- round 6, ~10 % of their vector instructions).
-template <bool EARLY_OUT = true>
+// IN_RANGE: the caller has shown that pc.z lies in [1e-4, 1e4] (integrate_item decides it once for all voxels of its item): neither the
+// pc.z <= 0 exit nor the IEEE-division side is compiled in; the arithmetic that remains is the other form's, operation for operation.
+template <bool EARLY_OUT = true, bool IN_RANGE = false>
 __device__ inline int fuse_depth_project(float mx, float my, float mz, const FuseParams& p, float& pcz) {
   Vec3 pc = transform_point(p.M_d, mx, my, mz);
   pcz = pc.z;
-  if (pc.z <= 0) return -1;
+  if constexpr (!IN_RANGE) {
+    if (pc.z <= 0) return -1;
+  }
   const float tx = p.fx * pc.x, ty = p.fy * pc.y;
 #if ITM_FAST_DIVISIONS
   // Conservative early-out before the two divisions: the voxel is rejected below when
@@ -67,7 +71,7 @@ __device__ inline int fuse_depth_project(float mx, float my, float mz, const Fus
         ty < (0.5f - p.cy) * pc.z || ty > ((float)(p.H - 2) + 0.5f - p.cy) * pc.z) return -1;
   }
   float u, v;
-  if (pc.z >= 1e-4f && pc.z <= 1e4f) {       // normal range: shared refined reciprocal, exact quotients
+  if (IN_RANGE || (pc.z >= 1e-4f && pc.z <= 1e4f)) {       // normal range: shared refined reciprocal, exact quotients
     const float rz = refined_rcp(pc.z);
     u = div_by_rcp(tx, pc.z, rz) + p.cx;
     v = div_by_rcp(ty, pc.z, rz) + p.cy;
@@ -285,9 +289,29 @@ __device__ inline void integrate_item(const HashEntry& he, int z0, int lane, typ
   int pix[kSlices];
   float pcz[kSlices], mz[kSlices];
 #pragma unroll
-  for (int k = 0; k < kSlices; ++k) {
-    mz[k] = (float)(he.pz * kBlockSide + z0 + k) * p.voxelSize;
-    pix[k] = present ? fuse_depth_project<false>(mx, my, mz[k], p, pcz[k]) : -2;     // -2: no block
+  for (int k = 0; k < kSlices; ++k) mz[k] = (float)(he.pz * kBlockSide + z0 + k) * p.voxelSize;
+  // ONE range decision per item instead of one per voxel (short voxel types; the second copy of the projection would cost ITMVoxel_f_rgb
+  // three registers).  fuse_depth_project takes its short, division-free form for pc.z in [1e-4, 1e4] and leaves at pc.z <= 0.
+  // pc.z = ((m2 mx + m6 my) + m10 mz) + m14 is evaluated in float without contraction; along a lane's column only mz changes,
+  // mz[k] = (float)(integer) * voxelSize is monotone in k, and a rounded product and a rounded sum are monotone in each operand: a lane's
+  // pc.z values are monotone in k, so all of them lie between the first slice's and the last's.  (Should an intermediate overflow, an end
+  // value is infinite or NaN and fails the test.)  Both ends inside the range for EVERY lane -- one ballot -- therefore shows exactly, with
+  // no margin to argue about, that every voxel of the item takes the short form and none the pc.z <= 0 exit; the projection compiled for
+  // that case has neither the tests nor the IEEE divisions in it.  Any other item runs the per-voxel code
+  // (tests/test_integrate_uniform_paths.py restates the decision in float32 and checks it against every voxel of blocks at the bounds).
+  // Measured on BASELINE configs[1]: -6 % vector, -14 % scalar instructions per launch (profiles/integrate_uniform_notes.md).
+  bool inRange = false;
+  if constexpr (ITM_FAST_DIVISIONS && VX::kShort) {
+    const float za = transform_point(p.M_d, mx, my, mz[0]).z, zb = transform_point(p.M_d, mx, my, mz[kSlices - 1]).z;      // (the values the projections below compute again)
+    const bool ok = za >= 1e-4f && za <= 1e4f && zb >= 1e-4f && zb <= 1e4f;
+    inRange = present && __builtin_amdgcn_ballot_w64(ok) == __builtin_amdgcn_ballot_w64(true);
+  }
+  if (inRange) {
+#pragma unroll
+    for (int k = 0; k < kSlices; ++k) pix[k] = fuse_depth_project<false, true>(mx, my, mz[k], p, pcz[k]);
+  } else {
+#pragma unroll
+    for (int k = 0; k < kSlices; ++k) pix[k] = present ? fuse_depth_project<false>(mx, my, mz[k], p, pcz[k]) : -2;     // -2: no block
   }
   float dm[kSlices];
 #pragma unroll

@@ -141,25 +141,40 @@ __device__ inline void project_partial_body(int part, uint2* cells, const int32_
   __syncthreads();
   const int nv = rc->noVisibleEntries;
   int need = 0;
-  for (int e = part * 512 + tid; e < nv; e += kRangeParts * 512) {
-    const HashEntry he = unpack_entry(hash[ids[e]]);
-    const Projected r = project_block(he, p);
-    projBuf[2 * e] = make_uint4((uint32_t)r.ulx, (uint32_t)r.uly, (uint32_t)r.lrx, (uint32_t)r.lry);
-    projBuf[2 * e + 1] = make_uint4(__float_as_uint(r.z0), __float_as_uint(r.z1), (uint32_t)r.n, 1u);
-    if (r.n == 0) continue;
-    need += r.n;
-    const uint32_t z0 = __float_as_uint(r.z0), z1 = __float_as_uint(r.z1);
-    for (int y = r.uly; y <= r.lry; ++y)
-      for (int x = r.ulx; x <= r.lrx; ++x) {
-        if (x < RW && y < RH) {
-          atomicMin(&cells[x + y * RW].x, z0);
-          atomicMax(&cells[x + y * RW].y, z1);
-        } else {
-          uint32_t* px = (uint32_t*)&range[x + y * p.W];
-          atomicMin(px, z0);
-          atomicMax(px + 1, z1);
+  // The list in kRangeParts equal runs, a lane's entries two at a time.  With more than kRangeParts * 512 visible blocks (BASELINE
+  // configs[1]: 9.6 k) some lanes project a second block.  Dealt out part * 512 + tid with a stride of kRangeParts * 512, all of that
+  // second pass fell to the first parts -- eight waves of it, two to a SIMD, its two dependent round trips (id, entry) starting only
+  // when the first pass had ended -- and those workgroups were the last of the fused launch to finish (per-workgroup stamps: 15.1-15.5 us
+  // against 9.5-11.5 for the other parts and 15.0 for the last integration workgroup).  Now every part gets the same share of it, a wave
+  // or two, each alone on its SIMD, and both entries are requested together: every part ends at 11.9-12.7 us
+  // (profiles/integrate_uniform_notes.md).  The partition does not matter to the result: the partial images are merged by min / max.
+  const int per = (nv + kRangeParts - 1) / kRangeParts;
+  const int hi = min(nv, (part + 1) * per);
+  for (int e0 = part * per + tid; e0 < hi; e0 += 2 * 512) {
+    const bool two = e0 + 512 < hi;
+    const int idA = ids[e0], idB = ids[two ? e0 + 512 : e0];
+    const uint4 rawA = hash[idA], rawB = hash[idB];
+    for (int half = 0; half < (two ? 2 : 1); ++half) {
+      const int e = e0 + half * 512;
+      const HashEntry he = unpack_entry(half ? rawB : rawA);
+      const Projected r = project_block(he, p);
+      projBuf[2 * e] = make_uint4((uint32_t)r.ulx, (uint32_t)r.uly, (uint32_t)r.lrx, (uint32_t)r.lry);
+      projBuf[2 * e + 1] = make_uint4(__float_as_uint(r.z0), __float_as_uint(r.z1), (uint32_t)r.n, 1u);
+      if (r.n == 0) continue;
+      need += r.n;
+      const uint32_t z0 = __float_as_uint(r.z0), z1 = __float_as_uint(r.z1);
+      for (int y = r.uly; y <= r.lry; ++y)
+        for (int x = r.ulx; x <= r.lrx; ++x) {
+          if (x < RW && y < RH) {
+            atomicMin(&cells[x + y * RW].x, z0);
+            atomicMax(&cells[x + y * RW].y, z1);
+          } else {
+            uint32_t* px = (uint32_t*)&range[x + y * p.W];
+            atomicMin(px, z0);
+            atomicMax(px + 1, z1);
+          }
         }
-      }
+    }
   }
   const int sum = block_reduce_sum<8>(need, lds);
   if (tid == 0 && sum) atomicAdd(&rc->noRenderingBlocks, sum);

@@ -27,7 +27,8 @@ st = np.zeros((n, 2), np.uint64)
 assert be.lib.itm_debug_read_fused_stamps(st.ctypes.data_as(C.c_void_p), n * 2) == 0
 t0 = st[:, 0].min()
 s = (st - t0).astype(np.float64) / 100.0     # us (100 MHz clock)
-proj, integ = s[:32], s[32:]   # (with dynamic queues the first 32 workgroups project, then integrate as well)
+proj, integ = s[:16], s[16:]   # the first kRangeParts = 16 workgroups project
+print("launch span %.2f us; projection workgroups end at" % s[:, 1].max(), np.sort(proj[:, 1]).round(2))
 print("projection  workgroups: start %.2f..%.2f us, end %.2f..%.2f us, duration mean %.2f max %.2f" % (proj[:, 0].min(), proj[:, 0].max(), proj[:, 1].min(), proj[:, 1].max(), (proj[:, 1] - proj[:, 0]).mean(), (proj[:, 1] - proj[:, 0]).max()))
 print("integration workgroups: start %.2f..%.2f us, end %.2f..%.2f us, duration mean %.2f max %.2f" % (integ[:, 0].min(), integ[:, 0].max(), integ[:, 1].min(), integ[:, 1].max(), (integ[:, 1] - integ[:, 0]).mean(), (integ[:, 1] - integ[:, 0]).max()))
 print("integration end percentiles (us):", np.percentile(integ[:, 1], [10, 50, 90, 99, 100]).round(2))
@@ -41,4 +42,4 @@ print("visible blocks %d: %d workgroups with work (duration mean %.2f, start mea
     nv, len(busy), (busy[:, 1] - busy[:, 0]).mean(), busy[:, 0].mean(), busy[:, 1].max(), len(idle), (idle[:, 1] - idle[:, 0]).mean() if len(idle) else 0, idle[:, 1].max() if len(idle) else 0))
 for lo in range(0, len(integ), max(1, len(integ) // 8)):
     seg = integ[lo:lo + max(1, len(integ) // 8)]
-    print("  workgroups %4d..%4d: start %.2f..%.2f  end %.2f..%.2f" % (lo + 32, lo + 32 + len(seg) - 1, seg[:, 0].min(), seg[:, 0].max(), seg[:, 1].min(), seg[:, 1].max()))
+    print("  workgroups %4d..%4d: start %.2f..%.2f  end %.2f..%.2f" % (lo + 16, lo + 16 + len(seg) - 1, seg[:, 0].min(), seg[:, 0].max(), seg[:, 1].min(), seg[:, 1].max()))
