@@ -100,7 +100,7 @@ struct itm_scene {
   bool orgPlaced = false;         // false until the first frame (or an upload) has placed the cubes
   long long accelMoves = 0;       // times the cubes were re-placed (itm_scene_accel_info)
   uint32_t frameParity = 0;
-  // dense integration: min / max tiles of the frame's depth image (integrate.hip), allocated on first use
+  // dense integration: min / max tiles of the frame's depth image (integrate_dense.hip), allocated on first use
   itm::DeviceBuffer<float2> depthTiles;
   itm::Profiler* prof = nullptr;
   // engine calls recorded but not yet launched (pending.hip): the render state that holds them, or nullptr
@@ -269,6 +269,8 @@ int validate_allocate(const itm_scene* s, const itm_view* v, const itm_render_st
 int validate_integrate(const itm_scene* s, const itm_view* v);
 int cancel_ahead(itm_scene* s, itm_render_state* rs, hipStream_t st);
 int launch_integrate(itm_scene* s, const itm_view* v, itm_render_state* rs, hipStream_t st, bool fuseProjection = false);
+struct FuseParams;                                     // fuse_device.h
+int launch_integrate_dense(itm_scene* s, const itm_view* v, const FuseParams& p, hipStream_t st);   // integrate_dense.hip: the dense half of launch_integrate
 bool can_fuse_projection(const itm_scene* s, const itm_render_state* rs);
 int launch_find_visible(const itm_scene* s, const float* M, const float* intr, itm_render_state* rs, hipStream_t st);
 int launch_expected_depths(const itm_scene* s, const float* M, const float* intr, itm_render_state* rs, bool rangeAlreadyInit, hipStream_t st, bool projected = false);

@@ -1,4 +1,4 @@
-"""Dense integration: the per-column frustum cull (integrate.hip, ColumnCull) must never drop a voxel the exact per-voxel test of
+"""Dense integration: the per-column frustum cull (integrate_dense.hip, ColumnCull) must never drop a voxel the exact per-voxel test of
 computeUpdatedVoxelDepthInfo (DeviceAgnostic/ITMSceneReconstructionEngine.h:9-50) keeps.  The volume after integrating from cameras
 in general position -- rotated about all three axes, inside and outside the volume, looking along and across its faces -- must be
 bit-identical to the oracle's, and the per-group test (debug key 9) must give the same volume."""
@@ -44,7 +44,7 @@ CAMERAS = [
 ]
 
 
-def integrate_all(be, keys=(), values=None):
+def integrate_all(be, keys=(), values=None, size=(128, 128, 128), offset=(-64, -64, 100), cameras=CAMERAS, **params):
     values = dict(values or {})
     for k in keys:
         values[k] = 1
@@ -53,12 +53,12 @@ def integrate_all(be, keys=(), values=None):
         be.check(be.fn["debug_set"](k, val), "debug_set")
     try:
         W, H = 160, 120
-        s = be.create_scene(capi.VOXEL_S, capi.INDEX_DENSE, capi.default_params(voxelSize=0.008, mu=0.04), denseSize=(128, 128, 128), denseOffset=(-64, -64, 100))
+        s = be.create_scene(capi.VOXEL_S, capi.INDEX_DENSE, capi.default_params(voxelSize=0.008, mu=0.04, **params), denseSize=size, denseOffset=offset)
         s.reco.ResetScene()
         rs = s.vis.CreateRenderState((W, H))
         rng = np.random.default_rng(7)
         volumes = []
-        for i, (ang, pos) in enumerate(CAMERAS):
+        for i, (ang, pos) in enumerate(cameras):
             depth = ((5.0 if pos[2] < -1 else 1.0) + 0.5 * rng.random((H, W))).astype(F)          # every pixel valid: every projected voxel is touched or rejected by eta
             depth[::7, ::5] = 0.0                                       # and a few invalid ones
             v = capi.View(be.to_backend(depth), W, H, M_d=pose(rotation(*ang), pos), intr_d=(145.0, 145.0, 80.0, 60.0))
@@ -90,6 +90,55 @@ def test_column_cull_equals_exact_test_for_cameras_in_general_position(hip, orac
         assert np.array_equal(a, e), "camera %d (classification after the fetch)" % i
         touched += int(np.count_nonzero(a.view(np.uint32) != want[i - 1].view(np.uint32))) if i else int(np.count_nonzero(a.view(np.uint32) != 32767))
     assert touched > 500000          # the cameras really see the volume
+
+
+# ---- small volumes that take every path of the ITMVoxel_s launch, against the oracle after every frame -----------------------------
+# x size -> what it exercises (y = 40, z = 24 throughout: rows shorter than one strip of 64 groups, under 100 k voxels):
+#   96: sx4 = 24, no power of two, no whole strip; 960 groups per slice, so with two splits of a slice the paired loop and its tail both run
+#   64: sx4 = 16, a power of two: the column interval and the classified kernels
+#   90: sx % 4 != 0: the generic one-voxel-per-lane kernel
+# The slab lies across the noisy surface (depth 1.0 .. 1.5 m) of four of the CAMERAS; maxW = 2 with stopIntegratingAtMaxW, so voxels saturate on the way.
+SMALL_CAMERAS = [CAMERAS[0], CAMERAS[1], CAMERAS[2], CAMERAS[8]]
+SMALL_KEYS = [{}, {16: 1}, {17: 1}, {16: 1, 17: 1}, {16: 2, 17: 1}, {17: 3}, {9: 1}, {9: 1, 17: 1}]
+# changed words summed over the four frames: half of what the oracle gave when the test was written (174 120, 117 466, 164 416)
+SMALL_FLOOR = {96: 87060, 64: 58733, 90: 82208}
+_small_want = {}
+
+
+def small_volumes(be, sx, values=None):
+    """Per frame, every voxel as the word sdf | w_depth << 16 (the fourth byte of an ITMVoxel_s is padding and is not part of the download's dtype)."""
+    vols = integrate_all(be, values=values, size=(sx, 40, 24), offset=(-(sx // 2), -20, 140), cameras=SMALL_CAMERAS, maxW=2, stopIntegratingAtMaxW=True)
+    return [v["sdf"].view(np.uint16).astype(np.uint32) | (v["w_depth"].astype(np.uint32) << 16) for v in vols]
+
+
+def small_want(oracle, sx):
+    if sx not in _small_want:
+        _small_want[sx] = small_volumes(oracle, sx)
+    return _small_want[sx]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("values", SMALL_KEYS, ids=lambda v: "-".join("k%d=%d" % kv for kv in v.items()) or "default")
+@pytest.mark.parametrize("sx", [96, 64, 90])
+def test_small_dense_volumes_equal_the_oracle_in_every_launch_shape(hip, oracle, sx, values):
+    want = small_want(oracle, sx)
+    got = small_volumes(hip, sx, values)
+    changed = 0
+    for i, (a, b) in enumerate(zip(want, got)):
+        assert np.array_equal(a, b), "frame %d: %d voxels differ" % (i, int(np.count_nonzero(a != b)))
+        changed += int(np.count_nonzero(a != (want[i - 1] if i else 32767)))
+    assert changed > SMALL_FLOOR[sx], changed          # the frames really touch the volume
+    assert np.count_nonzero((want[-1] >> 16) == 2) > 0          # and weights reach maxW
+
+
+@pytest.mark.gpu
+def test_small_dense_volume_check_mode_counts_no_violation(hip, oracle):
+    c = (C.c_int32 * 4)()
+    hip.check(hip.fn["debug_dense_classify_check"](c, 1), "classify_check")
+    got = small_volumes(hip, 64, {16: 3, 17: 1})
+    hip.check(hip.fn["debug_dense_classify_check"](c, 1), "classify_check")
+    assert all(np.array_equal(a, b) for a, b in zip(small_want(oracle, 64), got))
+    assert c[3] == 0 and c[0] + c[1] + c[2] > 0, list(c)
 
 
 # ---- the interval itself, on the host: thousands of poses against the exact float test ---------------------------------------------
@@ -175,7 +224,7 @@ def test_dense_ray_cast_from_cameras_in_general_position(hip, oracle):
     assert found > 20000          # the cameras really hit the surface, and most rays leave without a hit
 
 
-# ---- free-space / shadow classification of 4-voxel groups against the depth tiles (integrate.hip, classify_group) -------------------
+# ---- free-space / shadow classification of 4-voxel groups against the depth tiles (integrate_dense.hip, classify_group) -------------------
 def smooth_scene_volumes(be, stop_at_max, mode, frames=7, check=None, no_strips=0):
     """The sphere + wall scene fused into a 128^3 dense volume around the sphere (smooth depth: most groups lie in observed free
     space or in the sphere's shadow), from the parity trajectory and two rotated cameras; maxW 4, so weights saturate on the way."""

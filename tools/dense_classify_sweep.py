@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Seeded sweep of the dense integration's classification (integrate.hip: classify_group, strip kernel): random volumes, voxel sizes,
+"""Seeded sweep of the dense integration's classification (integrate_dense.hip: classify_group, strip kernel): random volumes, voxel sizes,
 band widths, intrinsics and 6-DoF poses over smooth depth images (sphere + wall, random holes, an occasional NaN / zero region).
 Per case and frame (a) the check mode -- classify every group, run the exact path anyway, count disagreements -- must report none,
 and (b) the strip kernel's volume must equal the volume of the unclassified exact path, bit for bit.  GPU against GPU: no oracle
