@@ -572,7 +572,13 @@ int ITM_FN(upload)(itm_scene* scene, itm_render_state* rs, int which, const void
 /* Scene checkpoint: one file per memory block in the layout of ORUtils/MemoryBlockPersister.h:17-130
  * (int32 element count, then the raw elements): hash.dat (ITMHashEntry), excess.dat (int), alloc.dat (int),
  * voxel.dat (TVoxel), counters.dat (itm_counters as 8 ints), config.dat (itm_scene_config + itm_scene_params as bytes,
- * checked on load), and for a render state visible_ids.dat (int) / visible_type.dat (uchar).  Loading into a scene of
+ * checked on load), and for a render state visible_ids.dat (int) / visible_type.dat (uchar).  A scene created with
+ * useSwapping also writes swap_states.dat (uchar per table entry: 0, 1, 2), cache_flags.dat (uchar per table entry:
+ * ITMGlobalCache::hasStoredData, 0 / 1) and cache_blocks.dat (TVoxel: the 512 voxels of every flagged entry's cached block,
+ * flagged entries only, in entry order -- never the whole cache); entries with ptr == -1 have their voxels nowhere else.
+ * Loading validates every file before anything of the scene is replaced (a refused load leaves scene, render state and host
+ * cache untouched); a swapping scene refuses a checkpoint without those three files, states or flags out of range, and a
+ * block count other than the number of flags set, and its host cache is replaced wholesale.  Loading into a scene of
  * the same configuration and continuing gives bit-identical results to the uninterrupted run.  `dir` must exist. */
 int ITM_FN(scene_save)(const itm_scene* scene, const itm_render_state* rs, const char* dir, itm_stream stream);
 int ITM_FN(scene_load)(itm_scene* scene, itm_render_state* rs, const char* dir, itm_stream stream);

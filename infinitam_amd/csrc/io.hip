@@ -189,6 +189,18 @@ static int load_block(const std::string& file, void* data, size_t bytes, size_t 
   fclose(f);
   return ok ? ITM_OK : fail("truncated " + file);
 }
+// A block whose element count is the file's own to say (the cached blocks of a swapping scene): the file must hold exactly that many.
+static int load_counted_block(const std::string& file, std::vector<char>& data, size_t elemBytes) {
+  FILE* f = fopen(file.c_str(), "rb");
+  if (!f) return fail("cannot open " + file);
+  int32_t count = -1;
+  long size = -1;
+  bool ok = fread(&count, 4, 1, f) == 1 && fseek(f, 0, SEEK_END) == 0 && (size = ftell(f)) >= 4 && fseek(f, 4, SEEK_SET) == 0;
+  if (ok && (count < 0 || (unsigned long long)(size - 4) != (unsigned long long)count * elemBytes)) { fclose(f); return fail("element count and length of " + file + " disagree"); }
+  if (ok) { data.resize((size_t)count * elemBytes); ok = data.empty() || fread(data.data(), 1, data.size(), f) == data.size(); }
+  fclose(f);
+  return ok ? ITM_OK : fail("truncated " + file);
+}
 
 struct BlockFile { int which; const char* name; size_t elemBytes; bool render; };
 
@@ -198,7 +210,12 @@ static void checkpoint_blocks(const itm_scene* s, std::vector<BlockFile>& v) {
   v.push_back({ITM_BUF_ALLOCATION_LIST, "alloc.dat", 4, false});
   v.push_back({ITM_BUF_VOXEL_BLOCKS, "voxel.dat", (size_t)itm_voxel_size_bytes(s->cfg.voxelType), false});
   if (hash) { v.push_back({ITM_BUF_VISIBLE_IDS, "visible_ids.dat", 4, true}); v.push_back({ITM_BUF_VISIBLE_TYPE, "visible_type.dat", 1, true}); }
+  // a swapping scene: the swap state of every entry.  The host cache goes beside it: its flags (cache_flags.dat) and, compactly, the
+  // blocks of the flagged entries in entry order (cache_blocks.dat) -- a table entry with ptr == -1 has its voxels nowhere else.
+  if (hash && s->swapHost) v.push_back({ITM_BUF_SWAP_STATES, "swap_states.dat", 1, false});
 }
+static const char* const kCacheFlagsFile = "cache_flags.dat";
+static const char* const kCacheBlocksFile = "cache_blocks.dat";
 
 int itm_scene_save(const itm_scene* s, const itm_render_state* rs, const char* dir, itm_stream stream) {
   if (!s || !dir) return fail("null argument");
@@ -224,8 +241,17 @@ int itm_scene_save(const itm_scene* s, const itm_render_state* rs, const char* d
     if (rc) return abandon(rc);
     if ((rc = stage(d + b.name, host.data(), bytes, b.elemBytes))) return abandon(rc);
   }
+  int rc;
+  if (s->swapHost) {
+    std::vector<uint8_t> flags; std::vector<char> cached;
+    itm::swap_cache_export(s, flags, cached);
+    const size_t voxBytes = (size_t)itm_voxel_size_bytes(s->cfg.voxelType);
+    if (cached.size() / voxBytes > (size_t)INT32_MAX) return abandon(fail("host cache too large for one memory block"));
+    if ((rc = stage(d + kCacheFlagsFile, flags.data(), flags.size(), 1))) return abandon(rc);
+    if ((rc = stage(d + kCacheBlocksFile, cached.data(), cached.size(), voxBytes))) return abandon(rc);
+  }
   itm_counters c;
-  int rc = itm_get_counters(s, rs, &c, stream);
+  rc = itm_get_counters(s, rs, &c, stream);
   if (rc) return abandon(rc);
   if ((rc = stage(d + "counters.dat", &c, sizeof c, 4))) return abandon(rc);
   char cfg[sizeof(itm_scene_config) + sizeof(itm_scene_params)];
@@ -238,7 +264,9 @@ int itm_scene_save(const itm_scene* s, const itm_render_state* rs, const char* d
 
 // Everything is read into host memory and validated BEFORE the first byte reaches the scene: a truncated, mismatched or
 // corrupt checkpoint leaves the scene exactly as it was.  Checked: the configuration AND the scene parameters, every block's
-// element count, the counters against the pool sizes, every table entry / list element / visible id against its range.
+// element count, the counters against the pool sizes, every table entry / list element / visible id against its range; of a swapping
+// scene also the swap states (0, 1, 2), the cache flags (0, 1) and that there are as many cached blocks as flags.  Such a scene refuses
+// a checkpoint without those files, and its host cache is replaced wholesale.
 int itm_scene_load(itm_scene* s, itm_render_state* rs, const char* dir, itm_stream stream) {
   if (!s || !dir) return fail("null argument");
   if (rs && rs->scene != s) return fail("render state belongs to another scene");
@@ -280,7 +308,24 @@ int itm_scene_load(itm_scene* s, itm_render_state* rs, const char* dir, itm_stre
       const unsigned char* t = (const unsigned char*)host[i].data();        // entriesVisibleType: 0 invisible, 1 / 2 visible (in memory / swapped out), 3 visible in the previous frame
       for (size_t k = 0; k < n; ++k)
         if (t[k] > 3) return fail("visible_type.dat: not a visibility type");
+    } else if (b.which == ITM_BUF_SWAP_STATES) {
+      const unsigned char* t = (const unsigned char*)host[i].data();
+      for (size_t k = 0; k < n; ++k)
+        if (t[k] > 2) return fail("swap_states.dat: not a swap state");
     }
+  }
+  std::vector<uint8_t> cacheFlags; std::vector<char> cached;
+  if (s->swapHost) {
+    cacheFlags.resize((size_t)s->noTotalEntries);
+    if ((rc = load_block(d + kCacheFlagsFile, cacheFlags.data(), cacheFlags.size(), 1))) return rc;
+    size_t stored = 0;
+    for (uint8_t f : cacheFlags) {
+      if (f > 1) return fail("cache_flags.dat: not a flag");
+      stored += f;
+    }
+    const size_t voxBytes = (size_t)itm_voxel_size_bytes(s->cfg.voxelType);
+    if ((rc = load_counted_block(d + kCacheBlocksFile, cached, voxBytes))) return rc;
+    if (cached.size() != stored * 512 * voxBytes) return fail("cache_blocks.dat: the number of blocks is not the number of flags set");
   }
   if (rs) rs->denseRangeReady = false;        // validated: from here on the scene is being replaced
   for (size_t i = 0; i < blocks.size(); ++i) {
@@ -288,6 +333,7 @@ int itm_scene_load(itm_scene* s, itm_render_state* rs, const char* dir, itm_stre
     if (b.render && !rs) continue;
     if ((rc = itm_upload(s, rs, b.which, host[i].data(), host[i].size(), stream))) return rc;   // also rebuilds the occupancy bitmap / directory
   }
+  if (s->swapHost) itm::swap_cache_replace(s, cacheFlags.data(), cached.data());
   return itm_set_counters(s, rs, &c, stream);
 }
 

@@ -255,6 +255,10 @@ int rebuild_sdf_mirror(itm_scene* s, hipStream_t st);
 int launch_swap_after_allocation(itm_scene* s, itm_render_state* rs, hipStream_t st);   // swapping.hip
 void free_swap_state(itm_scene* s);
 int create_swap_state(itm_scene* s);
+// the host cache of a swapping scene as the checkpoint sees it (swapping.hip): the flags of all entries and, compactly, the stored
+// blocks of the flagged entries in entry order
+void swap_cache_export(const itm_scene* s, std::vector<uint8_t>& flags, std::vector<char>& blocks);
+void swap_cache_replace(itm_scene* s, const uint8_t* flags, const char* blocks);      // wholesale; inputs as swap_cache_export gives them
 int live_hash_scenes(int device);                                     // hash scenes alive on a device (scene.hip)
 int accel_unfill(itm_scene* s, hipStream_t st);                      // empties the cubes through the table that filled them
 int accel_place(itm_scene* s, const float* invM, hipStream_t st);    // (re-)places the cubes around a view

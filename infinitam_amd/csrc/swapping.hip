@@ -196,6 +196,30 @@ void free_swap_state(itm_scene* s) {
   s->swapHost = nullptr;
 }
 
+// The checkpoint's view of the cache (io.hip): what the flags say is stored, and nothing else -- the cache itself is one slot per table
+// entry (several GB of address space, mostly untouched) and is never written out whole.
+void swap_cache_export(const itm_scene* s, std::vector<uint8_t>& flags, std::vector<char>& blocks) {
+  const SwapHost* h = s->swapHost;
+  const size_t N = (size_t)s->noTotalEntries, blockBytes = (size_t)kBlockVoxels * s->voxBytes;
+  flags.assign(h->hasStored, h->hasStored + N);
+  size_t n = 0;
+  for (size_t e = 0; e < N; ++e) n += flags[e] ? 1 : 0;
+  blocks.resize(n * blockBytes);
+  size_t k = 0;
+  for (size_t e = 0; e < N; ++e)
+    if (flags[e]) memcpy(blocks.data() + (k++) * blockBytes, h->stored + e * blockBytes, blockBytes);
+}
+void swap_cache_replace(itm_scene* s, const uint8_t* flags, const char* blocks) {
+  SwapHost* h = s->swapHost;
+  const size_t N = (size_t)s->noTotalEntries, blockBytes = (size_t)kBlockVoxels * s->voxBytes;
+  size_t k = 0;
+  for (size_t e = 0; e < N; ++e) {
+    if (flags[e]) memcpy(h->stored + e * blockBytes, blocks + (k++) * blockBytes, blockBytes);
+    else if (h->hasStored[e]) memset(h->stored + e * blockBytes, 0, blockBytes);        // as calloc left the slots that were never used
+    h->hasStored[e] = flags[e];
+  }
+}
+
 int launch_swap_after_allocation(itm_scene* s, itm_render_state* rs, hipStream_t st) {
   swap_after_allocation_kernel<<<1, kSelThreads, 0, st>>>(s->swapStates, s->hash, rs->visibleType, s->noTotalEntries, s->allocList, s->counters, accel_writer(s));
   ITM_LAUNCH_CHECK();

@@ -74,6 +74,19 @@ def reference_pool40000_backend() -> Optional[Backend]:
     return _cache["ref40000"]
 
 
+REF_SWAP_LIB = os.path.join(ORACLE_DIR, "_ref", "libitm_ref_swap.so")      # reference built with the sizes of tests/swapped_cases.py
+
+
+def reference_swap_backend() -> Optional[Backend]:
+    """The reference's CPU engines compiled with a pool of 0x4000 blocks and 0x200 blocks per swapping call (oracle/Makefile target
+    refswap)."""
+    if "refswap" not in _cache:
+        if os.path.isdir(REFERENCE_TREE):
+            subprocess.run(["make", "-C", ORACLE_DIR, "refswap"], check=not os.path.exists(REF_SWAP_LIB), capture_output=True)
+        _cache["refswap"] = Backend(REF_SWAP_LIB, "itmr_") if os.path.exists(REF_SWAP_LIB) else None
+    return _cache["refswap"]
+
+
 # Oracle outputs certified against the reference: digests of what the oracle computed in a test that compared it, bit for bit, with
 # the reference's own engines.  Where the reference build is absent those tests still run and the oracle must reproduce the record.
 REFERENCE_RECORDS = os.path.join(GOLDEN_DIR, "reference_records.json")

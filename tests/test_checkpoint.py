@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import itm_testlib as T
+import test_swapped_scene
 from infinitam_amd import capi
 from itm_testlib import Scenario
 
@@ -136,3 +137,5 @@ def test_rejected_checkpoints_leave_the_scene_untouched(hip, tmp_path):
     victim.scene.load(good, victim.rs)
     for ses in (src, victim, twin):
         ses.close()
+    # the same of a swapping scene, whose checkpoint also holds the swap states and the host cache
+    test_swapped_scene.check_refused_loads_of_a_swapping_scene(hip, tmp_path)

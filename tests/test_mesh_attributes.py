@@ -166,8 +166,9 @@ def hip_attributes(hip, sc, max_triangles=0, frames=None):
     return ses, m, tri, m.normals(), (m.colours() if sc.colour else None)
 
 
-def assert_equals_restatement(name, tri, normals, colours):
-    rtri, g, n, c = restated(name)
+def assert_equals_restatement(name, tri, normals, colours, restatement=None):
+    """restatement: (triangles, gradients, normals, colour floats | None) of a scene that is not one of MC.SCENES"""
+    rtri, g, n, c = restatement if restatement is not None else restated(name)
     assert np.array_equal(tri, rtri)
     got, want = bits(normals).reshape(-1, 3), bits(n)
     if not np.array_equal(got, want):

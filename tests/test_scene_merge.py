@@ -13,8 +13,10 @@ import pytest
 
 import itm_testlib as T
 import scene_merge_terms as M
+import swapped_cases
 import test_swapping
 from infinitam_amd import capi, synth
+from swapped_cases import swapping_scene       # (test_scene_resample builds on it through this module)
 
 W, H = 320, 240
 POOL = 0x4000              # voxel blocks per scene: the scenes below hold a few thousand (whole pools are downloaded and compared)
@@ -321,20 +323,7 @@ def test_derived_structures_after_a_merge_are_those_of_an_upload(hip, oracle, fo
             hip.check(hip.fn["debug_set"](key, 0), "debug_set")
 
 
-def swapping_scene(be, away):
-    """test_swapping's sequence at 1 cm voxels (the scene is 932 blocks then): three frames on it, then `away` frames looking at a wall,
-    in each of which 0x200 blocks leave for the host cache."""
-    intr, seq = test_swapping.poses_and_depths()
-    s = be.create_scene(capi.VOXEL_S, capi.INDEX_HASH, capi.default_params(voxelSize=0.01), useSwapping=True, localBlockNum=POOL, transferBlockNum=0x200)
-    s.reco.ResetScene()
-    rs = s.vis.CreateRenderState((W, H))
-    for Mk, depth in seq[:3 + away]:
-        v = capi.View(be.to_backend(depth), W, H, M_d=Mk, intr_d=intr)
-        s.reco.AllocateSceneFromDepth(v, rs)
-        s.reco.IntegrateIntoScene(v, rs)
-        s.swap_integrate_global_into_local(rs)
-        s.swap_save_to_global_memory(rs)
-    return s, rs
+assert (swapped_cases.W, swapped_cases.H, swapped_cases.POOL) == (W, H, POOL)
 
 
 @pytest.mark.gpu

@@ -60,25 +60,29 @@ def run(be, voxel=capi.VOXEL_S, colour=False, frames=None, localBlockNum=0):
     return out
 
 
+def compare_frame(x, y, tag):
+    """one frame's snapshots; every cached block that `sample` names"""
+    assert x["counters"] == y["counters"], tag + "%s vs %s" % (x["counters"], y["counters"])
+    T.assert_fields_equal(x["hash"], y["hash"], tag + "hash")
+    assert np.array_equal(x["swap"], y["swap"]), tag + "swap states (%d differ)" % int(np.count_nonzero(x["swap"] != y["swap"]))
+    assert np.array_equal(x["vis_type"], y["vis_type"]), tag + "visible types"
+    assert np.array_equal(x["vis_ids"], y["vis_ids"]), tag + "visible ids"
+    # the free list: entries above lastFreeBlockId are dead storage in both, below they must agree
+    n = x["counters"]["lastFreeBlockId"] + 1
+    assert np.array_equal(x["alloc"][:max(n, 0)], y["alloc"][:max(n, 0)]), tag + "allocation list"
+    T.assert_fields_equal(x["voxels"], y["voxels"], tag + "voxels")
+    assert np.array_equal(x["flags"], y["flags"]), tag + "cache flags"
+    for e, p, q in zip(x["sample"], x["blocks"], y["blocks"]):
+        T.assert_fields_equal(p, q, tag + "cached block of entry %d" % e)
+    assert np.array_equal(x["raycast"][..., 3], y["raycast"][..., 3]), tag + "hit mask"
+    hit = x["raycast"][..., 3] > 0
+    assert np.array_equal(x["raycast"][hit], y["raycast"][hit]), tag + "ray-cast hits"
+    assert np.array_equal(x["points"], y["points"]), tag + "ICP points"
+
+
 def compare(a, b, what):
     for k, (x, y) in enumerate(zip(a, b)):
-        tag = "%s frame %d: " % (what, k)
-        assert x["counters"] == y["counters"], tag + "%s vs %s" % (x["counters"], y["counters"])
-        T.assert_fields_equal(x["hash"], y["hash"], tag + "hash")
-        assert np.array_equal(x["swap"], y["swap"]), tag + "swap states (%d differ)" % int(np.count_nonzero(x["swap"] != y["swap"]))
-        assert np.array_equal(x["vis_type"], y["vis_type"]), tag + "visible types"
-        assert np.array_equal(x["vis_ids"], y["vis_ids"]), tag + "visible ids"
-        # the free list: entries above lastFreeBlockId are dead storage in both, below they must agree
-        n = x["counters"]["lastFreeBlockId"] + 1
-        assert np.array_equal(x["alloc"][:max(n, 0)], y["alloc"][:max(n, 0)]), tag + "allocation list"
-        T.assert_fields_equal(x["voxels"], y["voxels"], tag + "voxels")
-        assert np.array_equal(x["flags"], y["flags"]), tag + "cache flags"
-        for e, p, q in zip(x["sample"], x["blocks"], y["blocks"]):
-            T.assert_fields_equal(p, q, tag + "cached block of entry %d" % e)
-        assert np.array_equal(x["raycast"][..., 3], y["raycast"][..., 3]), tag + "hit mask"
-        hit = x["raycast"][..., 3] > 0
-        assert np.array_equal(x["raycast"][hit], y["raycast"][hit]), tag + "ray-cast hits"
-        assert np.array_equal(x["points"], y["points"]), tag + "ICP points"
+        compare_frame(x, y, "%s frame %d: " % (what, k))
 
 
 def sanity(frames):
