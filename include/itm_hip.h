@@ -564,7 +564,12 @@ int ITM_FN(get_counters)(const itm_scene* scene, const itm_render_state* rs, itm
 int ITM_FN(set_counters)(itm_scene* scene, itm_render_state* rs, const itm_counters* in,
                          itm_stream stream);
 size_t ITM_FN(buffer_bytes)(const itm_scene* scene, const itm_render_state* rs, int which);
-/* Synchronous copies of whole buffers between host memory and the scene / render state. */
+/* Synchronous copies of whole buffers between host memory and the scene / render state.
+ * Sentinel words: in a HASH scene two sdf words are no values -- the short -32768 (ITMVoxel_s, ITMVoxel_s_rgb) and the float word
+ * 0xffffffff (ITMVoxel_f, ITMVoxel_f_rgb; one of the NaNs).  The integration never produces them, and the scene's sdf mirror keeps
+ * them for "no block here".  An upload of ITM_BUF_VOXEL_BLOCKS into a hash scene that holds one in any voxel is refused with
+ * ITM_ERR_INVALID before anything is written (the message names the first such voxel; the scene stays as it was); -32767 and
+ * 0xfffffffe are values like any other.  Dense scenes have no mirror and accept every word, as the reference does. */
 int ITM_FN(download)(const itm_scene* scene, const itm_render_state* rs, int which, void* dst_host,
                      size_t bytes, itm_stream stream);
 int ITM_FN(upload)(itm_scene* scene, itm_render_state* rs, int which, const void* src_host,
@@ -578,7 +583,9 @@ int ITM_FN(upload)(itm_scene* scene, itm_render_state* rs, int which, const void
  * flagged entries only, in entry order -- never the whole cache); entries with ptr == -1 have their voxels nowhere else.
  * Loading validates every file before anything of the scene is replaced (a refused load leaves scene, render state and host
  * cache untouched); a swapping scene refuses a checkpoint without those three files, states or flags out of range, and a
- * block count other than the number of flags set, and its host cache is replaced wholesale.  Loading into a scene of
+ * block count other than the number of flags set, and its host cache is replaced wholesale.  A hash scene also refuses, in
+ * the same way and with ITM_ERR_INVALID, a voxel.dat or cache_blocks.dat that holds a sentinel word (see itm_upload) in any voxel;
+ * itm_scene_save never writes one, because no scene holds one.  Loading into a scene of
  * the same configuration and continuing gives bit-identical results to the uninterrupted run.  `dir` must exist. */
 int ITM_FN(scene_save)(const itm_scene* scene, const itm_render_state* rs, const char* dir, itm_stream stream);
 int ITM_FN(scene_load)(itm_scene* scene, itm_render_state* rs, const char* dir, itm_stream stream);

@@ -101,6 +101,10 @@ constexpr uint32_t kPageVoxMask = (1u << kPageVoxBits) - 1u;
 constexpr uint32_t kMirrorVoxels = (uint32_t)kMirrorSide * 8u;      // voxels per side of the cube
 constexpr size_t kMirrorTableCells = kMirrorCells >> (3 * kPageBits);      // 16^3
 constexpr int kPageNone = -1, kPageClaiming = -2, kPageUnmappable = -3;
+// kAbsent is "no block here".  It is a word no voxel of a hash scene may hold: the integration never produces it (a short sdf is
+// (short)(f * 32767) with |f| <= 1, a float sdf is never that NaN), and every way foreign voxel bytes enter a hash scene -- the upload of
+// the voxel blocks, a checkpoint's voxel.dat and cache_blocks.dat -- refuses a pool that holds it (refuse_absent_sdf_words, scene.hip;
+// include/itm_hip.h "Sentinel words").  A mirror cell copied from the pool therefore never reads as absent.
 template <bool SHORT> struct MirrorCodec;
 template <> struct MirrorCodec<true> {
   using T = int16_t;

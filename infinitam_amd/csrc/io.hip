@@ -312,6 +312,8 @@ int itm_scene_load(itm_scene* s, itm_render_state* rs, const char* dir, itm_stre
       const unsigned char* t = (const unsigned char*)host[i].data();
       for (size_t k = 0; k < n; ++k)
         if (t[k] > 2) return fail("swap_states.dat: not a swap state");
+    } else if (b.which == ITM_BUF_VOXEL_BLOCKS) {
+      if ((rc = itm::refuse_absent_sdf_words(s, host[i].data(), n, b.name))) return rc;
     }
   }
   std::vector<uint8_t> cacheFlags; std::vector<char> cached;
@@ -326,6 +328,7 @@ int itm_scene_load(itm_scene* s, itm_render_state* rs, const char* dir, itm_stre
     const size_t voxBytes = (size_t)itm_voxel_size_bytes(s->cfg.voxelType);
     if ((rc = load_counted_block(d + kCacheBlocksFile, cached, voxBytes))) return rc;
     if (cached.size() != stored * 512 * voxBytes) return fail("cache_blocks.dat: the number of blocks is not the number of flags set");
+    if ((rc = itm::refuse_absent_sdf_words(s, cached.data(), cached.size() / voxBytes, kCacheBlocksFile))) return rc;
   }
   if (rs) rs->denseRangeReady = false;        // validated: from here on the scene is being replaced
   for (size_t i = 0; i < blocks.size(); ++i) {

@@ -252,6 +252,10 @@ int debug_counter_ren_tracker(int which, void* handle, const uint32_t* set, uint
 int debug_counter_pose_quality(int which, void* handle, const uint32_t* set, uint32_t* get);     // pose_quality.hip
 int debug_counter_image_maps(int which, void* handle, const uint32_t* set, uint32_t* get);       // image_maps.hip
 int rebuild_sdf_mirror(itm_scene* s, hipStream_t st);
+// Foreign voxel bytes on their way into a HASH scene (buffer upload, checkpoint load, the checkpoint's cached blocks): ITM_ERR_INVALID, naming
+// the voxel, when one of the n voxels holds the sdf word that the sdf mirror keeps for "no block here" (MirrorCodec::kAbsent,
+// accel_device.h); `what` says where the bytes come from.  Dense scenes have no mirror and take any word.  Host memory, host only.
+int refuse_absent_sdf_words(const itm_scene* s, const void* voxels_host, size_t n, const char* what);
 int launch_swap_after_allocation(itm_scene* s, itm_render_state* rs, hipStream_t st);   // swapping.hip
 void free_swap_state(itm_scene* s);
 int create_swap_state(itm_scene* s);

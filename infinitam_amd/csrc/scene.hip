@@ -224,6 +224,21 @@ static int directory_pass(itm_scene* s, hipStream_t st) {
 // the mirror's values again from the pool (the voxels were replaced, the table was not)
 int rebuild_sdf_mirror(itm_scene* s, hipStream_t st) { return mirror_pass<true>(s, st); }
 
+int refuse_absent_sdf_words(const itm_scene* s, const void* voxels_host, size_t n, const char* what) {
+  if (s->cfg.indexType != ITM_INDEX_HASH) return ITM_OK;
+  const bool isFloat = voxel_is_float(s->cfg.voxelType);
+  const char* v = (const char*)voxels_host;      // (the sdf is the first member of every voxel type)
+  for (size_t i = 0; i < n; ++i, v += s->voxBytes) {
+    bool absent;
+    if (isFloat) { uint32_t w; memcpy(&w, v, 4); absent = MirrorCodec<false>::absent(w); }
+    else { int16_t w; memcpy(&w, v, 2); absent = MirrorCodec<true>::absent(w); }
+    if (absent)
+      return set_error(ITM_ERR_INVALID, std::string(what) + ": voxel " + std::to_string(i) + " holds the sdf word " + (isFloat ? "0xffffffff" : "-32768") +
+                                            ", which is no value in a hash scene (it marks \"no block here\" in the sdf mirror)");
+  }
+  return ITM_OK;
+}
+
 // empties the cubes: to be called while the table still holds the entries that filled them
 int accel_unfill(itm_scene* s, hipStream_t st) {
   int rc = directory_pass<false>(s, st);
@@ -883,6 +898,7 @@ int itm_upload(itm_scene* s, itm_render_state* rs, int which, const void* src, s
   if (!p || !src || bytes > b) return set_error(ITM_ERR_INVALID, "bad buffer / size");
   { const int rc = enter_scene(s, rs); if (rc) return rc; }
   if ((which == ITM_BUF_VISIBLE_IDS || which == ITM_BUF_VISIBLE_TYPE) && refuse_while_ahead(s, rs, "upload of the visible list")) return ITM_ERR_INVALID;
+  if (which == ITM_BUF_VOXEL_BLOCKS) { const int rc = refuse_absent_sdf_words(s, src, bytes / s->voxBytes, "upload of the voxel blocks"); if (rc) return rc; }      // before anything is written
   hipStream_t st = as_stream(stream);
   if (which == ITM_BUF_HASH_ENTRIES) { int rc = accel_unfill(s, st); if (rc) return rc; ++s->tableEpoch; }      // while the table still holds what filled the cubes
   ITM_HIP(hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, st));
