@@ -57,7 +57,7 @@ int ITM_FN(debug_set)(int key, int value);
  *                                   "exited" word with it, as if that kernel had run and left
  *                     TRACKER_FALLBACKS, TRACKER_RELAUNCHES  read only: sessions given up for one launch per evaluation / sessions
  *                                   replaced because the previous one seemed to have left without an answer
- *   itm_colour_tracker*, itm_ren_tracker*, itm_pose_quality_handle*   COLOUR_SEQ, REN_SEQ, POSE_QUALITY_SEQ: as TRACKER_SEQ
+ *   itm_colour_tracker*, itm_ren_tracker*, itm_pose_quality_handle*, itm_aligner*   COLOUR_SEQ, REN_SEQ, POSE_QUALITY_SEQ, ALIGN_SEQ: as TRACKER_SEQ
  *   itm_stream        IMAGE_MAP_EPOCH  epoch of the last image-map call on this stream of the current device (the slot is created if
  *                                   the stream has none yet; that allocates and zeroes a block of slots exactly as a first GetImage would) */
 #define ITM_COUNTER_LIST_EPOCH 1
@@ -71,6 +71,7 @@ int ITM_FN(debug_set)(int key, int value);
 #define ITM_COUNTER_REN_SEQ 9
 #define ITM_COUNTER_POSE_QUALITY_SEQ 10
 #define ITM_COUNTER_IMAGE_MAP_EPOCH 11
+#define ITM_COUNTER_ALIGN_SEQ 12
 int ITM_FN(debug_counter)(int which, void* handle, const uint32_t* set, uint32_t* get);
 /* Everything the library allocates passes through one pair of functions (csrc/device_memory.h): out = {live allocations, live bytes,
  * allocations attempted since the library was loaded}, device and pinned memory together, process-wide.  Memory handed out by

@@ -1219,6 +1219,111 @@ int ITM_FN(pose_quality_destroy)(itm_pose_quality_handle* handle);
 int ITM_FN(pose_quality_evaluate)(itm_pose_quality_handle* handle, const itm_scene* scene, const itm_view* view, const itm_pose_quality_config* cfg,
                                   itm_pose_quality* out, float* residuals_dev, itm_stream stream);
 
+/* ---- scene alignment: refines the rigid pose between sdf samples and a TSDF scene ------------------------------------------------------
+ * itm_scene_resample fuses src into dst under a transform that something has to supply to the accuracy the resampling works at; a
+ * relocalisation or the exchange's poses are centimetres and degrees off.  Here a coarse dstFromSrc is refined by registering SAMPLES
+ * against dst: a sample is (p, d), a point p in metres in the source frame and the signed distance d in metres it should read there.
+ * d = 0 everywhere: plain surface points (mesh vertices, a lidar sweep).  Samples taken from the voxels of a scene src
+ * (itm_scene_band_samples): sdf-to-sdf registration of two scenes.  The reference has no counterpart; this definition is the
+ * specification and tests/scene_align_terms.py its restatement.
+ *
+ * itm_scene_band_samples, sequential definition.  A stored voxel of src at global voxel coordinates (x, y, z) is KEPT when
+ *   w_depth >= cfg->minWeight,  fabsf(SDF_valueToFloat(sdf)) < cfg->maxAbsSdf (0 < maxAbsSdf <= 1; strict: a truncated +-1 is never
+ *   kept)  and  x, y and z are multiples of cfg->stride (>= 1).
+ * Its sample is the float4 ((float)x * voxelSize, (float)y * voxelSize, (float)z * voxelSize, SDF_valueToFloat(sdf) * mu): one rounding
+ * each.  Order: hash scenes in ascending table slot -- the slot list as in itm_scene_merge (NULL: every slot; duplicates count once; a
+ * slot outside the table: ITM_ERR_INVALID), entries with ptr < 0 (swapped out, free) and block pointers outside the pool skipped --
+ * and inside a block in ascending x + 8 y + 64 z; dense scenes in ascending linear index (a slot list is refused).  *count_out
+ * receives the number of kept voxels, samples_dev (device, 16-byte aligned, may be NULL when capacity is 0) the first `capacity` of
+ * them: a caller asks twice, or sizes from the voxel count.  Recorded calls of src are launched first; src is only read; `stream` is
+ * synchronised once, for the count (and once before, for the check of a slot list).
+ *
+ * itm_aligner_evaluate, sequential definition (float32, every product and sum rounded on its own, division IEEE; no transcendental
+ * function anywhere).  M = dstFromSrc (column-major, metres: x_dst = R x_src + t), sample i = (p, d):
+ *   x_k = ((R_k0 p_0 + R_k1 p_1) + R_k2 p_2) + t_k;   q = x / voxelSize  (as itm_scene_query_points forms it)
+ *   q is not finite or has !(|c| < 262136) (ITM_QUERY_INVALID's rule): the sample is invalid and nothing is read.
+ *   The eight corners of the cell floor(q) are read as readVoxel reads them.  The sample is VALID iff all eight voxels exist and none
+ *   converts to 1.0f: an absent, an unobserved and a front-truncated voxel all read 1, the rule the Ren tracker uses.  No weight is read
+ *   (minWeight acts where the samples are made).
+ *   s = readFromSDF_float_interpolated(q);  g = the derivative of that same interpolant per voxel, c = q - floor(q), v the raw corners:
+ *     g_x = (1-c_z) ((1-c_y) (v100 - v000) + c_y (v110 - v010)) + c_z ((1-c_y) (v101 - v001) + c_y (v111 - v011))
+ *     g_y = (1-c_z) ((1-c_x) (v010 - v000) + c_x (v110 - v100)) + c_z ((1-c_x) (v011 - v001) + c_x (v111 - v101))
+ *     g_z = (1-c_y) ((1-c_x) (v001 - v000) + c_x (v101 - v100)) + c_y ((1-c_x) (v011 - v010) + c_x (v111 - v110))
+ *   each blended on raw values and then converted by SDF_valueToFloat, as s is.
+ *   r = mu * s - d;   n = g * (mu / voxelSize), the quotient formed once as a float;   J = (n, x cross n), the cross product as
+ *   (x_1 n_2 - x_2 n_1, x_2 n_0 - x_0 n_2, x_0 n_1 - x_1 n_0): the derivative of r for a twist (v, w) applied on the left of M.
+ *   Huber, delta = cfg->huberDelta (metres): a = |r|;  a <= delta: w = 1, rho = (0.5f * r) * r;  else w = delta / a,
+ *   rho = delta * (a - 0.5f * delta).
+ *   Over the valid samples, added in double in a fixed order (the same call gives the same bits):
+ *     f = sum rho,   nabla_k = sum (w r) J_k,   hessian[r + c * 6] = sum (w J_r) J_c      (the products are float)
+ *   each rounded to float once at the end; noValid is exact.  No sample set, or n == 0: nothing is launched, the result is zeros.
+ *
+ * itm_aligner_align: Levenberg-Marquardt over the pose, kept in double and rounded to float once per evaluation.
+ *   The linear part of dstFromSrc_in is first brought to the rotation next to it (the steps of itm_rigid_quantise).  lambda = 1.
+ *   A step solves (H + lambda diag(H)) step = -nabla in double (a diagonal entry below 1e-15 in magnitude is replaced by
+ *   lambda * 1e-10); the trial pose is exp(step) o pose, the twist (v, w) on the left.  It is accepted when its noValid >= cfg->minValid
+ *   and its MEAN cost f / noValid is below the current one (the valid set changes with the pose: raw sums do not compare): lambda *= 0.1.
+ *   Otherwise lambda *= 10.  A system that is not positive definite counts as a rejected step without an evaluation.
+ *   The loop ends when max |step_k| < cfg->minStep (metres / radians: ITM_ALIGN_CONVERGED), when lambda > 1e8 (ITM_ALIGN_STALLED) or after
+ *   cfg->maxEvaluations evaluations (ITM_ALIGN_MAX_EVALUATIONS).  There is no relative-decrease test: with the step size as the only
+ *   criterion the last iterate lies within about a step of the fixed point.
+ *   First evaluation with noValid < cfg->minValid: ITM_ALIGN_TOO_FEW_SAMPLES and dstFromSrc_out = dstFromSrc_in, bit for bit.
+ *   conditioning = the smallest eigenvalue of S H S at the final pose, S = diag(a, a, a, b, b, b), 1 / a^2 = the largest of the three
+ *   translational and 1 / b^2 = the largest of the three rotational diagonal entries of H (cyclic Jacobi in double; 0 when a block has
+ *   no positive diagonal entry).  Metres against radians do not matter: the value does not change when either unit is rescaled.  Those
+ *   two factors are all the units account for; scaling each parameter by its OWN diagonal entry (D^-1/2 H D^-1/2, D = diag(H)) reads
+ *   0.69 -- well posed -- on the fused sphere-and-wall scene of the tests, whose free rotation happens to be about a coordinate axis:
+ *   its diagonal entry is discretisation noise, four orders below the other two rotations, and its own square root turns it into a 1.
+ *   Below cfg->minConditioning the status becomes ITM_ALIGN_DEGENERATE: the geometry does not determine the pose (a sphere in front of
+ *   a wall leaves the rotation about the wall's normal through the sphere free).  The pose is still returned, its determined directions
+ *   refined; the caller decides.
+ * itm_align_default_config(voxelSize, mu) (host only): minWeight 1, maxAbsSdf 1, stride 1, huberDelta mu / 4, minStep 1e-5,
+ * maxEvaluations 60, minValid 100, minConditioning 1e-3.  minConditioning is POLICY chosen on analytic scenes -- it lies between the
+ * 4e-6 of a sphere in front of a wall and the 7e-2 of a room corner -- nobody has tuned it on sensor data.
+ * ITM_ERR_INVALID with nothing changed: a null argument, a matrix entry that is not finite, an entry of R^T R - I above 1e-3 in
+ * magnitude, det R < 0, huberDelta <= 0, minStep <= 0, and for itm_aligner_align no samples set.  The matrix and the configuration are
+ * checked before anything else is looked at.
+ *
+ * Calls.  A handle owns its reduction records and serialises its own calls.  set_samples keeps the DEVICE pointer (float4 (p, d), 16-byte
+ * aligned) and does not copy: the samples stay the caller's and stay alive while the handle uses them.  evaluate launches dst's recorded
+ * calls first, reads dst only, enqueues ONE launch on `stream` and returns with *out filled through tagged records in page-locked host
+ * memory (no stream synchronise); align is a sequence of evaluations.  itm_align_step and itm_align_apply_step are the loop's two host
+ * steps on their own (host only): the step of an evaluation for a lambda (0 where the system is not positive definite), and
+ * exp(step) o pose rounded to float. */
+#define ITM_ALIGN_CONVERGED 0
+#define ITM_ALIGN_MAX_EVALUATIONS 1
+#define ITM_ALIGN_STALLED 2
+#define ITM_ALIGN_TOO_FEW_SAMPLES 3
+#define ITM_ALIGN_DEGENERATE 4
+typedef struct itm_aligner itm_aligner;
+typedef struct itm_align_config {
+  int32_t minWeight;         /* band samples: w_depth a voxel needs */
+  float maxAbsSdf;           /* band samples: |sdf| below this, float sdf units */
+  int32_t stride;            /* band samples: every stride-th voxel per axis */
+  float huberDelta;          /* metres */
+  float minStep;             /* metres / radians */
+  int32_t maxEvaluations, minValid;
+  float minConditioning;
+} itm_align_config;          /* 32 bytes */
+typedef struct itm_align_eval { float f; int32_t noValid; float nabla[6]; float hessian[36]; } itm_align_eval;      /* 176 bytes */
+typedef struct itm_align_result {
+  int32_t status, evaluations, noValid, reserved;
+  double initialCost, finalCost;      /* mean cost f / noValid at the first and at the final pose */
+  double conditioning;
+} itm_align_result;          /* 40 bytes */
+int ITM_FN(align_default_config)(float voxelSize, float mu, itm_align_config* cfg);
+int ITM_FN(align_step)(const itm_align_eval* eval, double lambda, float step[6]);
+int ITM_FN(align_apply_step)(const float pose[16], const float step[6], float out[16]);
+int ITM_FN(scene_band_samples)(const itm_scene* src, const int32_t* srcSlots_dev, int n, const itm_align_config* cfg, float* samples_dev, int32_t capacity,
+                               int32_t* count_out, itm_stream stream);
+int ITM_FN(aligner_create)(itm_aligner** out);
+int ITM_FN(aligner_destroy)(itm_aligner* aligner);
+int ITM_FN(aligner_set_samples)(itm_aligner* aligner, const float* samples_dev, int32_t n, itm_stream stream);
+int ITM_FN(aligner_evaluate)(itm_aligner* aligner, const itm_scene* dst, const float dstFromSrc[16], const itm_align_config* cfg, itm_align_eval* out,
+                             itm_stream stream);
+int ITM_FN(aligner_align)(itm_aligner* aligner, const itm_scene* dst, const float dstFromSrc_in[16], const itm_align_config* cfg, float dstFromSrc_out[16],
+                          itm_align_result* res, itm_stream stream);
+
 /* The acceleration structures a hash scene carries beside the reference's table (none of them part of the reference's state, all
  * derived from it): a block directory and a slot directory over a cube of 512^3 blocks, an sdf mirror over 256^3 blocks for the
  * short voxel types.  The cubes are NOT tied to the world origin: the first frame places them around its camera (the reference's

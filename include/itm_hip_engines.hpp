@@ -367,6 +367,68 @@ class ITMSceneResampleEngine_HIP {
   }
 };
 
+// Scene alignment (itm_scene_band_samples + itm_aligner_*; no reference class): the pose dstFromSrc that ResampleScene wants, refined
+// from a coarse one (a relocalisation, the poses the exchange gathers) by registering sdf samples against `dst`.  The engine owns one
+// aligner handle and the sample buffer it fills; one engine per host thread.
+template <class TVoxel, class TIndex>
+class ITMSceneAlignEngine_HIP {
+  itm_aligner* aligner = nullptr;
+  void* samples = nullptr;
+  int32_t capacity = 0, count = 0;
+
+ public:
+  itm_stream stream = nullptr;
+  ITMSceneAlignEngine_HIP() { check(itm_aligner_create(&aligner), "itm_aligner_create"); }
+  ~ITMSceneAlignEngine_HIP() { itm_aligner_destroy(aligner); if (samples) itm_dev_free(samples); }
+  ITMSceneAlignEngine_HIP(const ITMSceneAlignEngine_HIP&) = delete;
+  ITMSceneAlignEngine_HIP& operator=(const ITMSceneAlignEngine_HIP&) = delete;
+
+  static itm_align_config DefaultConfig(const ITMSceneParams* p) {
+    itm_align_config cfg;
+    check(itm_align_default_config(p->voxelSize, p->mu, &cfg), "itm_align_default_config");
+    return cfg;
+  }
+  // The samples are the band voxels of `src` (srcVisible: a render state of src whose visible list selects the blocks; nullptr: all);
+  // returns how many there are.
+  int32_t SetSamplesFromScene(const ITMScene<TVoxel, TIndex>* src, const itm_align_config& cfg, const ITMRenderState* srcVisible = nullptr) {
+    const int32_t* slots = nullptr;
+    int n = 0;
+    if (srcVisible) {
+      itm_counters c;
+      check(itm_get_counters(src->handle, srcVisible->handle, &c, stream), "AlignScene (visible list)");
+      slots = (const int32_t*)itm_buffer_ptr(src->handle, srcVisible->handle, ITM_BUF_VISIBLE_IDS);
+      n = c.noVisibleEntries;
+      if (!slots) throw std::runtime_error("AlignScene: the render state has no visible list");
+    }
+    for (int pass = 0; pass < 2; ++pass) {      // the second pass only when the buffer had to grow
+      check(itm_scene_band_samples(src->handle, slots, n, &cfg, (float*)samples, capacity, &count, stream), "AlignScene (itm_scene_band_samples)");
+      if (count <= capacity) break;
+      if (samples) { itm_dev_free(samples); samples = nullptr; capacity = 0; }
+      check(itm_dev_malloc(&samples, (size_t)count * 16), "AlignScene (samples)");
+      capacity = count;
+    }
+    check(itm_aligner_set_samples(aligner, (const float*)samples, count, stream), "AlignScene (itm_aligner_set_samples)");
+    return count;
+  }
+  // The caller's own samples: device float4 (x, y, z in metres in the source frame, the signed distance in metres to read there); kept, not copied
+  void SetSamples(const float* samples_dev, int32_t n) { check(itm_aligner_set_samples(aligner, samples_dev, n, stream), "itm_aligner_set_samples"); }
+  void Evaluate(const ITMScene<TVoxel, TIndex>* dst, const Matrix4f& dstFromSrc, const itm_align_config& cfg, itm_align_eval* out) {
+    check(itm_aligner_evaluate(aligner, dst->handle, dstFromSrc.m, &cfg, out, stream), "itm_aligner_evaluate");
+  }
+  // dstFromSrc: the coarse pose on entry, the refined one on return.  res->status says what the result is worth (ITM_ALIGN_*).
+  void Align(const ITMScene<TVoxel, TIndex>* dst, Matrix4f& dstFromSrc, const itm_align_config& cfg, itm_align_result* res = nullptr) {
+    float out[16];
+    check(itm_aligner_align(aligner, dst->handle, dstFromSrc.m, &cfg, out, res, stream), "itm_aligner_align");
+    dstFromSrc = Matrix4f(out);
+  }
+  void AlignScene(const ITMScene<TVoxel, TIndex>* dst, const ITMScene<TVoxel, TIndex>* src, Matrix4f& dstFromSrc, itm_align_result* res = nullptr,
+                  const itm_align_config* cfg = nullptr) {
+    const itm_align_config c = cfg ? *cfg : DefaultConfig(dst->sceneParams);
+    SetSamplesFromScene(src, c);
+    Align(dst, dstFromSrc, c, res);
+  }
+};
+
 // Scene queries (itm_scene_query_points / itm_scene_cast_rays; the reference makes these reads only per pixel, inside its engines):
 // readFromSDF_float_interpolated, computeSingleNormalFromSDF, readFromSDF_color4u_interpolated at caller-supplied points, castRay along
 // caller-supplied segments.  All pointers are DEVICE memory; one launch on `stream`, nothing is synchronised.
@@ -916,6 +978,12 @@ class ITMMainEngine_HIP {
   // x_other, metres).  The scene of `other` is resampled at this scene's voxels and fused (itm_scene_resample).
   void MergeSceneFrom(const ITMMainEngine_HIP& other, const Matrix4f& thisFromOther, itm_resample_stats* stats = nullptr) {
     ITMSceneResampleEngine_HIP<TVoxel, TIndex>().ResampleScene(&scene, &other.scene, thisFromOther, nullptr, stats);
+  }
+  // Refines thisFromOther (the coarse pose on entry, the refined one on return) by registering the band voxels of `other`'s scene
+  // against this engine's scene (ITMSceneAlignEngine_HIP); its natural use is followed by MergeSceneFrom(other, thisFromOther).  Neither
+  // scene is written.  res->status: ITM_ALIGN_DEGENERATE when the geometry does not determine the pose -- the caller decides.
+  void AlignSceneFrom(const ITMMainEngine_HIP& other, Matrix4f& thisFromOther, itm_align_result* res = nullptr) {
+    ITMSceneAlignEngine_HIP<TVoxel, TIndex>().AlignScene(&scene, &other.scene, thisFromOther, res);
   }
   // Resamples this engine's scene into `coarse`, a scene of twice the voxel size and the same mu (itm_scene_coarsen).  This engine's
   // scene, tracking state and render states stay as they are.

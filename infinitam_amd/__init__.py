@@ -10,8 +10,8 @@ import os
 import subprocess
 
 from . import capi, synth  # noqa: F401
-from .capi import (Backend, DevBuffer, ItmError, PoseQuality, PoseQualityConfig, PoseQualityStats,  # noqa: F401
-                   Relocaliser, RenderState, Scene, View, default_params)
+from .capi import (AlignConfig, AlignResult, Backend, DevBuffer, ItmError, PoseQuality, PoseQualityConfig,  # noqa: F401
+                   PoseQualityStats, Relocaliser, RenderState, Scene, SceneAligner, View, default_params)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libitmhip.so"

@@ -326,12 +326,58 @@ class PoseQualityStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class AlignConfig(C.Structure):
+    """itm_align_config (include/itm_hip.h, scene alignment): the band samples' selection and the aligner's loop.  32 bytes."""
+    _fields_ = [("minWeight", C.c_int32), ("maxAbsSdf", C.c_float), ("stride", C.c_int32), ("huberDelta", C.c_float), ("minStep", C.c_float),
+                ("maxEvaluations", C.c_int32), ("minValid", C.c_int32), ("minConditioning", C.c_float)]
+
+    def replace(self, **kw) -> "AlignConfig":
+        c = AlignConfig.from_buffer_copy(self)
+        for k, v in kw.items():
+            setattr(c, k, v)
+        return c
+
+
+class AlignEval(C.Structure):
+    """itm_align_eval: cost, valid count, gradient and Hessian (hessian[r + c * 6]) of one evaluation.  176 bytes."""
+    _fields_ = [("f", C.c_float), ("noValid", C.c_int32), ("nabla", C.c_float * 6), ("hessian", C.c_float * 36)]
+
+
+class AlignResult(C.Structure):
+    """itm_align_result.  40 bytes."""
+    _fields_ = [("status", C.c_int32), ("evaluations", C.c_int32), ("noValid", C.c_int32), ("reserved", C.c_int32),
+                ("initialCost", C.c_double), ("finalCost", C.c_double), ("conditioning", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+
+
+ALIGN_CONVERGED, ALIGN_MAX_EVALUATIONS, ALIGN_STALLED, ALIGN_TOO_FEW_SAMPLES, ALIGN_DEGENERATE = range(5)
+ALIGN_STATUS_NAMES = ("converged", "max_evaluations", "stalled", "too_few_samples", "degenerate")
+
+
+def align_default_config(voxelSize, mu, be=None) -> AlignConfig:
+    """itm_align_default_config (host only)."""
+    if be is None:
+        from . import load
+        be = load()
+    cfg = AlignConfig()
+    be.check(be.fn["align_default_config"](float(voxelSize), float(mu), C.byref(cfg)), "align_default_config")
+    return cfg
+
+
+def _matrix16(M):
+    """the 16 floats, column-major, of a 4 x 4 matrix (x_out = M x_in) or of 16 floats that are column-major already"""
+    arr = np.asarray(M, np.float32)
+    return np.ascontiguousarray(arr.T if arr.ndim == 2 else arr).reshape(16)
+
+
 TRACKING_FAILED, TRACKING_POOR, TRACKING_GOOD = 0, 1, 2
 POSE_QUALITY_UNKNOWN, POSE_QUALITY_NONE = np.float32(1e30), np.float32(-1e30)
 DEBUG_POSE_QUALITY_ROWS = 29
 # itm_debug_counter (include/itm_debug.h): the forward-only 32-bit counters behind the tagged granules
 (COUNTER_LIST_EPOCH, COUNTER_FRAME_PARITY, COUNTER_TABLE_EPOCH, COUNTER_TRACKER_SEQ, COUNTER_TRACKER_SESSION, COUNTER_TRACKER_FALLBACKS,
- COUNTER_TRACKER_RELAUNCHES, COUNTER_COLOUR_SEQ, COUNTER_REN_SEQ, COUNTER_POSE_QUALITY_SEQ, COUNTER_IMAGE_MAP_EPOCH) = range(1, 12)
+ COUNTER_TRACKER_RELAUNCHES, COUNTER_COLOUR_SEQ, COUNTER_REN_SEQ, COUNTER_POSE_QUALITY_SEQ, COUNTER_IMAGE_MAP_EPOCH, COUNTER_ALIGN_SEQ) = range(1, 13)
 
 
 class ItmError(RuntimeError):
@@ -543,6 +589,16 @@ _HOST_IO_SIGS = {
     "pose_quality_create": (C.c_int, [C.POINTER(_P)]),
     "pose_quality_destroy": (C.c_int, [_P]),
     "pose_quality_evaluate": (C.c_int, [_P, _P, C.POINTER(ViewStruct), C.POINTER(PoseQualityConfig), C.POINTER(PoseQualityStats), _P, _P]),
+    # scene alignment (product only); default_config, step and apply_step are host-only
+    "align_default_config": (C.c_int, [C.c_float, C.c_float, C.POINTER(AlignConfig)]),
+    "align_step": (C.c_int, [C.POINTER(AlignEval), C.c_double, C.POINTER(C.c_float)]),
+    "align_apply_step": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "scene_band_samples": (C.c_int, [_P, _P, C.c_int, C.POINTER(AlignConfig), _P, C.c_int32, C.POINTER(C.c_int32), _P]),
+    "aligner_create": (C.c_int, [C.POINTER(_P)]),
+    "aligner_destroy": (C.c_int, [_P]),
+    "aligner_set_samples": (C.c_int, [_P, _P, C.c_int32, _P]),
+    "aligner_evaluate": (C.c_int, [_P, _P, C.POINTER(C.c_float), C.POINTER(AlignConfig), C.POINTER(AlignEval), _P]),
+    "aligner_align": (C.c_int, [_P, _P, C.POINTER(C.c_float), C.POINTER(AlignConfig), C.POINTER(C.c_float), C.POINTER(AlignResult), _P]),
 }
 
 
@@ -864,6 +920,47 @@ class Scene:
         self.be.check(rc, "scene_resample")
         return stats.as_dict()
 
+    def align_config(self, **kw) -> AlignConfig:
+        """itm_align_default_config for this scene's voxelSize and mu, with the fields given in kw replaced."""
+        return align_default_config(float(self.params.voxelSize), float(self.params.mu), self.be).replace(**kw)
+
+    def band_samples(self, cfg: Optional[AlignConfig] = None, slots=None, capacity=None, stream=None):
+        """itm_scene_band_samples: (DevBuffer of float32 [min(count, capacity), 4] = (x, y, z in metres, sdf * mu), count).  cfg None:
+        the defaults; slots: as merge_from; capacity None: asks for the count first and sizes the buffer from it."""
+        cfg = cfg if cfg is not None else self.align_config()
+        ptr, n, keep = self._slot_list(slots, stream)
+        count = C.c_int32(0)
+        try:
+            if capacity is None:
+                self.be.check(self.be.fn["scene_band_samples"](_P(self.h), _P(ptr), n, C.byref(cfg), None, 0, C.byref(count), _P(stream)), "scene_band_samples")
+                capacity = count.value
+            capacity = int(capacity)
+            buf = DevBuffer(self.be, capacity * 16, np.float32, (capacity, 4))
+            if capacity > 0:
+                rc = self.be.fn["scene_band_samples"](_P(self.h), _P(ptr), n, C.byref(cfg), _P(buf.ptr), capacity, C.byref(count), _P(stream))
+                if rc != 0:
+                    buf.close()
+                self.be.check(rc, "scene_band_samples")
+        finally:
+            if keep is not None:
+                keep.close()
+        held = min(capacity, count.value)
+        buf.nbytes, buf.shape = held * 16, (held, 4)
+        return buf, count.value
+
+    def align_from(self, src: "Scene", init, cfg: Optional[AlignConfig] = None, slots=None, stream=None):
+        """The pose dstFromSrc (4 x 4, x_self = M x_src, metres) that registers the band samples of `src` to this scene, refined from
+        `init`: (matrix float32 [4, 4], AlignResult).  cfg None: the defaults; slots: the part of src to sample, as merge_from."""
+        cfg = cfg if cfg is not None else self.align_config()
+        samples, count = src.band_samples(cfg, slots, stream=stream)
+        aligner = SceneAligner(self.be)
+        try:
+            aligner.set_samples(samples, count)
+            return aligner.align(self, init, cfg, stream)
+        finally:
+            aligner.close()
+            samples.close()
+
     def query_points(self, points, units="metres", want=("sdf", "gradient"), stream=None) -> dict:
         """itm_scene_query_points: the outputs named in `want` (QUERY_OUTPUTS) at float32 points [n, 3] in "metres" or "voxels", as a
         dict of numpy arrays.  Uploads the points, downloads the outputs and synchronises `stream`."""
@@ -1152,6 +1249,58 @@ class PoseQuality:
         if self.h:
             self.be.fn["pose_quality_destroy"](_P(self.h))
             self.h = 0
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SceneAligner:
+    """itm_aligner: sdf samples (float4: a point in metres in the source frame and the signed distance in metres it should read)
+    registered against a TSDF scene (include/itm_hip.h).  One handle per host thread.  The samples stay the caller's: set_samples keeps
+    the buffer alive but does not copy it."""
+
+    def __init__(self, be: Backend):
+        self.be, self.h, self.samples = be, 0, None
+        p = _P()
+        be.check(be.fn["aligner_create"](C.byref(p)), "aligner_create")
+        self.h = p.value
+
+    def set_samples(self, samples, n=None, stream=None):
+        """samples: a DevBuffer of float32 [n, 4] (Scene.band_samples), or a numpy array of them (uploaded)."""
+        if not isinstance(samples, DevBuffer):
+            arr = np.ascontiguousarray(np.asarray(samples, np.float32).reshape(-1, 4))
+            samples = self.be.to_backend(arr, stream) if len(arr) else DevBuffer(self.be, 0, np.float32, (0, 4))
+        n = samples.nbytes // 16 if n is None else int(n)
+        self.be.check(self.be.fn["aligner_set_samples"](_P(self.h), _P(samples.ptr if n else None), n, _P(stream)), "aligner_set_samples")
+        self.samples = samples
+
+    def evaluate(self, dst: "Scene", M, cfg: Optional[AlignConfig] = None, stream=None) -> AlignEval:
+        """itm_aligner_evaluate at dstFromSrc = M (4 x 4, or its 16 floats column-major)."""
+        cfg = cfg if cfg is not None else dst.align_config()
+        flat = _matrix16(M)
+        out = AlignEval()
+        self.be.check(self.be.fn["aligner_evaluate"](_P(self.h), _P(dst.h), flat.ctypes.data_as(C.POINTER(C.c_float)), C.byref(cfg), C.byref(out), _P(stream)),
+                      "aligner_evaluate")
+        return out
+
+    def align(self, dst: "Scene", init, cfg: Optional[AlignConfig] = None, stream=None):
+        """itm_aligner_align from dstFromSrc = init: (matrix float32 [4, 4], AlignResult)."""
+        cfg = cfg if cfg is not None else dst.align_config()
+        flat = _matrix16(init)
+        out = np.zeros(16, np.float32)
+        res = AlignResult()
+        self.be.check(self.be.fn["aligner_align"](_P(self.h), _P(dst.h), flat.ctypes.data_as(C.POINTER(C.c_float)), C.byref(cfg),
+                                                  out.ctypes.data_as(C.POINTER(C.c_float)), C.byref(res), _P(stream)), "aligner_align")
+        return np.ascontiguousarray(out.reshape(4, 4).T), res
+
+    def close(self):
+        if self.h:
+            self.be.fn["aligner_destroy"](_P(self.h))
+            self.h = 0
+        self.samples = None
 
     def __del__(self):
         try:

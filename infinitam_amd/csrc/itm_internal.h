@@ -251,6 +251,7 @@ int debug_counter_colour_tracker(int which, void* handle, const uint32_t* set, u
 int debug_counter_ren_tracker(int which, void* handle, const uint32_t* set, uint32_t* get);      // ren_tracker.hip
 int debug_counter_pose_quality(int which, void* handle, const uint32_t* set, uint32_t* get);     // pose_quality.hip
 int debug_counter_image_maps(int which, void* handle, const uint32_t* set, uint32_t* get);       // image_maps.hip
+int debug_counter_aligner(int which, void* handle, const uint32_t* set, uint32_t* get);          // align.hip
 int rebuild_sdf_mirror(itm_scene* s, hipStream_t st);
 // Foreign voxel bytes on their way into a HASH scene (buffer upload, checkpoint load, the checkpoint's cached blocks): ITM_ERR_INVALID, naming
 // the voxel, when one of the n voxels holds the sdf word that the sdf mirror keeps for "no block here" (MirrorCodec::kAbsent,

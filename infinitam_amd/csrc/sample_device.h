@@ -34,6 +34,23 @@ __device__ inline float gradient_axis(S&& raw, float fa, float fu, float fv) {
   return VX::to_float(plane[2] * ga + plane[3] * fa - lower);
 }
 
+// The derivative of the trilinear interpolant itself (Corners::trilinear, volume_device.h) from the same eight raw corner values
+// v[dx + 2 dy + 4 dz] and fractions (cx, cy, cz), per voxel: what a solver that minimises the interpolated sdf differentiates (the
+// 32-tap gradient above is the reference's shading normal: a different function, and it reads defaults beside the band).  Along an axis
+// the four differences of the cell's edges parallel to it are blended bilinearly with the other two fractions, the first of them
+// innermost; every product and sum is rounded on its own:
+//   g[0] = (1-cz) ((1-cy) (v1-v0) + cy (v3-v2)) + cz ((1-cy) (v5-v4) + cy (v7-v6))
+//   g[1] = (1-cz) ((1-cx) (v2-v0) + cx (v3-v1)) + cz ((1-cx) (v6-v4) + cx (v7-v5))
+//   g[2] = (1-cy) ((1-cx) (v4-v0) + cx (v5-v1)) + cy ((1-cx) (v6-v2) + cx (v7-v3))
+// each blended on raw values and then converted, as the value is.
+template <class VX>
+__device__ inline void trilinear_gradient(const float v[8], float cx, float cy, float cz, float g[3]) {
+  const float gx = 1.0f - cx, gy = 1.0f - cy, gz = 1.0f - cz;
+  g[0] = VX::to_float(gz * (gy * (v[1] - v[0]) + cy * (v[3] - v[2])) + cz * (gy * (v[5] - v[4]) + cy * (v[7] - v[6])));
+  g[1] = VX::to_float(gz * (gx * (v[2] - v[0]) + cx * (v[3] - v[1])) + cz * (gx * (v[6] - v[4]) + cx * (v[7] - v[5])));
+  g[2] = VX::to_float(gy * (gx * (v[4] - v[0]) + cx * (v[5] - v[1])) + cy * (gx * (v[6] - v[2]) + cx * (v[7] - v[3])));
+}
+
 // The colour at a fractional position (cx, cy, cz: its fractions) over any source of packed colours: `packed(dx, dy, dz)` is the voxel at
 // floor(p) + (dx, dy, dz) as r | g << 8 | b << 16, 0 where no voxel is stored.  Returns (r, g, b) / 255 and w = 1.
 template <class C>

@@ -684,6 +684,7 @@ int itm_debug_counter(int which, void* handle, const uint32_t* set, uint32_t* ge
   if (rc == -1) rc = debug_counter_ren_tracker(which, handle, set, get);
   if (rc == -1) rc = debug_counter_pose_quality(which, handle, set, get);
   if (rc == -1) rc = debug_counter_image_maps(which, handle, set, get);
+  if (rc == -1) rc = debug_counter_aligner(which, handle, set, get);
   return rc == -1 ? set_error(ITM_ERR_INVALID, "unknown counter") : rc;
 }
 
