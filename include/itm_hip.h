@@ -993,6 +993,70 @@ typedef struct itm_resample_stats {
 } itm_resample_stats;
 int ITM_FN(scene_resample)(itm_scene* dst, const itm_scene* src, const itm_rigid_q* q, const int32_t* srcSlots_dev, int n, itm_resample_stats* stats, itm_stream stream);
 
+/* ---- scene pruning: returns the voxel blocks of a hash scene that carry no information to the pool --------------------------------------
+ * Not a reference operation: a reference scene only gains blocks (AllocateSceneFromDepth allocates every block the band depth +- mu
+ * touches; nothing but host swapping gives one back, and that keeps the entry).  A block without an observed voxel, or whose observed
+ * voxels all sit at "free", reads exactly as an absent one does (readVoxel of a missing block: sdf 1, w 0), so removing it changes no
+ * read while it frees a block of the pool, a table slot, its directory cells and its mirror values.
+ * Refusals, each ITM_ERR_INVALID with the reason in itm_last_error and the scene untouched: a NULL scene or config; a dense scene; a scene
+ * created with useSwapping (its host cache and swap states are keyed by table slot, and swapping is that scene's own way of getting
+ * blocks back); a scene that holds the block requests of a frame issued ahead (itm_cancel_ahead first); classes == 0 or with a bit
+ * outside the four; a freeSdf that is not finite or lies outside [-1, 1]; weakMaxW < 1 with ITM_PRUNE_WEAK selected; a box with
+ * min > max in a component when it is used (ITM_PRUNE_BOX selected, or boxOnly).  Recorded calls of the scene are launched first.
+ *
+ * Sequential definition (the kernels reproduce it bit for bit; tests/scene_prune_terms.py transcribes it):
+ *  1. Classes.  For every entry that holds a voxel block of the pool (ptr >= 0), in ascending slot order, over its 512 voxels: a voxel
+ *     is OBSERVED if w_depth > 0 (colour weights play no part).  EMPTY: no observed voxel.  SURFACE: an observed voxel BELOW the
+ *     threshold -- short voxels: stored word < (short)(freeSdf * 32767.0f), the threshold computed once; float voxels: not
+ *     (sdf >= freeSdf).  FREE: an observed voxel and not SURFACE.  WEAK: an observed voxel and the largest w_depth <= weakMaxW.  INBOX
+ *     (only when the box is used): boxMin <= pos <= boxMax in every component, block coordinates.  `considered` counts these entries;
+ *     entries with ptr == -1 (or a pointer outside the pool, which only an uploaded table can hold) count in withoutBlock, take part
+ *     in nothing and are left as they are; empty slots have the decision byte 0.
+ *  2. Candidates.  An entry is a FIRST candidate if it shows a selected class among EMPTY, FREE, WEAK (with boxOnly: and is INBOX);
+ *     with ITM_PRUNE_BOX selected every INBOX entry is a first candidate and FORCED, whatever it holds -- this is how a region is
+ *     erased.  With `protect`, a first candidate that is not forced STAYS if one of its 26 neighbours (found by walking from
+ *     hashIndex(pos) along the offset chain, as step 2 of itm_scene_merge does) holds a block, is SURFACE and is not a first candidate
+ *     itself: it counts in protectedByNeighbour.  The trilinear reads and the marching-cubes cells at the surface (meshing skips a cell
+ *     whose corner block is missing) are then unchanged.  The others are the CANDIDATES.
+ *  3. Buckets, ascending; the head, then its chain in chain order.  A candidate excess entry is DROPPED and its predecessor's offset
+ *     becomes its offset.  A candidate head is DROPPED only if no entry of its chain stays (entries with ptr == -1 included);
+ *     otherwise it is PINNED (pinnedHeads) and keeps its block and voxels: the allocation takes an ordered slot with ptr < -1 without
+ *     looking at its offset and would cut the chain off, and moving a chain entry into the head would change table slots that other
+ *     structures hold.  candidates = dropped + pinnedHeads.
+ *  4. Release, the dropped entries in ascending slot order.  A counter below -1 counts as -1 (as in SaveToGlobalMemory above).
+ *     allocList[++lastFreeBlockId] = ptr; for an excess entry also excessList[++lastFreeExcessListId] = slot - bucketNum; a write past
+ *     either list (only an uploaded, inconsistent counter can ask for one) is left out and the counter stops at the list's last index.
+ *     The 512 voxels of every dropped block take the initial value (blocks on the allocation list are handed out unreset) and the
+ *     entry becomes the one ResetScene writes.
+ *  5. The occupancy bits, both directories and the sdf mirror read as itm_upload of the same table and voxels would leave them (in the
+ *     paged form a page whose blocks have all gone stays mapped with every cell "absent" until the cubes are next emptied, as after a
+ *     swap-out).  The request keys stay zero.  In EVERY render state of the scene: entriesVisibleType of a dropped slot becomes 0, the
+ *     dropped slots leave visibleEntryIDs with the order of the rest kept, noVisibleEntries is lowered; visibleRemoved counts the list
+ *     entries removed over all render states.  No later call finds a listed slot without a block.
+ *  6. dryRun: steps 1 - 3 only.  The decision bytes and the statistics are those of the real run (the two counters as they would
+ *     become); nothing in the scene or in a render state changes.
+ * decisions_dev (DEVICE, uchar[noTotalEntries], may be NULL) receives per entry the ITM_PRUNE_IS_* bits.  `stats` (host, may be NULL):
+ * with it the call synchronises `stream` once, at its end; without it everything is enqueued. */
+enum { ITM_PRUNE_EMPTY = 1, ITM_PRUNE_FREE = 2, ITM_PRUNE_WEAK = 4, ITM_PRUNE_BOX = 8 };
+enum { ITM_PRUNE_IS_EMPTY = 1, ITM_PRUNE_IS_FREE = 2, ITM_PRUNE_IS_WEAK = 4, ITM_PRUNE_IS_SURFACE = 8, ITM_PRUNE_IS_INBOX = 16,
+       ITM_PRUNE_IS_CANDIDATE = 64, ITM_PRUNE_IS_DROPPED = 128 };
+typedef struct itm_prune_config {
+  int32_t classes;              /* OR of ITM_PRUNE_*: which kinds of block are candidates (default EMPTY | FREE) */
+  float freeSdf;                /* FREE: every observed voxel has sdf >= freeSdf (default 1.0) */
+  int32_t weakMaxW;             /* WEAK: the block's largest w_depth is in 1 .. weakMaxW (default 1) */
+  int32_t protect;              /* 1: a candidate with a surface-bearing 26-neighbour stays (default 1) */
+  int32_t boxMin[3], boxMax[3]; /* block coordinates, inclusive */
+  int32_t boxOnly;              /* 1: EMPTY / FREE / WEAK apply inside the box only */
+  int32_t dryRun;               /* 1: decide and count, change nothing */
+} itm_prune_config;             /* 48 bytes */
+typedef struct itm_prune_stats {
+  int32_t considered, empty, free_, weak, inBox, candidates, protectedByNeighbour, pinnedHeads, dropped, droppedHeads, droppedExcess,
+          withoutBlock, visibleRemoved, lastFreeBlockId, lastFreeExcessListId;
+  int32_t reserved;
+} itm_prune_stats;              /* 64 bytes */
+int ITM_FN(prune_default_config)(itm_prune_config* out);
+int ITM_FN(scene_prune)(itm_scene* scene, const itm_prune_config* cfg, uint8_t* decisions_dev, itm_prune_stats* stats, itm_stream stream);
+
 /* ---- scene queries: the volume asked at caller-supplied points and along caller-supplied rays -------------------------------------
  * The reference makes these reads only from inside its engines, per pixel; here the work item is the caller's.  Both calls launch the
  * scene's recorded calls first, read the scene only, take DEVICE pointers and enqueue one launch on `stream` (no synchronisation).

@@ -159,6 +159,10 @@ struct ITMLibSettings {
   // chosen on a synthetic scene and not tuned on sensor data (include/itm_hip.h).
   itm_pose_quality_config poseQuality = {0.0f, 0, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
   int relocFusionDelay = 10;                  // GOOD frames that are tracked but not fused after a recovery
+  // Scene pruning (itm_scene_prune; the reference has none).  0 (default): never, and no code path changes.  N > 0: ITMMainEngine_HIP
+  // prunes its scene with pruneConfig after every N-th frame it has fused, once that frame's maps are prepared.
+  int pruneEveryNFrames = 0;
+  itm_prune_config pruneConfig = {ITM_PRUNE_EMPTY | ITM_PRUNE_FREE, 1.0f, 1, 1, {0, 0, 0}, {0, 0, 0}, 0, 0};      // itm_prune_default_config
 };
 
 struct ITMSceneParams : itm_scene_params {
@@ -317,6 +321,20 @@ class ITMSceneMergeEngine_HIP {
       if (!slots) throw std::runtime_error("MergeScene: the render state has no visible list");
     }
     check(itm_scene_merge(dst->handle, src->handle, slots, n, stats, stream), "MergeScene");
+  }
+};
+
+// Scene pruning (itm_scene_prune; no reference class): the blocks of `scene` that `cfg` selects (nullptr: the defaults -- blocks without
+// an observed voxel and blocks whose observed voxels all read "free") go back to the pool, their entries leave the table and every
+// render state of the scene loses them from its visible list.  Hash scenes without swapping.
+template <class TVoxel, class TIndex>
+class ITMScenePruneEngine_HIP {
+ public:
+  itm_stream stream = nullptr;
+  void PruneScene(ITMScene<TVoxel, TIndex>* scene, const itm_prune_config* cfg = nullptr, itm_prune_stats* stats = nullptr) {
+    itm_prune_config def;
+    if (!cfg) { check(itm_prune_default_config(&def), "PruneScene (default config)"); cfg = &def; }
+    check(itm_scene_prune(scene->handle, cfg, nullptr, stats, stream), "PruneScene");
   }
 };
 
@@ -900,6 +918,8 @@ class ITMMainEngine_HIP {
   ITMPose endPose;                 // pose_d as the previous frame left it
   bool haveEndPose = false, anyFrameFused = false, lastFrameFused = false;
   int fusionDelay = 0, relocalisationCount = 0;
+  int fusedSincePrune = 0;         // settings.pruneEveryNFrames
+  itm_prune_stats lastPrune = {};
 
  public:
   // calibType / c0 / c1: ITMDisparityCalib (0 = TRAFO_KINECT, 1 = TRAFO_AFFINE); sizes as ITMMainEngine's imgSize_rgb / imgSize_d
@@ -974,6 +994,13 @@ class ITMMainEngine_HIP {
   void MergeSceneFrom(const ITMMainEngine_HIP& other, itm_merge_stats* stats = nullptr) {
     ITMSceneMergeEngine_HIP<TVoxel, TIndex>().MergeScene(&scene, &other.scene, nullptr, stats);
   }
+  // Returns the blocks of this engine's scene that `cfg` selects (nullptr: settings.pruneConfig) to the pool (itm_scene_prune).  The
+  // live render state's visible list loses them; tracking state and maps stay as they are.
+  void PruneScene(const itm_prune_config* cfg = nullptr, itm_prune_stats* stats = nullptr) {
+    ITMScenePruneEngine_HIP<TVoxel, TIndex>().PruneScene(&scene, cfg ? cfg : &settings.pruneConfig, &lastPrune);
+    if (stats) *stats = lastPrune;
+  }
+  const itm_prune_stats& GetLastPruneStats() const { return lastPrune; }      // of the last PruneScene, by the host or by pruneEveryNFrames
   // The same for an `other` that lives in a frame of its own: thisFromOther maps its world to this engine's (x_this = thisFromOther
   // x_other, metres).  The scene of `other` is resampled at this scene's voxels and fused (itm_scene_resample).
   void MergeSceneFrom(const ITMMainEngine_HIP& other, const Matrix4f& thisFromOther, itm_resample_stats* stats = nullptr) {
@@ -1043,6 +1070,14 @@ class ITMMainEngine_HIP {
       int nearest; float distance;
       relocaliser->ProcessFrame(view.depth, &trackingState.pose_d, 1, &nearest, &distance, true);
     }
+    if (fusionActive) PruneIfDue();
+  }
+
+  // settings.pruneEveryNFrames: after the frame's maps are prepared, so that the recorded frame is launched as one fused frame as ever
+  void PruneIfDue() {
+    if (settings.pruneEveryNFrames <= 0 || ++fusedSincePrune < settings.pruneEveryNFrames) return;
+    fusedSincePrune = 0;
+    PruneScene();
   }
 
  public:
@@ -1125,6 +1160,7 @@ class ITMMainEngine_HIP {
         relocaliser->ProcessFrame(view.depth, &trackingState.pose_d, 1, &nearest, &distance, true);
       }
       if (delayed) --fusionDelay;
+      if (lastFrameFused) PruneIfDue();
     } else if (result == Q::TRACKING_POOR) {
       trackingController->Prepare(&trackingState, &view, renderState_live);
     } else {

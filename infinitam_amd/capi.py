@@ -207,6 +207,41 @@ class MergeStats(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+# itm_prune_config::classes and the bits of a decision byte (include/itm_hip.h, itm_scene_prune)
+PRUNE_EMPTY, PRUNE_FREE, PRUNE_WEAK, PRUNE_BOX = 1, 2, 4, 8
+PRUNE_IS_EMPTY, PRUNE_IS_FREE, PRUNE_IS_WEAK, PRUNE_IS_SURFACE, PRUNE_IS_INBOX, PRUNE_IS_CANDIDATE, PRUNE_IS_DROPPED = 1, 2, 4, 8, 16, 64, 128
+
+
+class PruneConfig(C.Structure):
+    """itm_prune_config (include/itm_hip.h, itm_scene_prune): 48 bytes."""
+    _fields_ = [("classes", C.c_int32), ("freeSdf", C.c_float), ("weakMaxW", C.c_int32), ("protect", C.c_int32),
+                ("boxMin", C.c_int32 * 3), ("boxMax", C.c_int32 * 3), ("boxOnly", C.c_int32), ("dryRun", C.c_int32)]
+
+    def replace(self, **kw) -> "PruneConfig":
+        out = PruneConfig.from_buffer_copy(self)
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise ItmError(f"PruneConfig has no field {k}")
+            if k in ("boxMin", "boxMax"):
+                getattr(out, k)[:] = [int(c) for c in v]
+            else:
+                setattr(out, k, v)
+        return out
+
+    def as_dict(self):
+        return {n: (list(getattr(self, n)) if n in ("boxMin", "boxMax") else getattr(self, n)) for n, _ in self._fields_}
+
+
+class PruneStats(C.Structure):
+    """itm_prune_stats (include/itm_hip.h, itm_scene_prune): 64 bytes."""
+    _fields_ = [(n, C.c_int32) for n in ("considered", "empty", "free_", "weak", "inBox", "candidates", "protectedByNeighbour", "pinnedHeads",
+                                         "dropped", "droppedHeads", "droppedExcess", "withoutBlock", "visibleRemoved", "lastFreeBlockId",
+                                         "lastFreeExcessListId", "reserved")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
 class CoarsenStats(C.Structure):
     """itm_coarsen_stats (include/itm_hip.h, itm_scene_coarsen)."""
     _fields_ = [(n, C.c_int32) for n in ("rounds", "considered", "alreadyPresent", "allocated", "written", "unserved",
@@ -556,6 +591,8 @@ _HOST_IO_SIGS = {
     "normal_to_uchar4": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     # scene merge (product only: no reference engine merges scenes)
     "scene_merge": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(MergeStats), _P]),
+    "prune_default_config": (C.c_int, [C.POINTER(PruneConfig)]),
+    "scene_prune": (C.c_int, [_P, C.POINTER(PruneConfig), _P, C.POINTER(PruneStats), _P]),
     # level of detail (product only: the reference has one resolution per scene)
     "scene_coarsen": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(CoarsenStats), _P]),
     # scene merge under a rigid transform (product only)
@@ -901,6 +938,29 @@ class Scene:
         """itm_scene_merge: fuses `src` into this scene on the GPU and returns the statistics.  slots: None (every slot of src's
         table), a DevBuffer of int32 table slots of src, or a numpy array of them (uploaded first)."""
         return self._slot_call("scene_merge", MergeStats(), src, slots, stream)
+
+    def prune_config(self, **kw) -> PruneConfig:
+        """itm_prune_default_config with the fields given in kw replaced."""
+        cfg = PruneConfig()
+        self.be.check(self.be.fn["prune_default_config"](C.byref(cfg)), "prune_default_config")
+        return cfg.replace(**kw)
+
+    def prune(self, cfg: Optional[PruneConfig] = None, decisions=False, stream=None) -> dict:
+        """itm_scene_prune: returns the blocks `cfg` selects (None: the defaults, empty and free-space blocks) to the pool and gives
+        the statistics; with `decisions` the dict also holds "decisions", the PRUNE_IS_* byte of every table entry.  Synchronises
+        `stream`."""
+        cfg = cfg if cfg is not None else self.prune_config()
+        stats = PruneStats()
+        n = self.be.fn["buffer_bytes"](_P(self.h), None, BUF_HASH_ENTRIES) // HASH_ENTRY_DTYPE.itemsize
+        dev = DevBuffer(self.be, n, np.uint8, (n,)) if decisions else None
+        rc = self.be.fn["scene_prune"](_P(self.h), C.byref(cfg), _P(dev.ptr if dev else None), C.byref(stats), _P(stream))
+        out = stats.as_dict()
+        if dev is not None:
+            if rc == 0:
+                out["decisions"] = dev.numpy(stream)
+            dev.close()
+        self.be.check(rc, "scene_prune")
+        return out
 
     def coarsen_from(self, src: "Scene", slots=None, stream=None) -> dict:
         """itm_scene_coarsen: resamples `src` into this scene, which has twice src's voxel size, on the GPU and returns the statistics.

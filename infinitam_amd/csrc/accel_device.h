@@ -247,6 +247,8 @@ struct AccelWriter {
   }
   // the entry of block (bx, by, bz) has lost its voxel block (the mirror values: store_absent; the occupancy bit stays, the entry does)
   __device__ void block_released(int bx, int by, int bz) const { directory_cells(-1, bx, by, bz, -1); }
+  // ordered entry `slot` has left the table (ptr < -1 again; the pruning, which drops a head only with its whole chain)
+  __device__ void head_released(int slot) const { atomicAnd(&headBits[slot >> 5], ~(1u << (slot & 31))); }
   // the two directory cells of block (bx, by, bz) alone (the passes that fill the cubes from the table write bits, cells and values apart)
   __device__ void directory_cells(int slot, int bx, int by, int bz, int ptr) const { directory_insert(dirPtr, dirSlot, org, bx, by, bz, ptr, slot); }
   // one word of the occupancy bitmap, from the table or cleared

@@ -120,6 +120,8 @@ struct itm_scene {
   itm::PinnedBuffer<volatile int32_t> fatalHost;   // mapped; device(): the same word as the device sees it
   // itm_scene_merge with this scene as destination (merge.hip): per-call scratch, kept between calls
   itm::DeviceBuffer<void> mergeScratch;
+  // itm_scene_prune (prune.hip): per-call scratch, kept between calls
+  itm::DeviceBuffer<void> pruneScratch;
 };
 
 struct itm_render_state {
@@ -265,6 +267,7 @@ int create_swap_state(itm_scene* s);
 void swap_cache_export(const itm_scene* s, std::vector<uint8_t>& flags, std::vector<char>& blocks);
 void swap_cache_replace(itm_scene* s, const uint8_t* flags, const char* blocks);      // wholesale; inputs as swap_cache_export gives them
 int live_hash_scenes(int device);                                     // hash scenes alive on a device (scene.hip)
+std::vector<itm_render_state*> render_states_of(const itm_scene* s);  // the render states registered with a scene, copied under the registry's lock (scene.hip)
 int accel_unfill(itm_scene* s, hipStream_t st);                      // empties the cubes through the table that filled them
 int accel_place(itm_scene* s, const float* invM, hipStream_t st);    // (re-)places the cubes around a view
 extern int g_debug_no_fused_projection;

@@ -450,6 +450,11 @@ static void free_rs(itm_render_state* r) {
   delete r;
 }
 
+std::vector<itm_render_state*> render_states_of(const itm_scene* s) {
+  std::lock_guard<std::mutex> lock(g_rsRegistryMutex);
+  return s->renderStates;
+}
+
 }  // namespace itm
 
 using namespace itm;
