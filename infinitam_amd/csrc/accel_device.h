@@ -48,6 +48,18 @@ __host__ __device__ inline uint32_t dir_cell(uint32_t ux, uint32_t uy, uint32_t 
   const uint32_t brick = ((uz >> 2) << (2 * (kDirBits - 2))) | ((uy >> 2) << (kDirBits - 2)) | (ux >> 2);
   return (brick << 6) | ((uz & 3u) << 4) | ((uy & 3u) << 2) | (ux & 3u);
 }
+// The same two answers from cube-relative VOXEL coordinates t = voxel - 8 * origin, taken modulo 2^32 (a reader that has a position
+// rather than a block: the ray cast's look-ahead).  With u = t >> 3 the block's cube-relative coordinate: u < kDirSide on every axis
+// exactly when t < 8 * kDirSide on every axis; u >> 2 is bits 5..11 of t and u & 3 bits 3..4, so the cell is six bit-field extracts
+// and their merge, without the shift to block units.  dir_cell_voxel is a valid cell for EVERY t (it is the cell of t taken modulo the
+// cube), so a reader may load first and ask dir_covers_voxel afterwards.  (ix >> 3) - d == (ix - 8 d) >> 3 for the arithmetic shift;
+// tests/cpp/dir_index_check.cpp compares both forms over every cube-relative triple and around the cube's faces.)
+__host__ __device__ inline bool dir_covers_voxel(uint32_t tx, uint32_t ty, uint32_t tz) { return ((tx | ty | tz) >> (kDirBits + 3)) == 0u; }
+__host__ __device__ inline uint32_t dir_cell_voxel(uint32_t tx, uint32_t ty, uint32_t tz) {
+  constexpr uint32_t m = (1u << (kDirBits - 2)) - 1u;
+  const uint32_t brick = (((tz >> 5) & m) << (2 * (kDirBits - 2))) | (((ty >> 5) & m) << (kDirBits - 2)) | ((tx >> 5) & m);
+  return (brick << 6) | (((tz >> 3) & 3u) << 4) | (((ty >> 3) & 3u) << 2) | ((tx >> 3) & 3u);
+}
 // records an allocated block (device side; called by the allocation sweep and the rebuild kernel)
 // (dirSlot: the same cells holding the TABLE SLOT of the block instead of its voxel-block index -- what the allocation request
 // needs to mark a block that already exists as visible, one coherent 4-byte load instead of the 16-byte entry of a random bucket)

@@ -23,9 +23,11 @@ constexpr int kMarchBurst = 2;
 constexpr int kParkStreak = 12;
 // directory cells fetched together per round trip by a parked ray's empty-space run (round 2: 4: 55 us, 6: 53, 8: 53; round 4 with a march
 // burst of 2, config 2 / config 5 ray cast: 6: 37.2-37.7 / 116-118, 8: 35.8-36.9 / 114.7-114.9, 12: 35.5-36.7 / 112.8-113.1, 16: 40.2-40.6 / 119.6,
-// 20: 41.8 / 130, 24: 40.4-42.1 / 131)
+// 20: 41.8 / 130, 24: 40.4-42.1 / 131).  Re-swept with the 30-instruction cell (profiles/raycast_lookahead_notes.md, headline frames/s,
+// 12: 13 636-13 733): 8: 13 627-13 764, 16: 13 568-13 601 (and 96-100 VGPRs)
 constexpr int kParkedLookahead = 12;
 // phase 1: "not found" steps in a row after which a ray counts as inside a run for the wave-wide look-ahead, and the cells it fetches
+// (re-swept likewise: 8 cells 13 376-13 468, 10: 13 636-13 733, 12: 13 629-13 749; a park streak of 10: 13 683-13 742)
 constexpr int kProbeAt = 2;
 constexpr int kProbeCells = 10;
 // Dense volumes: voxels fetched together by a ray that is crossing free space.  BASELINE configs[2] starts every ray 0.2 m in front
@@ -183,8 +185,8 @@ __device__ inline float4 march_ray(int x, int y, const VOL& vol, const RayParams
     return next;
   };
   // One look-ahead round of an empty-space run (hash index with the block directory): the directory cells of the positions q0 = pt,
-  // q1 = pt + 8 dir, ... -- computed with the reference's own additions -- are fetched together (cell 0 / no use for lanes that are not
-  // runners) and the ray advances over as many of them as are empty, each the reference's step for a position without a block, with
+  // q1 = pt + 8 dir, ... -- computed with the reference's own additions -- are fetched together (every lane loads, a lane that is no
+  // runner ignores what it gets) and the ray advances over as many of them as are empty, each the reference's step for a position without a block, with
   // its length update and range test; it stops in front of the first position that holds a block (or lies outside the directory),
   // which the regular loop then reads.  Returns the number of steps taken.
   auto miss_run = [&](auto kc, bool runner) -> int {
@@ -192,26 +194,42 @@ __device__ inline float4 march_ray(int x, int y, const VOL& vol, const RayParams
     const float sx = (float)kBlockSide * dx, sy = (float)kBlockSide * dy, sz = (float)kBlockSide * dz;   // exact products
     // (Round 5: with every cell folded into one mask -- all K loads awaited together, the count taken with a find-first-bit -- the hash
     // ray cast got SLOWER, configs[1] 36.5 -> 37.3 us, configs[4] 111.5 -> 119 us: the chain below consumes the cells as they arrive and
-    // leaves at the first block, and the compiler's habit of issuing the last cell's load only when all others were empty costs less
-    // than waiting for all of them every time.  profiles/r5_raycast_notes.md)
+    // leaves at the first block.  profiles/r5_raycast_notes.md)
+    // A cell is 30 straight-line instructions (40 and an exec bracket before: ray cast 36.4 -> 34.8 us, config 5's 112 -> 107.5 us,
+    // profiles/raycast_lookahead_notes.md; a parked wave has its SIMD to itself and pays every instruction and every exec bracket of
+    // a cell with issue time):
+    //  * the index comes from the voxel-unit coordinate t = voxel - 8 * origin (dir_cell_voxel: six bit-field extracts, no shift to
+    //    block units) and is a valid cell for EVERY t, so the load is unconditional -- no select of the index, which the compiler
+    //    turned into an exec-masked bracket around the index arithmetic of every cell;
+    //  * whether the directory covers the round is asked ONCE: a ray's positions are monotone per axis (additions of one sign, a monotone
+    //    rounding), so a round whose first and last cell lie inside the cube lies inside it entirely.  A round that touches the cube's
+    //    face takes no step at all; the regular loop reads those positions through the table, as it does everywhere outside the cube;
+    //  * the loads are pinned in front of the chain: without its bracket a load is free to sink into the chain, behind the test of the
+    //    cell before it, and the K round trips are dependent again (measured: 13 400 -> 12 900 frames/s).  The empty asm with its memory
+    //    clobber keeps every load above it; the scheduling fence per cell keeps the addresses from being computed all at once (110-120
+    //    VGPRs, four waves per SIMD); the asm on `edge` has the first cell's coordinates folded before the loop goes on.
+    static_assert(K >= 1 && K <= 32, "look-ahead cells");
     int ahead[K];
+    uint32_t edge = 0;      // the first and the last cell's cube-relative voxel coordinates, or-ed
     {
       float qx = px, qy = py, qz = pz;
+      const uint32_t ox8 = (uint32_t)vol.org.dx * (uint32_t)kBlockSide, oy8 = (uint32_t)vol.org.dy * (uint32_t)kBlockSide, oz8 = (uint32_t)vol.org.dz * (uint32_t)kBlockSide;
 #pragma unroll
       for (int j = 0; j < K; ++j) {
-        const uint32_t ux = (uint32_t)(((int)round_ref(qx) >> 3) - vol.org.dx), uy = (uint32_t)(((int)round_ref(qy) >> 3) - vol.org.dy),
-                       uz = (uint32_t)(((int)round_ref(qz) >> 3) - vol.org.dz);
-        const bool use = runner && dir_covers(ux, uy, uz);
-        const int v = vol.dirPtr[use ? dir_cell(ux, uy, uz) : 0u];
-        ahead[j] = use ? v : 0;                               // 0 = "cannot tell / a block": stops the run
+        const uint32_t tx = (uint32_t)(int)round_ref(qx) - ox8, ty = (uint32_t)(int)round_ref(qy) - oy8, tz = (uint32_t)(int)round_ref(qz) - oz8;
+        const uint32_t at = dir_cell_voxel(tx, ty, tz) << 2;                       // (a 32-bit byte offset from the scalar base)
+        if (j == 0 || j == K - 1) { edge |= tx | ty | tz; asm volatile("" : "+v"(edge)); }
+        ahead[j] = *(const int32_t*)((const char*)vol.dirPtr + at);
+        __builtin_amdgcn_sched_barrier(0);
         qx += sx; qy += sy; qz += sz;
       }
     }
+    asm volatile("" ::: "memory");
     int taken = 0;
-    if (runner) {
+    if (runner && dir_covers_voxel(edge, 0u, 0u)) {
 #pragma unroll
       for (int j = 0; j < K; ++j) {
-        if (ahead[j] >= 0) break;                             // q_j holds a block (or lies outside the directory): regular read next
+        if (ahead[j] >= 0) break;                             // q_j holds a block: regular read next
         px += sx; py += sy; pz += sz; total += (float)kBlockSide;   // the reference's step for a position without a block
         ++taken;
         if (!(total < totalMax)) { st = DONE; break; }
