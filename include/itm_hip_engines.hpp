@@ -302,6 +302,17 @@ class ITMSwappingEngine_HIP {
   }
 };
 
+// The slot list of a scene operation: the visible list of `srcVisible`, a render state of src (nullptr: no list, every block of src).
+template <class TVoxel, class TIndex>
+inline void visible_slots(const ITMScene<TVoxel, TIndex>* src, const ITMRenderState* srcVisible, itm_stream stream, const char* what, const int32_t** slots, int* n) {
+  if (!srcVisible) return;
+  itm_counters c;
+  check(itm_get_counters(src->handle, srcVisible->handle, &c, stream), (std::string(what) + " (visible list)").c_str());
+  *slots = (const int32_t*)itm_buffer_ptr(src->handle, srcVisible->handle, ITM_BUF_VISIBLE_IDS);
+  *n = c.noVisibleEntries;
+  if (!*slots) throw std::runtime_error(std::string(what) + ": the render state has no visible list");
+}
+
 // Scene merge (itm_scene_merge; no reference class): fuses `src` into `dst` on the GPU -- the blocks src has are allocated in dst by the
 // reference's two-phase allocation, then every voxel is combined as the swapping engine combines a stored block (src in that role).
 // Same voxel type, index type and voxelSize; both scenes on one device.  srcVisible: a render state of src whose visible list selects
@@ -313,13 +324,7 @@ class ITMSceneMergeEngine_HIP {
   void MergeScene(ITMScene<TVoxel, TIndex>* dst, const ITMScene<TVoxel, TIndex>* src, const ITMRenderState* srcVisible = nullptr, itm_merge_stats* stats = nullptr) {
     const int32_t* slots = nullptr;
     int n = 0;
-    if (srcVisible) {
-      itm_counters c;
-      check(itm_get_counters(src->handle, srcVisible->handle, &c, stream), "MergeScene (visible list)");
-      slots = (const int32_t*)itm_buffer_ptr(src->handle, srcVisible->handle, ITM_BUF_VISIBLE_IDS);
-      n = c.noVisibleEntries;
-      if (!slots) throw std::runtime_error("MergeScene: the render state has no visible list");
-    }
+    visible_slots(src, srcVisible, stream, "MergeScene", &slots, &n);
     check(itm_scene_merge(dst->handle, src->handle, slots, n, stats, stream), "MergeScene");
   }
 };
@@ -349,13 +354,7 @@ class ITMSceneCoarsenEngine_HIP {
   void CoarsenScene(ITMScene<TVoxel, TIndex>* dst, const ITMScene<TVoxel, TIndex>* src, const ITMRenderState* srcVisible = nullptr, itm_coarsen_stats* stats = nullptr) {
     const int32_t* slots = nullptr;
     int n = 0;
-    if (srcVisible) {
-      itm_counters c;
-      check(itm_get_counters(src->handle, srcVisible->handle, &c, stream), "CoarsenScene (visible list)");
-      slots = (const int32_t*)itm_buffer_ptr(src->handle, srcVisible->handle, ITM_BUF_VISIBLE_IDS);
-      n = c.noVisibleEntries;
-      if (!slots) throw std::runtime_error("CoarsenScene: the render state has no visible list");
-    }
+    visible_slots(src, srcVisible, stream, "CoarsenScene", &slots, &n);
     check(itm_scene_coarsen(dst->handle, src->handle, slots, n, stats, stream), "CoarsenScene");
   }
 };
@@ -374,13 +373,7 @@ class ITMSceneResampleEngine_HIP {
     check(itm_rigid_quantise(dstFromSrc.m, dst->sceneParams->voxelSize, &q), "ResampleScene (itm_rigid_quantise)");
     const int32_t* slots = nullptr;
     int n = 0;
-    if (srcVisible) {
-      itm_counters c;
-      check(itm_get_counters(src->handle, srcVisible->handle, &c, stream), "ResampleScene (visible list)");
-      slots = (const int32_t*)itm_buffer_ptr(src->handle, srcVisible->handle, ITM_BUF_VISIBLE_IDS);
-      n = c.noVisibleEntries;
-      if (!slots) throw std::runtime_error("ResampleScene: the render state has no visible list");
-    }
+    visible_slots(src, srcVisible, stream, "ResampleScene", &slots, &n);
     check(itm_scene_resample(dst->handle, src->handle, &q, slots, n, stats, stream), "ResampleScene");
   }
 };
@@ -411,13 +404,7 @@ class ITMSceneAlignEngine_HIP {
   int32_t SetSamplesFromScene(const ITMScene<TVoxel, TIndex>* src, const itm_align_config& cfg, const ITMRenderState* srcVisible = nullptr) {
     const int32_t* slots = nullptr;
     int n = 0;
-    if (srcVisible) {
-      itm_counters c;
-      check(itm_get_counters(src->handle, srcVisible->handle, &c, stream), "AlignScene (visible list)");
-      slots = (const int32_t*)itm_buffer_ptr(src->handle, srcVisible->handle, ITM_BUF_VISIBLE_IDS);
-      n = c.noVisibleEntries;
-      if (!slots) throw std::runtime_error("AlignScene: the render state has no visible list");
-    }
+    visible_slots(src, srcVisible, stream, "AlignScene", &slots, &n);
     for (int pass = 0; pass < 2; ++pass) {      // the second pass only when the buffer had to grow
       check(itm_scene_band_samples(src->handle, slots, n, &cfg, (float*)samples, capacity, &count, stream), "AlignScene (itm_scene_band_samples)");
       if (count <= capacity) break;

@@ -925,9 +925,10 @@ class Scene:
         keep = self.be.to_backend(arr, stream)
         return keep.ptr, len(arr), keep
 
-    def _slot_call(self, name, stats, src, slots, stream) -> dict:
+    def _slot_call(self, name, stats, src, slots, stream, *extra) -> dict:
+        """extra: the arguments of the entry point between the two scenes and the slot list."""
         ptr, n, keep = self._slot_list(slots, stream)
-        rc = self.be.fn[name](_P(self.h), _P(src.h), _P(ptr), n, C.byref(stats), _P(stream))
+        rc = self.be.fn[name](_P(self.h), _P(src.h), *extra, _P(ptr), n, C.byref(stats), _P(stream))
         if keep is not None:
             self.be.sync(stream)
             keep.close()
@@ -971,14 +972,7 @@ class Scene:
         """itm_scene_resample: resamples `src` into this scene's frame and fuses it here, on the GPU; returns the statistics.
         q_or_matrix: a RigidQ, or the 4 x 4 matrix dstFromSrc in metres (quantised with this scene's voxel size).  slots: as merge_from."""
         q = q_or_matrix if isinstance(q_or_matrix, RigidQ) else rigid_quantise(q_or_matrix, float(self.params.voxelSize), self.be)
-        ptr, n, keep = self._slot_list(slots, stream)
-        stats = ResampleStats()
-        rc = self.be.fn["scene_resample"](_P(self.h), _P(src.h), C.byref(q), _P(ptr), n, C.byref(stats), _P(stream))
-        if keep is not None:
-            self.be.sync(stream)
-            keep.close()
-        self.be.check(rc, "scene_resample")
-        return stats.as_dict()
+        return self._slot_call("scene_resample", ResampleStats(), src, slots, stream, C.byref(q))
 
     def align_config(self, **kw) -> AlignConfig:
         """itm_align_default_config for this scene's voxelSize and mu, with the fields given in kw replaced."""

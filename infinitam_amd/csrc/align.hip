@@ -289,8 +289,7 @@ int itm_scene_band_samples(const itm_scene* src, const int32_t* srcSlots_dev, in
   if (capacity < 0 || (capacity > 0 && !samples_dev)) return set_error(ITM_ERR_INVALID, "band samples: a capacity without a buffer");
   if (((uintptr_t)samples_dev & 15u) != 0) return set_error(ITM_ERR_INVALID, "band samples: samples_dev must be 16-byte aligned");
   const bool hash = src->cfg.indexType == ITM_INDEX_HASH;
-  if (!hash && srcSlots_dev) return set_error(ITM_ERR_INVALID, "band samples: a slot list with a dense scene");
-  if (hash && srcSlots_dev && n < 0) return set_error(ITM_ERR_INVALID, "band samples: negative slot count");
+  { const int rc = check_slot_list(hash, srcSlots_dev, n, "band samples", "a dense scene"); if (rc) return rc; }
   { const int rc = enter_scene(src, nullptr); if (rc) return rc; }
   hipStream_t st = as_stream(stream);
   BandParams p;
@@ -303,28 +302,17 @@ int itm_scene_band_samples(const itm_scene* src, const int32_t* srcSlots_dev, in
   const int nChunks = (int)((p.elements + kSweepChunk - 1) / kSweepChunk);
   *count_out = 0;
   if (nChunks == 0) return ITM_OK;
-  // scratch of the call: total | tallies | chunkCount | chunkBase | sel
-  const size_t S = hash && srcSlots_dev ? (size_t)src->noTotalEntries : 0;
-  const size_t oStats = 256, oCount = oStats + align256(kMsCount * 4), oBase = oCount + align256((size_t)nChunks * 4), oSel = oBase + align256((size_t)nChunks * 4);
+  // scratch of the call (scene_ops.h: BandArena; src is const here, so nothing is kept with it)
+  const BandArena a(kMsCount, (size_t)nChunks, hash && srcSlots_dev ? (size_t)src->noTotalEntries : 0);
   DeviceBuffer<void> scratch;
-  ITM_HIP(scratch.alloc(oSel + align256(S)));
-  uint8_t* base = (uint8_t*)scratch.get();
-  int32_t* dTotal = (int32_t*)base;
-  int32_t* dStats = (int32_t*)(base + oStats);
-  int32_t* chunkCount = (int32_t*)(base + oCount);
-  int32_t* chunkBase = (int32_t*)(base + oBase);
-  uint8_t* sel = S ? base + oSel : nullptr;
+  ITM_HIP(scratch.alloc(a.L.bytes()));
+  void* base = scratch.get();
+  int32_t* dTotal = a.total.at(base); int32_t* chunkCount = a.chunkCount.at(base); int32_t* chunkBase = a.chunkBase.at(base);
+  uint8_t* sel = hash && srcSlots_dev ? a.sel.at(base) : nullptr;
   if (sel) {
-    ITM_HIP(hipMemsetAsync(dStats, 0, kMsCount * 4, st));
-    ITM_HIP(hipMemsetAsync(sel, 0, S, st));
-    if (n > 0) {
-      merge_mark_kernel<<<(n + 255) / 256, 256, 0, st>>>(srcSlots_dev, n, src->noTotalEntries, sel, dStats);
-      ITM_LAUNCH_CHECK();
-    }
-    int32_t h[kMsCount];
-    ITM_HIP(hipMemcpyAsync(h, dStats, sizeof h, hipMemcpyDeviceToHost, st));
-    ITM_HIP(hipStreamSynchronize(st));
-    if (h[kMsBadSlot]) return set_error(ITM_ERR_INVALID, "band samples: a slot of the list is outside src's table");
+    MergePlacement tallies{a.stats.at(base), st};
+    ITM_HIP(hipMemsetAsync(tallies.dStats, 0, kMsCount * 4, st));
+    if (const int rc = select_slots(srcSlots_dev, n, src->noTotalEntries, sel, tallies, "band samples")) return rc;
   }
   const int rc = dispatch_volume(src, [&](auto vx, auto dense) {
     using VX = decltype(vx);

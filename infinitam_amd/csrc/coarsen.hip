@@ -14,8 +14,6 @@
 // LDS in the defined order.  Stores are whole voxels, consecutive lanes on consecutive voxels, plus the block's 512 mirror values
 // (mapping the page of a block this call allocated).  The workgroup zeroes the slot's request key again.
 // Dense: one lane per dst cell in a grid-stride loop, taps straight from global memory.
-#include <cstring>
-
 #include "merge_device.h"
 #include "volume_device.h"
 
@@ -169,60 +167,27 @@ using namespace itm;
 extern "C" {
 
 int itm_scene_coarsen(itm_scene* dst, const itm_scene* src, const int32_t* srcSlots_dev, int n, itm_coarsen_stats* stats, itm_stream stream) {
-  if (!dst || !src) return set_error(ITM_ERR_INVALID, "scene coarsen: null scene");
-  if (dst == src) return set_error(ITM_ERR_INVALID, "scene coarsen: dst and src are the same scene");
-  if (dst->device != src->device) return set_error(ITM_ERR_INVALID, "scene coarsen: the scenes are on different devices");
-  if (dst->cfg.voxelType != src->cfg.voxelType) return set_error(ITM_ERR_INVALID, "scene coarsen: the scenes differ in voxelType");
-  if (dst->cfg.indexType != src->cfg.indexType) return set_error(ITM_ERR_INVALID, "scene coarsen: the scenes differ in indexType");
-  const float twice = 2.0f * src->prm.voxelSize;
-  if (memcmp(&dst->prm.voxelSize, &twice, sizeof(float)) != 0) return set_error(ITM_ERR_INVALID, "scene coarsen: dst's voxelSize is not twice src's");
-  if (memcmp(&dst->prm.mu, &src->prm.mu, sizeof(float)) != 0) return set_error(ITM_ERR_INVALID, "scene coarsen: the scenes differ in mu");
+  { const int rc = check_scene_pair(dst, src, "scene coarsen", true, true); if (rc) return rc; }
+  { const int rc = enter_scene_pair(dst, src, srcSlots_dev, n, "scene coarsen"); if (rc) return rc; }
   const bool hash = dst->cfg.indexType == ITM_INDEX_HASH;
-  if (!hash) {
-    if (srcSlots_dev) return set_error(ITM_ERR_INVALID, "scene coarsen: a slot list with dense scenes");
-  } else if (srcSlots_dev && n < 0) return set_error(ITM_ERR_INVALID, "scene coarsen: negative slot count");
-  { const int rc = enter_scene(dst, nullptr); if (rc) return rc; }
-  { const int rc = enter_scene(src, nullptr); if (rc) return rc; }
-  if (dst->aheadRs) return set_error(ITM_ERR_INVALID, "scene coarsen: dst holds the block requests of a frame issued ahead (itm_cancel_ahead first)");
   hipStream_t st = as_stream(stream);
   itm_coarsen_stats out{};
   VolumeView fine = make_volume(src);
-  if (!hash) {
-    const int rc = dispatch_voxel(dst->cfg.voxelType, [&](auto vx) {
-      using VX = decltype(vx);
-      coarsen_dense_kernel<VX><<<4096, 256, 0, st>>>(fine, dst->vba, dst->cfg.denseSize[0], dst->cfg.denseSize[1], dst->cfg.denseSize[2],
-                                                     dst->cfg.denseOffset[0], dst->cfg.denseOffset[1], dst->cfg.denseOffset[2], dst->prm.maxW);
-      return ITM_OK;
+  if (!hash)
+    return finish_dense(dst, out, &itm_coarsen_stats::written, stats, [&](auto vx) {
+      coarsen_dense_kernel<decltype(vx)><<<4096, 256, 0, st>>>(fine, dst->vba, dst->cfg.denseSize[0], dst->cfg.denseSize[1], dst->cfg.denseSize[2], dst->cfg.denseOffset[0],
+                                                               dst->cfg.denseOffset[1], dst->cfg.denseOffset[2], dst->prm.maxW);
     });
-    if (rc) return rc;
-    ITM_LAUNCH_CHECK();
-    out.considered = out.written = 1;
-    if (stats) *stats = out;
-    return ITM_OK;
-  }
 
   MergePlacement pl;
   { const int rc = place_participants<1>(dst, src, srcSlots_dev, n, st, "scene coarsen", pl); if (rc) return rc; }
-  out.rounds = pl.rounds; out.allocated = pl.allocated; out.unserved = pl.unserved;
-  claim_blocks_kernel<<<(src->noTotalEntries + 255) / 256, 256, 0, st>>>(src->noTotalEntries, pl.where, dst->hash, dst->numVoxels, dst->allocKey, pl.list, pl.dStats);
-  ITM_LAUNCH_CHECK();
-  { const int rc = pl.read_stats(); if (rc) return rc; }
-  const int32_t* h = pl.h;
-  out.considered = h[kMsConsidered]; out.srcWithoutBlock = h[kMsSrcWithoutBlock]; out.alreadyPresent = h[kMsPresentFirst];
-  out.written = h[kMsCombined]; out.dstSwappedOut = h[kMsDstSwappedOut];
-  if (h[kMsListCount] > 0) {
-    const int count = h[kMsListCount];
-    const int rc = dispatch_voxel(dst->cfg.voxelType, [&](auto vx) {
-      using VX = decltype(vx);
-      coarsen_block_kernel<VX><<<count, 512, 0, st>>>(pl.list, fine, src->noTotalEntries, src->numVoxels, dst->hash, dst->vba, dst->numVoxels, dst->prm.maxW, dst->allocKey,
-                                                      accel_writer(dst));
-      return ITM_OK;
-    });
-    if (rc) return rc;
-    ITM_LAUNCH_CHECK();
-  }
-  if (stats) *stats = out;
-  return ITM_OK;
+  out.considered = pl.h[kMsConsidered]; out.srcWithoutBlock = pl.h[kMsSrcWithoutBlock];
+  return finish_placed(dst, pl, out, &itm_coarsen_stats::written, stats,
+      [&] { claim_blocks_kernel<<<(src->noTotalEntries + 255) / 256, 256, 0, st>>>(src->noTotalEntries, pl.where, dst->hash, dst->numVoxels, dst->allocKey, pl.list, pl.dStats); },
+      [&](auto vx, int count) {
+        coarsen_block_kernel<decltype(vx)><<<count, 512, 0, st>>>(pl.list, fine, src->noTotalEntries, src->numVoxels, dst->hash, dst->vba, dst->numVoxels, dst->prm.maxW, dst->allocKey,
+                                                                  accel_writer(dst));
+      });
 }
 
 }  // extern "C"

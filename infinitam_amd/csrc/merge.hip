@@ -64,60 +64,26 @@ using namespace itm;
 extern "C" {
 
 int itm_scene_merge(itm_scene* dst, const itm_scene* src, const int32_t* srcSlots_dev, int n, itm_merge_stats* stats, itm_stream stream) {
-  if (!dst || !src) return set_error(ITM_ERR_INVALID, "scene merge: null scene");
-  if (dst == src) return set_error(ITM_ERR_INVALID, "scene merge: dst and src are the same scene");
-  if (dst->device != src->device) return set_error(ITM_ERR_INVALID, "scene merge: the scenes are on different devices");
-  if (dst->cfg.voxelType != src->cfg.voxelType) return set_error(ITM_ERR_INVALID, "scene merge: the scenes differ in voxelType");
-  if (dst->cfg.indexType != src->cfg.indexType) return set_error(ITM_ERR_INVALID, "scene merge: the scenes differ in indexType");
-  if (memcmp(&dst->prm.voxelSize, &src->prm.voxelSize, sizeof(float)) != 0) return set_error(ITM_ERR_INVALID, "scene merge: the scenes differ in voxelSize");
+  // (mu is not compared: the combine works on the stored fractions of mu, and tests/scene_merge_terms.py defines it so)
+  { const int rc = check_scene_pair(dst, src, "scene merge", false, false); if (rc) return rc; }
   const bool hash = dst->cfg.indexType == ITM_INDEX_HASH;
-  if (!hash) {
-    if (memcmp(dst->cfg.denseSize, src->cfg.denseSize, sizeof dst->cfg.denseSize) != 0 || memcmp(dst->cfg.denseOffset, src->cfg.denseOffset, sizeof dst->cfg.denseOffset) != 0 ||
-        dst->numVoxels != src->numVoxels)
-      return set_error(ITM_ERR_INVALID, "scene merge: dense scenes differ in denseSize / denseOffset");
-    if (srcSlots_dev) return set_error(ITM_ERR_INVALID, "scene merge: a slot list with dense scenes");
-  } else if (srcSlots_dev && n < 0) return set_error(ITM_ERR_INVALID, "scene merge: negative slot count");
-  { const int rc = enter_scene(dst, nullptr); if (rc) return rc; }
-  { const int rc = enter_scene(src, nullptr); if (rc) return rc; }
-  if (dst->aheadRs) return set_error(ITM_ERR_INVALID, "scene merge: dst holds the block requests of a frame issued ahead (itm_cancel_ahead first)");
+  if (!hash && (memcmp(dst->cfg.denseSize, src->cfg.denseSize, sizeof dst->cfg.denseSize) != 0 || memcmp(dst->cfg.denseOffset, src->cfg.denseOffset, sizeof dst->cfg.denseOffset) != 0 ||
+                dst->numVoxels != src->numVoxels))
+    return set_error(ITM_ERR_INVALID, "scene merge: dense scenes differ in denseSize / denseOffset");
+  { const int rc = enter_scene_pair(dst, src, srcSlots_dev, n, "scene merge"); if (rc) return rc; }
   hipStream_t st = as_stream(stream);
   itm_merge_stats out{};
-  if (!hash) {
-    const int rc = dispatch_voxel(dst->cfg.voxelType, [&](auto vx) {
-      using VX = decltype(vx);
-      merge_dense_kernel<VX><<<4096, 256, 0, st>>>(src->vba, dst->vba, dst->numVoxels, dst->prm.maxW);
-      return ITM_OK;
-    });
-    if (rc) return rc;
-    ITM_LAUNCH_CHECK();
-    out.considered = out.combined = 1;
-    if (stats) *stats = out;
-    return ITM_OK;
-  }
+  if (!hash)
+    return finish_dense(dst, out, &itm_merge_stats::combined, stats, [&](auto vx) { merge_dense_kernel<decltype(vx)><<<4096, 256, 0, st>>>(src->vba, dst->vba, dst->numVoxels, dst->prm.maxW); });
 
   MergePlacement pl;
   { const int rc = place_participants<0>(dst, src, srcSlots_dev, n, st, "scene merge", pl); if (rc) return rc; }
-  int32_t* dStats = pl.dStats; int32_t* where = pl.where; int32_t* list = pl.list;
-  const int32_t* h = pl.h;
-  out.rounds = pl.rounds; out.allocated = pl.allocated; out.unserved = pl.unserved;
-  const int reqGrid = (src->noTotalEntries + 255) / 256;
-  merge_list_kernel<<<reqGrid, 256, 0, st>>>(src->hash, src->noTotalEntries, where, dst->hash, src->numVoxels, dst->numVoxels, list, dStats);
-  ITM_LAUNCH_CHECK();
-  { const int rc = pl.read_stats(); if (rc) return rc; }
-  out.considered = h[kMsConsidered]; out.srcWithoutBlock = h[kMsSrcWithoutBlock]; out.alreadyPresent = h[kMsPresentFirst];
-  out.combined = h[kMsCombined]; out.dstSwappedOut = h[kMsDstSwappedOut];
-  if (h[kMsListCount] > 0) {
-    const int count = h[kMsListCount];
-    const int rc = dispatch_voxel(dst->cfg.voxelType, [&](auto vx) {
-      using VX = decltype(vx);
-      merge_combine_kernel<VX><<<count, 512, 0, st>>>(list, src->hash, src->vba, where, dst->hash, dst->vba, dst->prm.maxW, accel_writer(dst));
-      return ITM_OK;
-    });
-    if (rc) return rc;
-    ITM_LAUNCH_CHECK();
-  }
-  if (stats) *stats = out;
-  return ITM_OK;
+  out.considered = pl.h[kMsConsidered]; out.srcWithoutBlock = pl.h[kMsSrcWithoutBlock];
+  return finish_placed(dst, pl, out, &itm_merge_stats::combined, stats,
+      [&] { merge_list_kernel<<<(src->noTotalEntries + 255) / 256, 256, 0, st>>>(src->hash, src->noTotalEntries, pl.where, dst->hash, src->numVoxels, dst->numVoxels, pl.list, pl.dStats); },
+      [&](auto vx, int count) {
+        merge_combine_kernel<decltype(vx)><<<count, 512, 0, st>>>(pl.list, src->hash, src->vba, pl.where, dst->hash, dst->vba, dst->prm.maxW, accel_writer(dst));
+      });
 }
 
 }  // extern "C"

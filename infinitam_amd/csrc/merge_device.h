@@ -17,9 +17,11 @@
 // requests only).  Losers of a target ask again in the next round, where the winner's entry is part of the chain.  The host reads the
 // round's counts (one round trip per round, as the swapping engine does per call).  The sweep sets the occupancy bit and the directory
 // cells of what it allocates; the caller's voxel launch stores the 512 mirror values of every block it touches.
+// Host side, below the kernels: the selection by slot list, the rounds, and the tail of a call (scratch and refusals: scene_ops.h).
 #pragma once
 
 #include "itm_internal.h"
+#include "scene_ops.h"
 #include "wave_utils.h"
 
 namespace itm {
@@ -203,21 +205,32 @@ static __global__ void __launch_bounds__(256) claim_blocks_kernel(int srcEntries
   tally(stats, kMsCombined, (first && dp >= 0 && (size_t)dp * kBlockVoxels + kBlockVoxels <= dstVoxels) ? 1 : 0);
 }
 
-static inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
-// ---- host side: steps 1 and 2 of a call ------------------------------------------------------------------------------------------------
-// The scratch of a call, kept with dst: tallies | where[srcEntries] | list[srcEntries] | chunkCnt[dst chunks] | sel[srcEntries]
-struct MergePlacement {
-  int32_t* dStats = nullptr; int32_t* where = nullptr; int32_t* list = nullptr;
+// ---- host side: steps 1 and 2 of a call, and its tail -----------------------------------------------------------------------------------
+struct MergePlacement {      // (its arrays: scene_ops.h, PlacementArena and ResampleArena)
+  int32_t* dStats = nullptr; hipStream_t st = nullptr; int32_t* where = nullptr; int32_t* list = nullptr;
   int32_t h[kMsCount] = {};                         // the tallies as last read
   int rounds = 0, allocated = 0, unserved = 0;
-  hipStream_t st = nullptr;
-  int read_stats() {
+  int read_stats() {                                // one host round trip
     ITM_HIP(hipMemcpyAsync(h, dStats, sizeof h, hipMemcpyDeviceToHost, st));
     ITM_HIP(hipStreamSynchronize(st));
     return ITM_OK;
   }
 };
+
+// The selection by slot list.  mark_slots clears sel[0 .. srcEntries) and marks the listed slots (one outside the table raises kMsBadSlot
+// in the tallies, which the caller has cleared); it reads nothing back, so a caller may queue more in front of the one round trip.
+// refuse_bad_slots judges the tallies once read (ITM_ERR_INVALID, dst still untouched); select_slots: mark, read, judge.
+inline int mark_slots(const int32_t* srcSlots_dev, int n, int srcEntries, uint8_t* sel, int32_t* dStats, hipStream_t st) {
+  ITM_HIP(hipMemsetAsync(sel, 0, (size_t)srcEntries, st));
+  if (n > 0) { merge_mark_kernel<<<(n + 255) / 256, 256, 0, st>>>(srcSlots_dev, n, srcEntries, sel, dStats); ITM_LAUNCH_CHECK(); }
+  return ITM_OK;
+}
+inline int refuse_bad_slots(const int32_t* h, const char* what) { return h[kMsBadSlot] ? refuse(what, "a slot of the list is outside src's table") : ITM_OK; }
+inline int select_slots(const int32_t* srcSlots_dev, int n, int srcEntries, uint8_t* sel, MergePlacement& p, const char* what) {
+  { const int rc = mark_slots(srcSlots_dev, n, srcEntries, sel, p.dStats, p.st); if (rc) return rc; }
+  { const int rc = p.read_stats(); if (rc) return rc; }
+  return refuse_bad_slots(p.h, what);
+}
 
 // The rounds of step 2 over any device array of packed entries: `posHash[0 .. posEntries)` names the positions (an entry with ptr >= 0
 // takes part, `sel` -- may be null -- narrows that to the selected slots), `p.where` has one int per entry.  itm_scene_merge and
@@ -228,6 +241,7 @@ inline int place_positions(itm_scene* dst, const uint4* posHash, int posEntries,
   const int reqGrid = (posEntries + 255) / 256;
   for (int round = 1;; ++round) {
     ITM_HIP(hipMemsetAsync(chunkCnt, 0, (size_t)dst->numChunks * 8, st));
+    static_assert(kMsTargets == kMsPending + 1 && kMsServedBlocks == kMsPending + 2 && kMsServedExcess == kMsPending + 3, "the four per-round tallies are consecutive");
     ITM_HIP(hipMemsetAsync(p.dStats + kMsPending, 0, 4 * 4, st));      // pending, targets, served blocks, served excess entries: per round
     if (round == 1) merge_request_kernel<true, SHIFT><<<reqGrid, 256, 0, st>>>(posHash, posEntries, sel, p.where, table, dst->allocKey, chunkCnt, p.dStats);
     else merge_request_kernel<false, SHIFT><<<reqGrid, 256, 0, st>>>(posHash, posEntries, sel, p.where, table, dst->allocKey, chunkCnt, p.dStats);
@@ -272,26 +286,45 @@ inline void place_cubes_like(itm_scene* dst, const itm_scene* src, ToDst&& toDst
 // the rounds over src's table.  `what`: the entry point's name for messages.
 template <int SHIFT>
 inline int place_participants(itm_scene* dst, const itm_scene* src, const int32_t* srcSlots_dev, int n, hipStream_t st, const char* what, MergePlacement& p) {
-  const size_t S = (size_t)src->noTotalEntries;
-  const size_t oStats = 0, oWhere = align256(kMsCount * 4), oList = oWhere + align256(S * 4), oChunk = oList + align256(S * 4),
-               oSel = oChunk + align256((size_t)dst->numChunks * 8), need = oSel + align256(S);
-  ITM_HIP(dst->mergeScratch.reserve(need));
-  uint8_t* base = (uint8_t*)dst->mergeScratch.get();
-  p.dStats = (int32_t*)(base + oStats); p.where = (int32_t*)(base + oWhere); p.list = (int32_t*)(base + oList); p.st = st;
-  int2* chunkCnt = (int2*)(base + oChunk); uint8_t* sel = srcSlots_dev ? base + oSel : nullptr;
+  const PlacementArena a(kMsCount, (size_t)src->noTotalEntries, (size_t)dst->numChunks);
+  ITM_HIP(dst->mergeScratch.reserve(a.L.bytes()));
+  void* base = dst->mergeScratch.get();
+  p.dStats = a.stats.at(base); p.where = a.where.at(base); p.list = a.list.at(base); p.st = st;
+  uint8_t* sel = srcSlots_dev ? a.sel.at(base) : nullptr;
   ITM_HIP(hipMemsetAsync(p.dStats, 0, kMsCount * 4, st));
-  if (sel) {
-    ITM_HIP(hipMemsetAsync(sel, 0, S, st));
-    if (n > 0) {
-      merge_mark_kernel<<<(n + 255) / 256, 256, 0, st>>>(srcSlots_dev, n, src->noTotalEntries, sel, p.dStats);
-      ITM_LAUNCH_CHECK();
-    }
-    { const int rc = p.read_stats(); if (rc) return rc; }
-    if (p.h[kMsBadSlot]) return set_error(ITM_ERR_INVALID, std::string(what) + ": a slot of the list is outside src's table");      // dst is untouched
-  }
+  if (sel) { const int rc = select_slots(srcSlots_dev, n, src->noTotalEntries, sel, p, what); if (rc) return rc; }
   // (c >> SHIFT is the centre of src's cube in dst's blocks; SHIFT == 0 leaves c as it is)
   place_cubes_like(dst, src, [](const int c[3], int o[3]) { for (int i = 0; i < 3; ++i) o[i] = c[i] >> SHIFT; });
-  return place_positions<SHIFT>(dst, src->hash, src->noTotalEntries, sel, chunkCnt, st, p);
+  return place_positions<SHIFT>(dst, src->hash, src->noTotalEntries, sel, a.chunkCnt.at<int2>(base), st, p);
+}
+
+// The tail of a placed call.  listLaunch() fills p.list and the tallies (claim_blocks_kernel, or merge's own list); then the one round
+// trip, the statistics every operation reports (done: the field that counts the blocks written) and blocks(vx, count), the caller's
+// voxel launch over list[0 .. count).  *stats (may be null) is written once all has been launched.
+template <class Stats, class ListLaunch, class Blocks>
+inline int finish_placed(itm_scene* dst, MergePlacement& p, Stats& out, int32_t Stats::*done, Stats* stats, ListLaunch&& listLaunch, Blocks&& blocks) {
+  out.rounds = p.rounds; out.allocated = p.allocated; out.unserved = p.unserved;
+  listLaunch();
+  ITM_LAUNCH_CHECK();
+  { const int rc = p.read_stats(); if (rc) return rc; }
+  out.alreadyPresent = p.h[kMsPresentFirst]; out.*done = p.h[kMsCombined]; out.dstSwappedOut = p.h[kMsDstSwappedOut];
+  if (const int count = p.h[kMsListCount]; count > 0) {
+    const int rc = dispatch_voxel(dst->cfg.voxelType, [&](auto vx) { blocks(vx, count); return ITM_OK; });
+    if (rc) return rc;
+    ITM_LAUNCH_CHECK();
+  }
+  if (stats) *stats = out;
+  return ITM_OK;
+}
+// A call on dense scenes: cells(vx), the caller's grid-stride launch over dst's array; the statistics say one volume, written.
+template <class Stats, class Cells>
+inline int finish_dense(const itm_scene* dst, Stats& out, int32_t Stats::*done, Stats* stats, Cells&& cells) {
+  const int rc = dispatch_voxel(dst->cfg.voxelType, [&](auto vx) { cells(vx); return ITM_OK; });
+  if (rc) return rc;
+  ITM_LAUNCH_CHECK();
+  out.considered = out.*done = 1;
+  if (stats) *stats = out;
+  return ITM_OK;
 }
 
 }  // namespace itm

@@ -24,6 +24,7 @@
 
 #include "itm_internal.h"
 #include "ordered_device.h"
+#include "scene_ops.h"
 #include "wave_utils.h"
 
 namespace itm {
@@ -327,7 +328,6 @@ __global__ void __launch_bounds__(256) prune_rs_commit_kernel(int32_t* __restric
 }
 
 constexpr int kClassifyGrid = 2048;      // workgroups of the classifying launch at most: 8 192 waves, each over every 8 192nd group of 64 entries
-static inline size_t prune_align(size_t n) { return (n + 255) & ~(size_t)255; }
 
 }  // namespace itm
 
@@ -358,7 +358,7 @@ int itm_scene_prune(itm_scene* s, const itm_prune_config* cfg, uint8_t* decision
     for (int k = 0; k < 3; ++k)
       if (cfg->boxMin[k] > cfg->boxMax[k]) return set_error(ITM_ERR_INVALID, "scene prune: the box has min > max");
   { const int rc = enter_scene(s, nullptr); if (rc) return rc; }
-  if (s->aheadRs) return set_error(ITM_ERR_INVALID, "scene prune: the scene holds the block requests of a frame issued ahead (itm_cancel_ahead first)");
+  { const int rc = refuse_ahead(s, "scene prune", "the scene"); if (rc) return rc; }
   hipStream_t st = as_stream(stream);
   const bool write = !cfg->dryRun;
 
@@ -367,19 +367,16 @@ int itm_scene_prune(itm_scene* s, const itm_prune_config* cfg, uint8_t* decision
   r.shortThr = (int)(int16_t)(cfg->freeSdf * 32767.0f); r.floatThr = cfg->freeSdf; r.weakMaxW = cfg->weakMaxW;
   for (int k = 0; k < 3; ++k) { r.bmin[k] = boxUsed ? cfg->boxMin[k] : 0; r.bmax[k] = boxUsed ? cfg->boxMax[k] : 0; }
 
-  // scratch, kept with the scene: statistics | decision bytes | dropped flags | chunk counts | dropped ids | list copy | list chunk counts
+  // scratch, kept with the scene (scene_ops.h: PruneArena)
   const std::vector<itm_render_state*> states = render_states_of(s);
   const int N = s->noTotalEntries, nChunks = s->numChunks, cap = s->cfg.localBlockNum, rsChunks = (cap + kSweepChunk - 1) / kSweepChunk;
   const size_t padded = (size_t)nChunks * kSweepChunk;
-  const size_t oStats = 0, oDec = prune_align(kPsCount * 4), oFlags = oDec + prune_align(padded), oChunk = oFlags + prune_align(padded),
-               oIds = oChunk + prune_align((size_t)nChunks * 4), oTmp = oIds + prune_align((size_t)N * 4), oRsChunk = oTmp + prune_align((size_t)cap * 4),
-               oPart = oRsChunk + prune_align((size_t)rsChunks * 4), need = oPart + prune_align((size_t)kClassifyGrid * 4 * kPartialWords * 4);
-  ITM_HIP(s->pruneScratch.reserve(need));
-  uint8_t* base = (uint8_t*)s->pruneScratch.get();
-  int32_t* dStats = (int32_t*)(base + oStats); uint8_t* dec = base + oDec; uint8_t* flags = base + oFlags; int32_t* chunkCount = (int32_t*)(base + oChunk);
-  int32_t* ids = (int32_t*)(base + oIds); int32_t* tmp = (int32_t*)(base + oTmp); int32_t* rsChunk = (int32_t*)(base + oRsChunk);
-  int32_t* partial = (int32_t*)(base + oPart);
-  ITM_HIP(hipMemsetAsync(base, 0, oIds, st));      // statistics, bytes, flags and chunk counts
+  const PruneArena a(kPsCount, padded, (size_t)nChunks, (size_t)N, (size_t)cap, (size_t)rsChunks, (size_t)kClassifyGrid * 4 * kPartialWords);
+  ITM_HIP(s->pruneScratch.reserve(a.L.bytes()));
+  void* base = s->pruneScratch.get();
+  int32_t* dStats = a.stats.at(base); uint8_t* dec = a.dec.at(base); uint8_t* flags = a.flags.at(base); int32_t* chunkCount = a.chunkCount.at(base);
+  int32_t* ids = a.ids.at(base); int32_t* tmp = a.tmp.at(base); int32_t* rsChunk = a.rsChunk.at(base); int32_t* partial = a.partial.at(base);
+  ITM_HIP(hipMemsetAsync(base, 0, a.L.bytes_before(a.ids), st));      // statistics, bytes, flags and chunk counts
 
   const int nBlocks = s->cfg.localBlockNum;
   {

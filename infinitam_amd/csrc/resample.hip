@@ -374,14 +374,8 @@ int itm_rigid_quantise(const float dstFromSrc[16], float voxelSize, itm_rigid_q*
 }
 
 int itm_scene_resample(itm_scene* dst, const itm_scene* src, const itm_rigid_q* q, const int32_t* srcSlots_dev, int n, itm_resample_stats* stats, itm_stream stream) {
-  if (!dst || !src) return set_error(ITM_ERR_INVALID, "scene resample: null scene");
-  if (!q) return set_error(ITM_ERR_INVALID, "scene resample: null transform");
-  if (dst == src) return set_error(ITM_ERR_INVALID, "scene resample: dst and src are the same scene");
-  if (dst->device != src->device) return set_error(ITM_ERR_INVALID, "scene resample: the scenes are on different devices");
-  if (dst->cfg.voxelType != src->cfg.voxelType) return set_error(ITM_ERR_INVALID, "scene resample: the scenes differ in voxelType");
-  if (dst->cfg.indexType != src->cfg.indexType) return set_error(ITM_ERR_INVALID, "scene resample: the scenes differ in indexType");
-  if (memcmp(&dst->prm.voxelSize, &src->prm.voxelSize, sizeof(float)) != 0) return set_error(ITM_ERR_INVALID, "scene resample: the scenes differ in voxelSize");
-  if (memcmp(&dst->prm.mu, &src->prm.mu, sizeof(float)) != 0) return set_error(ITM_ERR_INVALID, "scene resample: the scenes differ in mu");
+  if (dst && src && !q) return set_error(ITM_ERR_INVALID, "scene resample: null transform");      // (second to the null scene)
+  { const int rc = check_scene_pair(dst, src, "scene resample", false, true); if (rc) return rc; }
   for (int i = 0; i < 3; ++i) {
     long long rowInv = 0, rowFwd = 0;
     for (int j = 0; j < 3; ++j) { rowInv += llabs((long long)q->inv[3 * i + j]); rowFwd += llabs((long long)q->fwd[3 * i + j]); }
@@ -389,60 +383,39 @@ int itm_scene_resample(itm_scene* dst, const itm_scene* src, const itm_rigid_q* 
     if (q->invT[i] <= -kQ30MaxT || q->invT[i] >= kQ30MaxT || q->fwdT[i] <= -kQ30MaxT || q->fwdT[i] >= kQ30MaxT)
       return set_error(ITM_ERR_INVALID, "scene resample: a translation of the transform is 2^18 voxels or more");
   }
+  { const int rc = enter_scene_pair(dst, src, srcSlots_dev, n, "scene resample"); if (rc) return rc; }
   const bool hash = dst->cfg.indexType == ITM_INDEX_HASH;
-  if (!hash) {
-    if (srcSlots_dev) return set_error(ITM_ERR_INVALID, "scene resample: a slot list with dense scenes");
-  } else if (srcSlots_dev && n < 0) return set_error(ITM_ERR_INVALID, "scene resample: negative slot count");
-  { const int rc = enter_scene(dst, nullptr); if (rc) return rc; }
-  { const int rc = enter_scene(src, nullptr); if (rc) return rc; }
-  if (dst->aheadRs) return set_error(ITM_ERR_INVALID, "scene resample: dst holds the block requests of a frame issued ahead (itm_cancel_ahead first)");
   hipStream_t st = as_stream(stream);
   itm_resample_stats out{};
   VolumeView from = make_volume(src);
-  if (!hash) {
-    const int rc = dispatch_voxel(dst->cfg.voxelType, [&](auto vx) {
-      using VX = decltype(vx);
-      resample_dense_kernel<VX><<<4096, 256, 0, st>>>(from, *q, dst->vba, dst->cfg.denseSize[0], dst->cfg.denseSize[1], dst->cfg.denseSize[2], dst->cfg.denseOffset[0],
-                                                      dst->cfg.denseOffset[1], dst->cfg.denseOffset[2], dst->prm.maxW);
-      return ITM_OK;
+  if (!hash)
+    return finish_dense(dst, out, &itm_resample_stats::resampled, stats, [&](auto vx) {
+      resample_dense_kernel<decltype(vx)><<<4096, 256, 0, st>>>(from, *q, dst->vba, dst->cfg.denseSize[0], dst->cfg.denseSize[1], dst->cfg.denseSize[2], dst->cfg.denseOffset[0],
+                                                                dst->cfg.denseOffset[1], dst->cfg.denseOffset[2], dst->prm.maxW);
     });
-    if (rc) return rc;
-    ITM_LAUNCH_CHECK();
-    out.considered = out.resampled = 1;
-    if (stats) *stats = out;
-    return ITM_OK;
-  }
 
-  // The scratch of a call, kept with dst: tallies | chunkCnt[dst chunks] | chunkCount[src chunks] | sel[S] | cnt[S] | where[N] | list[N] | C[N].
-  // N is known after the count pass: a buffer that has to grow loses its contents, so the count pass then runs once more.
-  const size_t S = (size_t)src->noTotalEntries;
-  const int srcChunks = (int)((S + kSweepChunk - 1) / kSweepChunk);
-  const size_t oStats = 0, oChunk = align256(kMsCount * 4), oCount = oChunk + align256((size_t)dst->numChunks * 8), oSel = oCount + align256((size_t)srcChunks * 4),
-               oCnt = oSel + align256(S), oWhere = oCnt + align256(S);
-  MergePlacement pl;
-  pl.st = st;
+  // The scratch of a call, kept with dst (scene_ops.h: ResampleArena).  The tail is sized by N, the candidates, known after the count
+  // pass: a buffer that has to grow loses its contents, so the count pass then runs once more.
+  const int srcChunks = (src->noTotalEntries + kSweepChunk - 1) / kSweepChunk;
+  ResampleArena a(kMsCount, (size_t)dst->numChunks, (size_t)srcChunks, (size_t)src->noTotalEntries);
+  MergePlacement pl{nullptr, st};
   size_t N = 0;
-  uint8_t* base = nullptr;
+  void* base = nullptr;
   for (int pass = 0;; ++pass) {
-    const size_t need = oWhere + 2 * align256(N * 4) + align256(N * 16);
+    const size_t need = a.size_tail(N);
     const bool kept = pass > 0 && dst->mergeScratch.get() && need <= dst->mergeScratch.capacity();
     if (kept) break;
     ITM_HIP(dst->mergeScratch.reserve(need));
-    base = (uint8_t*)dst->mergeScratch.get();
-    pl.dStats = (int32_t*)(base + oStats);
-    uint8_t* sel = srcSlots_dev ? base + oSel : nullptr;
+    base = dst->mergeScratch.get();
+    pl.dStats = a.stats.at(base);
+    uint8_t* sel = srcSlots_dev ? a.sel.at(base) : nullptr;
     ITM_HIP(hipMemsetAsync(pl.dStats, 0, kMsCount * 4, st));
-    if (sel) {
-      ITM_HIP(hipMemsetAsync(sel, 0, S, st));
-      if (n > 0) {
-        merge_mark_kernel<<<(n + 255) / 256, 256, 0, st>>>(srcSlots_dev, n, src->noTotalEntries, sel, pl.dStats);
-        ITM_LAUNCH_CHECK();
-      }
-    }
-    resample_count_kernel<<<srcChunks, 256, 0, st>>>(src->hash, src->noTotalEntries, sel, *q, base + oCnt, (int32_t*)(base + oCount), pl.dStats);
+    if (sel) { const int rc = mark_slots(srcSlots_dev, n, src->noTotalEntries, sel, pl.dStats, st); if (rc) return rc; }
+    // (the count pass runs in the same round trip as the mark)
+    resample_count_kernel<<<srcChunks, 256, 0, st>>>(src->hash, src->noTotalEntries, sel, *q, a.cnt.at(base), a.chunkCount.at(base), pl.dStats);
     ITM_LAUNCH_CHECK();
     { const int rc = pl.read_stats(); if (rc) return rc; }
-    if (pl.h[kMsBadSlot]) return set_error(ITM_ERR_INVALID, "scene resample: a slot of the list is outside src's table");      // dst is untouched
+    { const int rc = refuse_bad_slots(pl.h, "scene resample"); if (rc) return rc; }      // dst is untouched
     N = (size_t)pl.h[kMsRsCandidates];
   }
   out.considered = pl.h[kMsRsParticipants]; out.srcWithoutBlock = pl.h[kMsRsNoBlock]; out.outOfRange = pl.h[kMsRsOutOfRange]; out.candidates = (int32_t)N;
@@ -453,35 +426,18 @@ int itm_scene_resample(itm_scene* dst, const itm_scene* src, const itm_rigid_q* 
       o[i] = (int)((v >> 30) >> 3);
     }
   });
-  if (N == 0) {
-    out.rounds = 1;      // (the one round that finds no request)
-    if (stats) *stats = out;
-    return ITM_OK;
-  }
-  pl.where = (int32_t*)(base + oWhere); pl.list = (int32_t*)(base + oWhere + align256(N * 4));
-  uint4* cand = (uint4*)(base + oWhere + 2 * align256(N * 4));
-  resample_fill_kernel<<<srcChunks, 256, 0, st>>>(src->hash, src->noTotalEntries, *q, base + oCnt, (const int32_t*)(base + oCount), srcChunks, (int)N, cand);
+  if (N == 0) { out.rounds = 1; if (stats) *stats = out; return ITM_OK; }      // (the one round that finds no request)
+  pl.where = a.where.at(base); pl.list = a.list.at(base);
+  uint4* cand = a.cand.at<uint4>(base);
+  resample_fill_kernel<<<srcChunks, 256, 0, st>>>(src->hash, src->noTotalEntries, *q, a.cnt.at(base), a.chunkCount.at(base), srcChunks, (int)N, cand);
   ITM_LAUNCH_CHECK();
-  { const int rc = place_positions<0>(dst, cand, (int)N, nullptr, (int2*)(base + oChunk), st, pl); if (rc) return rc; }
-  out.rounds = pl.rounds; out.allocated = pl.allocated; out.unserved = pl.unserved;
-  claim_blocks_kernel<<<((int)N + 255) / 256, 256, 0, st>>>((int)N, pl.where, dst->hash, dst->numVoxels, dst->allocKey, pl.list, pl.dStats);
-  ITM_LAUNCH_CHECK();
-  { const int rc = pl.read_stats(); if (rc) return rc; }
-  const int32_t* h = pl.h;
-  out.alreadyPresent = h[kMsPresentFirst]; out.resampled = h[kMsCombined]; out.dstSwappedOut = h[kMsDstSwappedOut];
-  if (h[kMsListCount] > 0) {
-    const int count = h[kMsListCount];
-    const int rc = dispatch_voxel(dst->cfg.voxelType, [&](auto vx) {
-      using VX = decltype(vx);
-      resample_block_kernel<VX, ITM_RESAMPLE_STAGED != 0><<<count, 512, 0, st>>>(pl.list, from, src->noTotalEntries, src->numVoxels, *q, dst->hash, dst->vba, dst->numVoxels, dst->prm.maxW, dst->allocKey,
-                                                       accel_writer(dst));
-      return ITM_OK;
-    });
-    if (rc) return rc;
-    ITM_LAUNCH_CHECK();
-  }
-  if (stats) *stats = out;
-  return ITM_OK;
+  { const int rc = place_positions<0>(dst, cand, (int)N, nullptr, a.chunkCnt.at<int2>(base), st, pl); if (rc) return rc; }
+  return finish_placed(dst, pl, out, &itm_resample_stats::resampled, stats,
+      [&] { claim_blocks_kernel<<<((int)N + 255) / 256, 256, 0, st>>>((int)N, pl.where, dst->hash, dst->numVoxels, dst->allocKey, pl.list, pl.dStats); },
+      [&](auto vx, int count) {
+        resample_block_kernel<decltype(vx), ITM_RESAMPLE_STAGED != 0><<<count, 512, 0, st>>>(pl.list, from, src->noTotalEntries, src->numVoxels, *q, dst->hash, dst->vba, dst->numVoxels,
+                                                                                             dst->prm.maxW, dst->allocKey, accel_writer(dst));
+      });
 }
 
 }  // extern "C"
