@@ -311,6 +311,59 @@ int ITM_FN(process_frame_ahead)(itm_scene* scene, const itm_view* view, const it
  * right after its "previous list -> 3" loop (CPU :160-161) -- so that any allocation may follow.  itm_reset_scene cancels by itself. */
 int ITM_FN(cancel_ahead)(itm_scene* scene, itm_render_state* rs, itm_stream stream);
 
+/* ---- frame de-integration: takes one fused depth frame back out of the TSDF ------------------------------------------------------
+ * Not a reference operation: the reference can fuse a frame and cannot un-fuse it.  A host whose poses are corrected after the fact
+ * (a loop closure, a batch optimisation, a pose verdict that turned out wrong) removes the frame's contribution with this call and
+ * fuses it again under the new pose with the two calls above ("A pose update").
+ *
+ * The call visits exactly the voxels itm_integrate_into_scene visits for the same arguments: in a hash scene the blocks on the render
+ * state's visible list with ptr >= 0, in a dense scene the whole array.  How the list got there is the caller's business:
+ * itm_find_visible_blocks for the old pose, itm_allocate_scene_from_depth(..., onlyUpdateVisibleList = 1, ...), or the list as saved
+ * when the frame was fused, uploaded again (ITM_BUF_VISIBLE_IDS + itm_set_counters).
+ *
+ * Per voxel (tests/defusion_terms.py transcribes this; the kernels reproduce it bit for bit).  The projection, the depth pixel, eta
+ * and the exit eta < -mu are those of computeUpdatedVoxelDepthInfo, operation for operation: a voxel the integration would not write
+ * is not touched.  stopIntegratingAtMaxW is not consulted (keepSaturated below stands for it).  For a voxel the integration would
+ * write, with oldW = w_depth, oldF = SDF_valueToFloat(sdf), obs = MIN(1, eta / mu):
+ *   oldW == 0                        untouched; counted in `unobserved`
+ *   oldW >= maxW and keepSaturated   untouched, colour included; counted in `saturated` (its true count of observations is unknown)
+ *   oldW == 1                        sdf = SDF_initialValue(), w_depth = 0; counted in `reset`
+ *   otherwise                        F' = ((float)oldW * oldF - obs) / (float)(oldW - 1): product, difference and quotient each rounded
+ *                                    once, IEEE division, nothing contracted; F' = MAX(-1, MIN(1, F')) with the reference's macros, a
+ *                                    changed value counted in `clamped` (removing an observation that was never added can leave
+ *                                    [-1, 1], which the short encoding cannot hold); sdf = SDF_floatToValue(F'), w_depth = oldW - 1.
+ *                                    A saturated voxel without keepSaturated is treated as a count of oldW.
+ *   `touched` counts the voxels whose depth part was written (the last two rows).
+ * Colour voxel types: the gate is the integration's -- !(eta > mu || fabs(eta / mu) > 0.25) with the eta the depth part returned (-1
+ * where it left early), then the colour image's bounds -- and a voxel kept as saturated above is skipped.  With oldWc = w_color,
+ * m = the bilinear colour / 255, oc = clr / 255:  oldWc == 0, or oldWc >= (uchar)maxW with keepSaturated: untouched;  oldWc == 1:
+ * clr = 0, w_color = 0 (`colourReset`);  otherwise c' = (oc * oldWc - m) / (oldWc - 1) per channel, x = c' * 255 rounded half away from
+ * zero and clamped to [0, 255], w_color = oldWc - 1.  `coloured` counts the voxels whose colour part was written (resets included).
+ *
+ * cfg == NULL: keepSaturated = stopIntegratingAtMaxW of the scene.  keepSaturated is 0 or 1.
+ * stats (host, may be NULL): integer sums, independent of order.  blocks: visible-list entries with a block (0 in a dense scene);
+ * visited: voxels visited.  With `stats` the call synchronises `stream` once, at its end; without it nothing is read back.
+ *
+ * What the operation is NOT.  It is the exact inverse in the weights below saturation, and in the sdf only up to the stored encoding:
+ * fuse-then-unfuse returns a short sdf within 4 steps of 1 / 32767 and a float sdf within 2^-20 (tests/test_defusion_terms.py derives
+ * both), and colours within the rounding of a uchar times the weight.  A weight that was capped at maxW has forgotten how many
+ * observations it stands for.  A block allocated AFTER the frame was fused but inside that frame's frustum and band loses an
+ * observation it never got; a caller that minds passes the frame's saved visible list.
+ *
+ * Refusals, all before any launch, each ITM_ERR_INVALID with the scene unchanged: everything itm_integrate_into_scene refuses (a NULL
+ * argument, a NULL depth image, a render state of another scene, colour voxels without an rgb image); keepSaturated outside {0, 1}.
+ * Calls recorded for the fused frame (itm_scene_set_deferred_fusion) are launched first, as for every entry point naming the scene. */
+typedef struct itm_deintegrate_config {
+  int32_t keepSaturated;        /* 1: a voxel whose weight has reached maxW stays as it is */
+  int32_t reserved[3];
+} itm_deintegrate_config;       /* 16 bytes */
+typedef struct itm_deintegrate_stats {
+  int32_t blocks, visited, touched, reset, unobserved, saturated, clamped, coloured, colourReset;
+  int32_t reserved[7];
+} itm_deintegrate_stats;        /* 64 bytes */
+int ITM_FN(deintegrate_from_scene)(itm_scene* scene, const itm_view* view, itm_render_state* rs, const itm_deintegrate_config* cfg,
+                                   itm_deintegrate_stats* stats, itm_stream stream);
+
 /* ---- view builder (the step before the path) -------------------------------- */
 /* convertDepthAffineToFloat  DeviceAgnostic/ITMViewBuilder.h:22-28 */
 int ITM_FN(convert_depth_affine)(const int16_t* raw, float* depth_out, int w, int h, float a,

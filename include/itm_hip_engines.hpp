@@ -237,6 +237,14 @@ class ITMSceneReconstructionEngine_HIP {
     itm_view v = make_view(view, trackingState);
     check(itm_integrate_into_scene(scene->handle, &v, renderState->handle, stream), "IntegrateIntoScene");
   }
+  // Not in the reference interface: takes the frame `view`, fused under trackingState->pose_d, back out of the voxels that
+  // renderState's visible list names (itm_deintegrate_from_scene; a dense scene: every voxel).  cfg == nullptr: a voxel whose weight
+  // has reached maxW stays as it is exactly when the scene stops integrating there.  With `stats` the stream is synchronised.
+  void DeintegrateFromScene(ITMScene<TVoxel, TIndex>* scene, const ITMView* view, const ITMTrackingState* trackingState,
+                            const ITMRenderState* renderState, const itm_deintegrate_config* cfg = nullptr, itm_deintegrate_stats* stats = nullptr) {
+    itm_view v = make_view(view, trackingState);
+    check(itm_deintegrate_from_scene(scene->handle, &v, renderState->handle, cfg, stats, stream), "DeintegrateFromScene");
+  }
 };
 
 // ITMVisualisationEngine_HIP: the IITMVisualisationEngine methods
@@ -895,6 +903,7 @@ class ITMMainEngine_HIP {
   ITMScene<TVoxel, TIndex>* coarseScene = nullptr;
   itm_mesh* coarseMesh = nullptr;
   ITMRenderState* renderState_freeview = nullptr;      // created by the first free-camera GetImage
+  ITMRenderState* renderState_poseUpdate = nullptr;    // created by the first RemoveFrame / ReintegrateFrame: the visible list of the frame being moved
   void* depthImageBuf = nullptr;                       // device uchar4 of the depth size: the coloured depth / uncertainty image of GetImage
   ITMRelocaliser_HIP* relocaliser = nullptr;           // settings.useRelocalisation
   bool harvestingActive = true;
@@ -961,6 +970,7 @@ class ITMMainEngine_HIP {
     itm_mesh_destroy(exportMesh);
     itm_mesh_destroy(coarseMesh); delete coarseScene;
     delete renderState_freeview; itm_dev_free(depthImageBuf);
+    delete renderState_poseUpdate;
     delete renderState_live; delete trackingController; delete tracker; delete depthTracker; delete colourTracker; delete renTracker; delete wicpTracker; delete viewBuilder;
     for (void* p : {depthBuf, scratchBuf, normalBuf, sigmaBuf, pointsBuf, coloursBuf}) itm_dev_free(p);
   }
@@ -1012,6 +1022,30 @@ class ITMMainEngine_HIP {
   // The distance transform of a box of the fused volume (ITMDistanceFieldEngine_HIP; device pointers)
   void DistanceField(const itm_esdf_box& box, const itm_esdf_out& out, int sites = ITM_ESDF_SITE_SURFACE, int minWeight = 1, int maxDistance = 0) const {
     ITMDistanceFieldEngine_HIP<TVoxel, TIndex>().Compute(&scene, box, out, sites, minWeight, maxDistance);
+  }
+  // A pose update (a loop closure, a batch optimisation): `frame` -- its images still on the device -- was fused under oldPose and is
+  // taken back out of the scene: the visible blocks under oldPose are found through a render state of the engine's own that nothing
+  // else uses, then de-integrated (itm_deintegrate_from_scene has the definition and what the operation is not).  The engine's tracking
+  // pose, its live render state and its maps stay as they were.  With `stats` the stream is synchronised.
+  void RemoveFrame(const ITMView* frame, const ITMPose& pose, itm_deintegrate_stats* stats = nullptr) {
+    ITMRenderState* rs = PoseUpdateRenderState(frame);
+    ITMTrackingState at;
+    at.pose_d = pose;
+    visualisationEngine.FindVisibleBlocks(&at.pose_d, &frame->calib.intrinsics_d, rs);
+    ITMSceneReconstructionEngine_HIP<TVoxel, TIndex>().DeintegrateFromScene(&scene, frame, &at, rs, nullptr, stats);
+  }
+  // ... and fused again under newPose: RemoveFrame, then AllocateSceneFromDepth and IntegrateIntoScene as ProcessFrame issues them, through
+  // the same render state.  Everything is enqueued when the call returns (the frame's images may be reused).  The blocks the new pose
+  // allocates reach the live visible list with the next ProcessFrame that sees them.
+  void ReintegrateFrame(const ITMView* frame, const ITMPose& oldPose, const ITMPose& newPose, itm_deintegrate_stats* stats = nullptr) {
+    RemoveFrame(frame, oldPose, stats);
+    ITMRenderState* rs = PoseUpdateRenderState(frame);
+    ITMTrackingState at;
+    at.pose_d = newPose;
+    ITMSceneReconstructionEngine_HIP<TVoxel, TIndex> reco;
+    reco.AllocateSceneFromDepth(&scene, frame, &at, rs);
+    reco.IntegrateIntoScene(&scene, frame, &at, rs);
+    check(itm_flush(scene.handle, rs->handle, nullptr), "ReintegrateFrame (flush)");
   }
   ITMRenderState* GetRenderState() { return renderState_live; }
   const ITMVisualisationEngine_HIP<TVoxel, TIndex>* GetVisualisationEngine() const { return &visualisationEngine; }
@@ -1086,6 +1120,15 @@ class ITMMainEngine_HIP {
   }
 
  private:
+  // the render state of RemoveFrame / ReintegrateFrame, of the frame's depth size
+  ITMRenderState* PoseUpdateRenderState(const ITMView* frame) {
+    if (renderState_poseUpdate && (renderState_poseUpdate->imgSize.x != frame->depthSize.x || renderState_poseUpdate->imgSize.y != frame->depthSize.y)) {
+      delete renderState_poseUpdate;
+      renderState_poseUpdate = nullptr;
+    }
+    if (!renderState_poseUpdate) renderState_poseUpdate = visualisationEngine.CreateRenderState(frame->depthSize);
+    return renderState_poseUpdate;
+  }
   // the live visible list rebuilt for pose_d
   void FindVisibleBlocksAtPose() {
     if (settings.trackerType == ITMLibSettings::TRACKER_COLOR) {      // the live render state is the colour camera's (Prepare)

@@ -242,6 +242,20 @@ class PruneStats(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
 
 
+class DeintegrateConfig(C.Structure):
+    """itm_deintegrate_config (include/itm_hip.h, itm_deintegrate_from_scene): 16 bytes."""
+    _fields_ = [("keepSaturated", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class DeintegrateStats(C.Structure):
+    """itm_deintegrate_stats (include/itm_hip.h, itm_deintegrate_from_scene): 64 bytes."""
+    _fields_ = [(n, C.c_int32) for n in ("blocks", "visited", "touched", "reset", "unobserved", "saturated", "clamped", "coloured", "colourReset")] + \
+               [("reserved", C.c_int32 * 7)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
 class CoarsenStats(C.Structure):
     """itm_coarsen_stats (include/itm_hip.h, itm_scene_coarsen)."""
     _fields_ = [(n, C.c_int32) for n in ("rounds", "considered", "alreadyPresent", "allocated", "written", "unserved",
@@ -589,6 +603,8 @@ _HOST_IO_SIGS = {
     "depth_to_uchar4": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     "weight_to_uchar4": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     "normal_to_uchar4": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
+    # frame de-integration (product only: the reference cannot un-fuse a frame)
+    "deintegrate_from_scene": (C.c_int, [_P, C.POINTER(ViewStruct), _P, C.POINTER(DeintegrateConfig), C.POINTER(DeintegrateStats), _P]),
     # scene merge (product only: no reference engine merges scenes)
     "scene_merge": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(MergeStats), _P]),
     "prune_default_config": (C.c_int, [C.POINTER(PruneConfig)]),
@@ -1102,6 +1118,20 @@ class Scene:
         return {"directory_cells": int(c.directory_cells), "slot_directory_cells": int(c.slot_directory_cells), "mirror_blocks": int(c.mirror_blocks),
                 "page_counter": int(c.page_counter), "mirror_form": ("none", "dense", "paged")[c.mirror_form], "has_directory": bool(c.has_directory),
                 "page_table": table}
+
+    def deintegrate(self, view: View, rs: "RenderState", keep_saturated=None, stats=False, stream=None):
+        """itm_deintegrate_from_scene: takes the depth (and colour) frame `view` back out of the voxels `rs`'s visible list names (a dense
+        scene: every voxel).  keep_saturated: None (the scene's stopIntegratingAtMaxW), False or True.  With `stats` the counts come back
+        as a dict and `stream` is synchronised; without, nothing is read back and None is returned."""
+        vs = view if isinstance(view, ViewStruct) else view.struct()
+        cfg = None
+        if keep_saturated is not None:
+            cfg = DeintegrateConfig()
+            cfg.keepSaturated = keep_saturated if isinstance(keep_saturated, int) and not isinstance(keep_saturated, bool) else int(bool(keep_saturated))
+        out = DeintegrateStats() if stats else None
+        self.be.check(self.be.fn["deintegrate_from_scene"](_P(self.h), C.byref(vs), _P(rs.h if rs is not None else None), (C.byref(cfg) if cfg is not None else None),
+                                                           (C.byref(out) if out is not None else None), _P(stream)), "deintegrate_from_scene")
+        return out.as_dict() if out is not None else None
 
     def process_frame(self, view: View, rs: "RenderState", points: DevBuffer, normals: DevBuffer, stream=None):
         """ITMDenseMapper::ProcessFrame + ITMTrackingController::Prepare (Engine/ITMMainEngine.cpp:123-126)."""

@@ -191,6 +191,138 @@ __device__ inline void fuse_colour(typename VX::Reg& r, float mx, float my, floa
   r = VX::with_color(r, nc, (int)newW);
 }
 
+// ---- the inverse update (itm_deintegrate_from_scene, deintegrate.hip; include/itm_hip.h states the definition) -------------------------
+// What became of one voxel, as bits: the statistics are counts of them.
+enum : uint32_t { kUnfuseTouched = 1u, kUnfuseReset = 2u, kUnfuseUnobserved = 4u, kUnfuseSaturated = 8u, kUnfuseClamped = 16u,
+                  kUnfuseColoured = 32u, kUnfuseColourReset = 64u };
+
+// Kept as it is by keepSaturated: the voxel may have absorbed any number of observations since its weight reached maxW.
+template <class VX>
+__device__ inline bool unfuse_kept(const typename VX::Reg& r, const FuseParams& p, int keepSaturated) {
+  const int w = VX::w_depth(r);
+  return keepSaturated && w != 0 && w >= p.maxW;      // (weight 0 is "unobserved" whatever maxW is)
+}
+
+// fuse_average backwards: the observation obs = MIN(1, eta / mu) leaves the running average of a voxel that is not unfuse_kept.
+// Returns the kUnfuse* bits of the depth part.
+template <class VX>
+__device__ inline uint32_t unfuse_average(typename VX::Reg& r, float obs) {
+  const int oldW = VX::w_depth(r);
+  if (oldW == 0) return kUnfuseUnobserved;
+  if (oldW == 1) {
+    r = VX::with_depth(r, 1.0f, 0);      // SDF_initialValue(): 32767 / 1.0f
+    return kUnfuseTouched | kUnfuseReset;
+  }
+  const float oldF = VX::to_float(VX::raw_sdf(r));
+  float f = (float)oldW * oldF;
+  f = f - obs;
+  const float w = (float)(oldW - 1);
+#if ITM_FAST_DIVISIONS
+  // oldW - 1 is an integer in [1, 254]: inside the set fuse_average divides by, for which the refined reciprocal is RN(1 / w) (tested)
+  f = div_markstein(f, w, refined_rcp(w));
+#else
+  f /= w;
+#endif
+  // removing an observation that was never added can leave [-1, 1], which the short encoding cannot hold
+  const float c = (1.0f < f) ? 1.0f : f;        // MIN(1.0f, f)
+  const float g = (-1.0f < c) ? c : -1.0f;      // MAX(-1.0f, c)
+  const uint32_t clamped = (g != f) ? kUnfuseClamped : 0u;
+  r = VX::with_depth(r, g, oldW - 1);
+  return kUnfuseTouched | clamped;
+}
+
+// Stage 2 of the depth part, the exits of fuse_depth_update operation for operation.  Returns eta (or -1 when the voxel is not touched).
+template <class VX>
+__device__ inline float unfuse_depth_update(typename VX::Reg& r, float dm, float pcz, const FuseParams& p, uint32_t& what) {
+  if (dm <= 0.0f) return -1;
+  const float eta = dm - pcz;
+  if (eta < -p.mu) return eta;
+#if ITM_FAST_DIVISIONS
+  float obs = p.muFast ? div_markstein(eta, p.mu, p.rcpMu) : eta / p.mu;
+#else
+  float obs = eta / p.mu;
+#endif
+  obs = (1.0f < obs) ? 1.0f : obs;
+  what |= unfuse_average<VX>(r, obs);
+  return eta;
+}
+
+// fuse_colour backwards: the projection, the image bounds and the bilinear colour are fuse_colour's, operation for operation.
+// Returns the kUnfuse* bits of the colour part.
+template <class VX>
+__device__ inline uint32_t unfuse_colour(typename VX::Reg& r, float mx, float my, float mz, const uchar4* __restrict__ rgb, const FuseParams& p, int keepSaturated) {
+  int oc[3], owc;
+  VX::get_color(r, oc, owc);
+  if (owc == 0 || (keepSaturated && owc >= (p.maxW & 0xff))) return 0u;
+  Vec3 pc = transform_point(p.M_rgb, mx, my, mz);
+  float u, v;
+#if ITM_FAST_DIVISIONS
+  if (pc.z >= 1e-4f && pc.z <= 1e4f) {
+    const float rz = refined_rcp(pc.z);
+    u = div_by_rcp(p.fxc * pc.x, pc.z, rz) + p.cxc;
+    v = div_by_rcp(p.fyc * pc.y, pc.z, rz) + p.cyc;
+  } else
+#endif
+  {
+    u = p.fxc * pc.x / pc.z + p.cxc;
+    v = p.fyc * pc.y / pc.z + p.cyc;
+  }
+  if ((u < 1) || (u > p.Wc - 2) || (v < 1) || (v > p.Hc - 2)) return 0u;
+  int nc[3] = {0, 0, 0};
+  if (owc == 1) {
+    r = VX::with_color(r, nc, 0);
+    return kUnfuseColoured | kUnfuseColourReset;
+  }
+  const int px = (int)floorf(u), py = (int)floorf(v);
+  const float dx = u - (float)px, dy = v - (float)py;
+  const uchar4* __restrict__ row = rgb + (size_t)py * p.Wc + px;
+  const uchar4 A = row[0], B = row[1], C = row[p.Wc], D = row[p.Wc + 1];      // (all four taps: see fuse_colour)
+  const float a4[3] = {(float)A.x, (float)A.y, (float)A.z}, b4[3] = {(float)B.x, (float)B.y, (float)B.z};
+  const float c4[3] = {(float)C.x, (float)C.y, (float)C.z}, d4[3] = {(float)D.x, (float)D.y, (float)D.z};
+  const float oldW = (float)owc, newW = oldW - 1.0f;      // newW: an integer in [1, 254]
+#if ITM_FAST_DIVISIONS
+  const float r255 = 1.0f / 255.0f;
+  const float rW = refined_rcp(newW);
+#endif
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    float m = (a4[k] * (1.0f - dx) * (1.0f - dy) + b4[k] * dx * (1.0f - dy) + c4[k] * (1.0f - dx) * dy + d4[k] * dx * dy);
+#if ITM_FAST_DIVISIONS
+    m = div_markstein(m, 255.0f, r255);
+    float c = div_markstein((float)oc[k], 255.0f, r255) * oldW;
+    c = c - m;
+    c = div_markstein(c, newW, rW);
+#else
+    m = m / 255.0f;
+    float c = ((float)oc[k] / 255.0f) * oldW;
+    c = c - m;
+    c /= newW;
+#endif
+    int vi = (int)round_half_away(c * 255.0f);
+    vi = (vi < 255) ? vi : 255;
+    nc[k] = (0 < vi) ? vi : 0;
+  }
+  r = VX::with_color(r, nc, owc - 1);
+  return kUnfuseColoured;
+}
+
+// One voxel whole (the dense kernel; the hash kernel stages the same calls over the slices of an item).  Returns the kUnfuse* bits.
+template <class VX>
+__device__ inline uint32_t unfuse_voxel(typename VX::Reg& r, float mx, float my, float mz, const float* __restrict__ depth,
+                                        const uchar4* __restrict__ rgb, const FuseParams& p, int keepSaturated) {
+  float pcz;
+  const int pix = fuse_depth_project(mx, my, mz, p, pcz);
+  const float dm = (pix >= 0) ? depth[pix] : 0.0f;
+  // (a kept voxel is skipped altogether, colour included; it counts where the depth part would have written it)
+  if (unfuse_kept<VX>(r, p, keepSaturated)) return (dm <= 0.0f || dm - pcz < -p.mu) ? 0u : kUnfuseSaturated;
+  uint32_t what = 0u;
+  const float eta = (pix >= 0) ? unfuse_depth_update<VX>(r, dm, pcz, p, what) : -1.0f;
+  if constexpr (VX::kColor) {
+    if (in_colour_band(eta, p)) what |= unfuse_colour<VX>(r, mx, my, mz, rgb, p, keepSaturated);
+  }
+  return what;
+}
+
 template <class VX>
 __device__ inline bool fuse_voxel(typename VX::Reg& r, float mx, float my, float mz, const float* __restrict__ depth,
                                   const uchar4* __restrict__ rgb, const FuseParams& p) {

@@ -122,6 +122,8 @@ struct itm_scene {
   itm::DeviceBuffer<void> mergeScratch;
   // itm_scene_prune (prune.hip): per-call scratch, kept between calls
   itm::DeviceBuffer<void> pruneScratch;
+  // itm_deintegrate_from_scene (deintegrate.hip): the statistics' words and their striped copies, allocated by the first call that asks for them
+  itm::DeviceBuffer<int32_t> deintegrateStats;
 };
 
 struct itm_render_state {
