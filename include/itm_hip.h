@@ -673,7 +673,9 @@ int ITM_FN(mesh_scene)(const itm_scene* scene, itm_mesh* mesh, itm_stream stream
  * writers serve the result.  The per-brick buffers belong to the mesh and are allocated by the first call on a dense scene.  Three
  * launches, no host round trip.  itm_mesh_scene itself stays empty for dense scenes, as in the reference. */
 int ITM_FN(mesh_volume)(const itm_scene* scene, itm_mesh* mesh, itm_stream stream);
-/* mesh->noTotalTriangles / noMaxTriangles / the triangle buffer; synchronises `stream`.  Any output pointer may be NULL. */
+/* mesh->noTotalTriangles / noMaxTriangles / the triangle buffer; synchronises `stream`.  Any output pointer may be NULL.  The buffer's
+ * address is fixed for the life of the mesh unless itm_mesh_update is used: an update that copies kept runs writes a second buffer and
+ * the two change places, so ask again after every itm_mesh_update. */
 int ITM_FN(mesh_info)(const itm_mesh* mesh, uint32_t* noTotalTriangles, uint32_t* noMaxTriangles,
                       const float** triangles, itm_stream stream);
 /* copies min(noTotalTriangles, capacity) triangles (9 floats each) to host memory; synchronises `stream` */
@@ -838,6 +840,87 @@ typedef struct itm_mesh_smooth_stats {
  * voxelSize not finite or not > 0: ITM_ERR_INVALID. */
 int ITM_FN(mesh_smooth_default_config)(float voxelSize, itm_mesh_smooth_config* out);
 int ITM_FN(mesh_smooth)(itm_mesh* mesh, const itm_mesh_smooth_config* cfg, itm_mesh_smooth_stats* stats, itm_stream stream);
+/* Incremental mesh: the triangle buffer follows the scene at the cost of the blocks a frame touched (the reference has none; defined in
+ * terms of MeshScene, hash scenes only).
+ * RUN TABLE, kept with the mesh: for every slot s that MeshScene listed (ptr >= 0, ascending) the block position pos_s it held then, the
+ * first triangle of its run and the run's length.  It exists after a successful itm_mesh_scene on a hash scene (which records it: one
+ * more launch, its results do not change) and after a successful itm_mesh_update; it is CURRENT only while the buffer is exactly what
+ * those calls left and only if all generated triangles fitted (generated <= noMaxTriangles - 1).  itm_mesh_filter_components (once it
+ * rewrites), itm_mesh_smooth (steps > 0) and itm_mesh_volume on a dense scene make it stale.
+ * MARKS, kept with the mesh: a set of table slots, and the word "everything".  itm_mesh_touch adds to them, itm_mesh_update clears them.
+ *
+ * itm_mesh_touch(mesh, scene, rs, slots_dev, n): the blocks that were rewritten since the mesh was last brought up to date.
+ *   rs != NULL          the slots visibleEntryIDs[0 .. noVisibleEntries) of the render state are marked -- a fused frame writes exactly
+ *                       these blocks.  The count is read on the device.
+ *   slots_dev != NULL   the n >= 0 table slots in device memory are marked.
+ *   both NULL, n == -1  everything is marked: the next update is a full one.
+ *   Both lists may be given in one call.  A value outside the table ([0, noTotalEntries)) is ignored and counted (ignoredMarks of the
+ *   next update).  Recorded engine calls of the scene and of rs are launched first (the visible list is final only then); the call then
+ *   only enqueues work on `stream` and does not synchronise.  Marks accumulate over any number of calls.
+ *   Refusals (ITM_ERR_INVALID, the reason in itm_last_error, nothing changed): a NULL mesh or scene; a scene other than the mesh's; a
+ *   dense scene; a render state of another scene; n < 0 with a list, or both NULL with n != -1.
+ *
+ * itm_mesh_update(scene, mesh, stats): brings the buffer up to date.  Sequential definition:
+ *   0. Recorded calls are launched.  The call IS itm_mesh_scene (cap behaviour included) in three cases, stats->full naming which:
+ *      ITM_MESH_UPDATE_NO_RUN_TABLE the run table is not current, ITM_MESH_UPDATE_ALL_MARKED everything is marked,
+ *      ITM_MESH_UPDATE_OVERFLOW the triangles of step 5 number more than noMaxTriangles - 1.  Otherwise full = 0 and:
+ *   1. A' = the slots with ptr >= 0 now, ascending; A = the run table's slots.  APPEARED: s in A' that is not in A or holds another
+ *      position than pos_s.  VANISHED: s in A that is not in A' (swapped out, ptr == -1, included) or now holds another position.
+ *   2. Seeds P = the present positions of the marked slots that are in A'  u  the positions of the appeared  u  the old positions of
+ *      the vanished.
+ *   3. Dirty D = { s in A' : pos_s + d in P for some d in {0, 1}^3 }: the cells of a block read its own voxels and one layer of the seven
+ *      blocks at +d, and a missing corner kills a cell, so these are exactly the blocks whose cells can differ.
+ *   4. Every s in D gets the triangles of MeshScene's loop over that block as the scene is now; every s in A' \ D keeps its old run,
+ *      copied bit for bit.
+ *   5. The buffer is the runs in ascending slot order, zero behind them; noTotalTriangles is their sum.  The run table is rewritten for A'.
+ *   6. Delta (itm_mesh_update_info / itm_mesh_download_update): `changed` = D in ascending slot order, each {slot, pos, first triangle,
+ *      count} in the NEW buffer; `removed` = {old slot, old position} of the vanished whose old position no entry of A' holds now, in
+ *      ascending old slot order.  After a full path `changed` lists every listed block (runs as generated: with a full buffer the
+ *      triangles from noMaxTriangles - 1 on are not in it) and `removed` is what steps 1-2 found, empty where the run table was not current.
+ *   7. The marks are cleared.  The soup's attributes, the index, the indexed attributes and the components are stale, as after
+ *      itm_mesh_scene.  The buffer's DEVICE POINTER may change (ask itm_mesh_info again): the copy of step 4 needs a second buffer of
+ *      noMaxTriangles triangles, allocated by the first update that copies; the two change places.
+ * PROPERTY: if every block whose stored sdf changed since the run table was made is marked or has appeared, the buffer after the call
+ * equals a fresh itm_mesh_scene's bit for bit, order included.  Presence changes are found by the call itself, so itm_scene_prune,
+ * swapping out and new allocations need no touch; a fused or de-integrated frame needs its render state; itm_scene_merge / _resample,
+ * uploads and itm_scene_load change voxels in place and need their slots, or n == -1.
+ * stats (may be NULL): full; allocated = |A'|; marked = distinct marked slots inside the table; ignoredMarks; appeared; vanished (both 0
+ * where the run table was not current); remeshed = |D| and kept = |A' \ D| (allocated and 0 after a full path); trianglesBefore / After =
+ * noTotalTriangles; trianglesCopied / Generated = the triangles of the kept / re-meshed runs; noChanged, noRemoved = the delta's lengths.
+ * The call synchronises `stream` once to read the totals, which also decides the overflow fall-back (that path synchronises once more).
+ * MI355X: one pass over the table (presence diff, eight slot-directory look-ups per seed), ordered compactions, marching cubes over D
+ * only (the kernels of itm_mesh_scene on a list), a carry scan over A', one dword-granular coalesced copy of the kept runs.
+ * Refusals as itm_mesh_touch.  A call that fails on the device leaves the run table stale: the next update is a full one. */
+#define ITM_MESH_UPDATE_NO_RUN_TABLE 1
+#define ITM_MESH_UPDATE_ALL_MARKED 2
+#define ITM_MESH_UPDATE_OVERFLOW 3
+typedef struct itm_mesh_update_stats {
+  int32_t full, allocated, marked, ignoredMarks, appeared, vanished, remeshed, kept;
+  uint32_t trianglesBefore, trianglesAfter, trianglesCopied, trianglesGenerated;
+  uint32_t noChanged, noRemoved, reserved[2];
+} itm_mesh_update_stats;   /* 64 bytes */
+typedef struct itm_mesh_changed_block {
+  int32_t slot;            /* table slot */
+  int16_t pos[3];          /* block position */
+  int16_t reserved;        /* 0 */
+  uint32_t firstTriangle, noTriangles;
+} itm_mesh_changed_block;  /* 20 bytes */
+typedef struct itm_mesh_removed_block {
+  int32_t slot;            /* the table slot it held */
+  int16_t pos[3];
+  int16_t reserved;        /* 0 */
+} itm_mesh_removed_block;  /* 12 bytes */
+int ITM_FN(mesh_touch)(itm_mesh* mesh, const itm_scene* scene, const itm_render_state* rs, const int32_t* slots_dev, int n, itm_stream stream);
+int ITM_FN(mesh_update)(const itm_scene* scene, itm_mesh* mesh, itm_mesh_update_stats* stats, itm_stream stream);
+/* the delta of the last itm_mesh_update: its lengths and device arrays (NULL where empty; owned by the mesh, rewritten by the next
+ * update).  Any output pointer may be NULL.  No update since the mesh was created: ITM_ERR_INVALID.  Does not synchronise: the arrays
+ * were complete when the update returned. */
+int ITM_FN(mesh_update_info)(const itm_mesh* mesh, uint32_t* noChanged, uint32_t* noRemoved, const itm_mesh_changed_block** changed,
+                             const itm_mesh_removed_block** removed, itm_stream stream);
+/* copies min(count, capacity) entries of each array to host memory; any pointer may be NULL.  Synchronises `stream`. */
+int ITM_FN(mesh_download_update)(const itm_mesh* mesh, itm_mesh_changed_block* changed_host, uint32_t capacityChanged,
+                                 itm_mesh_removed_block* removed_host, uint32_t capacityRemoved, uint32_t* noChanged, uint32_t* noRemoved,
+                                 itm_stream stream);
 
 /* ---- multi-stream exchange (BASELINE configs[3]) ------------------------------------------------------------------
  * One depth stream per GPU; fusion needs no collective.  Per frame every rank publishes the record of itm_export_visible_record

@@ -163,6 +163,10 @@ struct ITMLibSettings {
   // prunes its scene with pruneConfig after every N-th frame it has fused, once that frame's maps are prepared.
   int pruneEveryNFrames = 0;
   itm_prune_config pruneConfig = {ITM_PRUNE_EMPTY | ITM_PRUNE_FREE, 1.0f, 1, 1, {0, 0, 0}, {0, 0, 0}, 0, 0};      // itm_prune_default_config
+  // Live mesh (itm_mesh_touch / itm_mesh_update; the reference meshes on request only).  0 (default): none, and no code path changes.
+  // N > 0: ITMMainEngine_HIP (hash scenes) owns a mesh that follows its scene: every fused frame marks the blocks it wrote, and after
+  // every N-th fused frame, once that frame's maps are prepared, the marked blocks are re-meshed (GetLiveMesh, GetLastMeshUpdateStats).
+  int liveMeshEveryNFrames = 0;
 };
 
 struct ITMSceneParams : itm_scene_params {
@@ -916,6 +920,9 @@ class ITMMainEngine_HIP {
   int fusionDelay = 0, relocalisationCount = 0;
   int fusedSincePrune = 0;         // settings.pruneEveryNFrames
   itm_prune_stats lastPrune = {};
+  itm_mesh* liveMesh = nullptr;    // settings.liveMeshEveryNFrames
+  int fusedSinceMeshUpdate = 0;
+  itm_mesh_update_stats lastMeshUpdate = {};
 
  public:
   // calibType / c0 / c1: ITMDisparityCalib (0 = TRAFO_KINECT, 1 = TRAFO_AFFINE); sizes as ITMMainEngine's imgSize_rgb / imgSize_d
@@ -963,11 +970,13 @@ class ITMMainEngine_HIP {
       relocaliser = new ITMRelocaliser_HIP(imgSize_d, Vector2f{params.viewFrustum_min, params.viewFrustum_max}, settings.relocHarvestingThreshold, 500, 4,
                                            settings.relocCapacity);
     if (settings.useTrackingVerdict) poseQuality = new ITMPoseQuality_HIP(params.mu, settings.poseQuality);
+    if (settings.liveMeshEveryNFrames > 0 && TIndex::kType == ITM_INDEX_HASH) check(itm_mesh_create(scene.handle, 0, &liveMesh), "itm_mesh_create (live mesh)");
   }
   ~ITMMainEngine_HIP() {
     delete poseQuality;
     delete relocaliser;
     itm_mesh_destroy(exportMesh);
+    itm_mesh_destroy(liveMesh);
     itm_mesh_destroy(coarseMesh); delete coarseScene;
     delete renderState_freeview; itm_dev_free(depthImageBuf);
     delete renderState_poseUpdate;
@@ -990,6 +999,7 @@ class ITMMainEngine_HIP {
   // states and `other` stay as they are: the merged blocks are seen by the next ProcessFrame whose view holds them.
   void MergeSceneFrom(const ITMMainEngine_HIP& other, itm_merge_stats* stats = nullptr) {
     ITMSceneMergeEngine_HIP<TVoxel, TIndex>().MergeScene(&scene, &other.scene, nullptr, stats);
+    TouchLiveMeshEverywhere();
   }
   // Returns the blocks of this engine's scene that `cfg` selects (nullptr: settings.pruneConfig) to the pool (itm_scene_prune).  The
   // live render state's visible list loses them; tracking state and maps stay as they are.
@@ -998,10 +1008,21 @@ class ITMMainEngine_HIP {
     if (stats) *stats = lastPrune;
   }
   const itm_prune_stats& GetLastPruneStats() const { return lastPrune; }      // of the last PruneScene, by the host or by pruneEveryNFrames
+  // The live mesh (settings.liveMeshEveryNFrames; nullptr without it or for a dense scene): the mesh of the scene as of the last update.
+  // Every fused frame, RemoveFrame and ReintegrateFrame mark the blocks they wrote, MergeSceneFrom marks everything, PruneScene needs no
+  // mark (itm_mesh_update finds the blocks that are gone).  UpdateLiveMesh brings it up to date now, whatever the frame count says.
+  itm_mesh* GetLiveMesh() { return liveMesh; }
+  const itm_mesh_update_stats& GetLastMeshUpdateStats() const { return lastMeshUpdate; }
+  void UpdateLiveMesh() {
+    if (!liveMesh) return;
+    fusedSinceMeshUpdate = 0;
+    check(itm_mesh_update(scene.handle, liveMesh, &lastMeshUpdate, nullptr), "UpdateLiveMesh");
+  }
   // The same for an `other` that lives in a frame of its own: thisFromOther maps its world to this engine's (x_this = thisFromOther
   // x_other, metres).  The scene of `other` is resampled at this scene's voxels and fused (itm_scene_resample).
   void MergeSceneFrom(const ITMMainEngine_HIP& other, const Matrix4f& thisFromOther, itm_resample_stats* stats = nullptr) {
     ITMSceneResampleEngine_HIP<TVoxel, TIndex>().ResampleScene(&scene, &other.scene, thisFromOther, nullptr, stats);
+    TouchLiveMeshEverywhere();
   }
   // Refines thisFromOther (the coarse pose on entry, the refined one on return) by registering the band voxels of `other`'s scene
   // against this engine's scene (ITMSceneAlignEngine_HIP); its natural use is followed by MergeSceneFrom(other, thisFromOther).  Neither
@@ -1033,6 +1054,7 @@ class ITMMainEngine_HIP {
     at.pose_d = pose;
     visualisationEngine.FindVisibleBlocks(&at.pose_d, &frame->calib.intrinsics_d, rs);
     ITMSceneReconstructionEngine_HIP<TVoxel, TIndex>().DeintegrateFromScene(&scene, frame, &at, rs, nullptr, stats);
+    TouchLiveMesh(rs);
   }
   // ... and fused again under newPose: RemoveFrame, then AllocateSceneFromDepth and IntegrateIntoScene as ProcessFrame issues them, through
   // the same render state.  Everything is enqueued when the call returns (the frame's images may be reused).  The blocks the new pose
@@ -1046,6 +1068,7 @@ class ITMMainEngine_HIP {
     reco.AllocateSceneFromDepth(&scene, frame, &at, rs);
     reco.IntegrateIntoScene(&scene, frame, &at, rs);
     check(itm_flush(scene.handle, rs->handle, nullptr), "ReintegrateFrame (flush)");
+    TouchLiveMesh(rs);
   }
   ITMRenderState* GetRenderState() { return renderState_live; }
   const ITMVisualisationEngine_HIP<TVoxel, TIndex>* GetVisualisationEngine() const { return &visualisationEngine; }
@@ -1091,7 +1114,7 @@ class ITMMainEngine_HIP {
       int nearest; float distance;
       relocaliser->ProcessFrame(view.depth, &trackingState.pose_d, 1, &nearest, &distance, true);
     }
-    if (fusionActive) PruneIfDue();
+    if (fusionActive) { TouchLiveMesh(renderState_live); PruneIfDue(); UpdateLiveMeshIfDue(); }
   }
 
   // settings.pruneEveryNFrames: after the frame's maps are prepared, so that the recorded frame is launched as one fused frame as ever
@@ -1099,6 +1122,18 @@ class ITMMainEngine_HIP {
     if (settings.pruneEveryNFrames <= 0 || ++fusedSincePrune < settings.pruneEveryNFrames) return;
     fusedSincePrune = 0;
     PruneScene();
+  }
+  // settings.liveMeshEveryNFrames: the blocks a frame wrote are those of its render state's visible list; the update runs where the
+  // pruning does, after the frame's maps are prepared, so that the recorded frame is launched as one fused frame as ever
+  void TouchLiveMesh(const ITMRenderState* rs) {
+    if (liveMesh) check(itm_mesh_touch(liveMesh, scene.handle, rs->handle, nullptr, 0, nullptr), "TouchLiveMesh");
+  }
+  void TouchLiveMeshEverywhere() {
+    if (liveMesh) check(itm_mesh_touch(liveMesh, scene.handle, nullptr, nullptr, -1, nullptr), "TouchLiveMesh (everything)");
+  }
+  void UpdateLiveMeshIfDue() {
+    if (!liveMesh || ++fusedSinceMeshUpdate < settings.liveMeshEveryNFrames) return;
+    UpdateLiveMesh();
   }
 
  public:
@@ -1190,7 +1225,7 @@ class ITMMainEngine_HIP {
         relocaliser->ProcessFrame(view.depth, &trackingState.pose_d, 1, &nearest, &distance, true);
       }
       if (delayed) --fusionDelay;
-      if (lastFrameFused) PruneIfDue();
+      if (lastFrameFused) { TouchLiveMesh(renderState_live); PruneIfDue(); UpdateLiveMeshIfDue(); }
     } else if (result == Q::TRACKING_POOR) {
       trackingController->Prepare(&trackingState, &view, renderState_live);
     } else {
@@ -1457,6 +1492,30 @@ class ITMMesh {
     noComponents = 0;
     return stats;
   }
+  // Incremental re-meshing (itm_mesh_touch / itm_mesh_update).  Touch marks the blocks that were rewritten since the mesh was last up to
+  // date: the visible list of a render state (what a fused frame wrote), `n` table slots in device memory, or everything.  Update
+  // (ITMMeshingEngine_HIP::UpdateMesh) re-meshes the marked blocks, those that appeared or vanished and their neighbours, and keeps every
+  // other run; triangles() may answer with another address afterwards.  Attributes, index and components are stale after it.
+  template <class TVoxel, class TIndex>
+  void Touch(const ITMScene<TVoxel, TIndex>* scene, const ITMRenderState* renderState, const int32_t* slots = nullptr, int n = 0) {
+    check(itm_mesh_touch(handle, scene->handle, renderState ? renderState->handle : nullptr, slots, n, stream), "Touch");
+  }
+  template <class TVoxel, class TIndex>
+  void TouchEverything(const ITMScene<TVoxel, TIndex>* scene) { check(itm_mesh_touch(handle, scene->handle, nullptr, nullptr, -1, stream), "Touch (everything)"); }
+  template <class TVoxel, class TIndex>
+  itm_mesh_update_stats Update(const ITMScene<TVoxel, TIndex>* scene) {
+    itm_mesh_update_stats stats;
+    check(itm_mesh_update(scene->handle, handle, &stats, stream), "Update");
+    noTotalTriangles = stats.trianglesAfter; noVertices = 0; noComponents = 0;
+    return stats;
+  }
+  // the delta of the last Update on the host: the re-meshed blocks with their runs, the blocks that are gone
+  void DownloadUpdate(std::vector<itm_mesh_changed_block>& changed, std::vector<itm_mesh_removed_block>& removed) const {
+    uint32_t nc = 0, nr = 0;
+    check(itm_mesh_update_info(handle, &nc, &nr, nullptr, nullptr, stream), "itm_mesh_update_info");
+    changed.resize(nc); removed.resize(nr);
+    check(itm_mesh_download_update(handle, changed.data(), nc, removed.data(), nr, nullptr, nullptr, stream), "DownloadUpdate");
+  }
 };
 
 // ITMMeshingEngine<TVoxel,TIndex>::MeshScene (Engine/ITMMeshingEngine.h:19-26)
@@ -1472,6 +1531,14 @@ class ITMMeshingEngine_HIP {
   void MeshVolume(ITMMesh* mesh, const ITMScene<TVoxel, TIndex>* scene) {
     check(itm_mesh_volume(scene->handle, mesh->handle, stream), "MeshVolume");
     check(itm_mesh_info(mesh->handle, &mesh->noTotalTriangles, nullptr, nullptr, stream), "itm_mesh_info");
+  }
+  // beyond the reference: itm_mesh_update -- MeshScene at the cost of the blocks that ITMMesh::Touch marked (hash scenes)
+  itm_mesh_update_stats UpdateMesh(ITMMesh* mesh, const ITMScene<TVoxel, TIndex>* scene) {
+    const itm_stream keep = mesh->stream;
+    mesh->stream = stream;
+    const itm_mesh_update_stats stats = mesh->Update(scene);
+    mesh->stream = keep;
+    return stats;
   }
 };
 

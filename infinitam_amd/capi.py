@@ -198,6 +198,34 @@ def mesh_smooth_config(quantum, steps=20, lam=0.5, mu=-0.53, pin_irregular=True)
                             MESH_SMOOTH_PIN_IRREGULAR if pin_irregular else 0)
 
 
+MESH_UPDATE_NO_RUN_TABLE, MESH_UPDATE_ALL_MARKED, MESH_UPDATE_OVERFLOW = 1, 2, 3      # itm_mesh_update_stats::full
+
+
+class MeshUpdateStats(C.Structure):
+    """itm_mesh_update_stats (include/itm_hip.h, itm_mesh_update): 64 bytes."""
+    _fields_ = ([(n, C.c_int32) for n in ("full", "allocated", "marked", "ignoredMarks", "appeared", "vanished", "remeshed", "kept")] +
+                [(n, C.c_uint32) for n in ("trianglesBefore", "trianglesAfter", "trianglesCopied", "trianglesGenerated", "noChanged", "noRemoved")] +
+                [("reserved", C.c_uint32 * 2)])
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
+class MeshChangedBlock(C.Structure):
+    """itm_mesh_changed_block (include/itm_hip.h, itm_mesh_update): 20 bytes."""
+    _fields_ = [("slot", C.c_int32), ("pos", C.c_int16 * 3), ("reserved", C.c_int16), ("firstTriangle", C.c_uint32), ("noTriangles", C.c_uint32)]
+
+
+class MeshRemovedBlock(C.Structure):
+    """itm_mesh_removed_block (include/itm_hip.h, itm_mesh_update): 12 bytes."""
+    _fields_ = [("slot", C.c_int32), ("pos", C.c_int16 * 3), ("reserved", C.c_int16)]
+
+
+# the same records as numpy dtypes (Mesh.update_delta)
+MESH_CHANGED_DTYPE = np.dtype([("slot", np.int32), ("pos", np.int16, 3), ("reserved", np.int16), ("firstTriangle", np.uint32), ("noTriangles", np.uint32)])
+MESH_REMOVED_DTYPE = np.dtype([("slot", np.int32), ("pos", np.int16, 3), ("reserved", np.int16)])
+
+
 class MergeStats(C.Structure):
     """itm_merge_stats (include/itm_hip.h, itm_scene_merge)."""
     _fields_ = [(n, C.c_int32) for n in ("rounds", "considered", "alreadyPresent", "allocated", "combined", "unserved",
@@ -599,6 +627,11 @@ _HOST_IO_SIGS = {
     "debug_mesh_smooth": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, C.POINTER(MeshSmoothConfig), _P, _P, C.POINTER(MeshSmoothStats), _P]),
     # the mesh of either index type: dense volumes brick by brick (product only: the reference's dense MeshScene is empty)
     "mesh_volume": (C.c_int, [_P, _P, _P]),
+    # incremental mesh: re-mesh the blocks a frame touched, keep the other runs (product only)
+    "mesh_touch": (C.c_int, [_P, _P, _P, _P, C.c_int, _P]),
+    "mesh_update": (C.c_int, [_P, _P, C.POINTER(MeshUpdateStats), _P]),
+    "mesh_update_info": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(_P), C.POINTER(_P), _P]),
+    "mesh_download_update": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _P]),
     # colour maps of the display path (product only: host loops in the reference, Engine/ITMVisualisationEngine.cpp:7-107)
     "depth_to_uchar4": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     "weight_to_uchar4": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
@@ -1574,6 +1607,43 @@ class Mesh:
         stats = MeshSmoothStats()
         be.check(be.fn["mesh_smooth"](_P(self.h), C.byref(cfg), C.byref(stats), _P(stream)), "mesh_smooth")
         return stats.as_dict()
+
+    def Touch(self, rs: Optional["RenderState"] = None, slots=None, everything: bool = False, stream=None):
+        """itm_mesh_touch: marks the blocks that were rewritten since the mesh was last up to date -- the visible list of `rs` (what a
+        fused frame wrote), the table slots `slots` (a DevBuffer of int32 or a numpy array, uploaded first), or everything.  Marks
+        accumulate until Update consumes them."""
+        be = self.scene.be
+        if everything:
+            be.check(be.fn["mesh_touch"](_P(self.h), _P(self.scene.h), None, None, -1, _P(stream)), "mesh_touch")
+        if rs is None and slots is None:
+            return
+        empty = slots is not None and not isinstance(slots, DevBuffer) and np.asarray(slots).size == 0
+        ptr, n, keep = self.scene._slot_list(np.zeros(1, np.int32) if empty else slots, stream)      # an empty list is still a list: never a null pointer
+        n = 0 if empty or slots is None else n
+        rc = be.fn["mesh_touch"](_P(self.h), _P(self.scene.h), _P(rs.h if rs is not None else None), _P(ptr), n, _P(stream))
+        if keep is not None:
+            be.sync(stream)
+            keep.close()
+        be.check(rc, "mesh_touch")
+
+    def Update(self, stream=None) -> dict:
+        """itm_mesh_update: re-meshes the marked blocks, those that appeared or vanished and their -d neighbours, and keeps every other
+        run; equal to MeshScene bit for bit when every rewritten block was marked.  triangles() may live at another address afterwards.
+        Returns the statistics; "full" is 0 or the MESH_UPDATE_* reason for which the call was MeshScene."""
+        stats = MeshUpdateStats()
+        self.scene.be.check(self.scene.be.fn["mesh_update"](_P(self.scene.h), _P(self.h), C.byref(stats), _P(stream)), "mesh_update")
+        return stats.as_dict()
+
+    def update_delta(self, stream=None) -> dict:
+        """The delta of the last Update: "changed" (MESH_CHANGED_DTYPE: slot, pos, firstTriangle, noTriangles of every re-meshed block,
+        ascending slots) and "removed" (MESH_REMOVED_DTYPE: the old slot and position of the blocks that are gone)."""
+        be = self.scene.be
+        nc, nr = C.c_uint32(), C.c_uint32()
+        be.check(be.fn["mesh_update_info"](_P(self.h), C.byref(nc), C.byref(nr), None, None, _P(stream)), "mesh_update_info")
+        changed, removed = np.zeros(nc.value, MESH_CHANGED_DTYPE), np.zeros(nr.value, MESH_REMOVED_DTYPE)
+        be.check(be.fn["mesh_download_update"](_P(self.h), changed.ctypes.data_as(_P), nc.value, removed.ctypes.data_as(_P), nr.value, None, None,
+                                               _P(stream)), "mesh_download_update")
+        return {"changed": changed, "removed": removed}
 
     def close(self):
         if self.h:

@@ -77,11 +77,24 @@ struct itm_mesh {
   uint32_t noComponents = 0, componentRounds = 0;
   // scratch of itm_mesh_smooth (mesh_smooth.hip); allocated / grown by the call, sized from the counts
   itm::SmoothBuffers smooth;
+  // incremental re-meshing (mesh_update.hip; hash scenes).  The RUN TABLE: per table slot {px | py << 16, pz | listed << 16, first
+  // triangle, triangle count} of the block the slot held when the buffer was last generated, zero for a slot that was not listed.
+  // `update` holds it twice (the one an update reads, the one it writes), the marks of itm_mesh_touch, the call's flags, lists and
+  // statistics and the delta (UpdateArena); allocated with the mesh.
+  itm::DeviceBuffer<void> update;
+  int runCurrentHalf = 0;                    // which of the arena's two run tables describes the buffer
+  bool allMarked = false;                    // itm_mesh_touch(everything) since the last update
+  itm::DeviceBuffer<float> spare;            // the buffer an update writes while it copies from `triangles`; allocated by the first update that copies
+  uint32_t spareHigh = 0;                    // triangles of `spare` that may not be zero
+  int lastFull = 0;                          // the last update: its reason code, ...
+  uint32_t noChanged = 0, noRemoved = 0;     // ... and the lengths of its delta
+  bool deltaValid = false;
 
   // ---- which products describe the buffer's present contents ------------------------------------------------------------------------
   //   soup (the triangle buffer) -+- soup attributes (normals, colours)
   //                               +- index -+- indexed attributes
-  //                                         +- components
+  //                               |         +- components
+  //                               +- run table (which run of the buffer belongs to which block: itm_mesh_update)
   // A product is current once the call that computes it has succeeded (empty cases included: they need no device work) and stale from
   // the moment something above it is rewritten; a call that fails leaves its product stale.  Who rewrites what: itm_mesh_scene /
   // itm_mesh_volume and, once it starts rewriting, itm_mesh_filter_components the soup; itm_mesh_index the index; itm_mesh_components
@@ -89,8 +102,10 @@ struct itm_mesh {
   // itm_mesh_smooth moves positions and nothing else: vertices and soup are rewritten TOGETHER, through the faces, so the index goes on
   // describing the soup (vertices[faces] is the soup, first[k] names a soup vertex that holds vertices[k]) and stays current -- although
   // two distinct vertices may now hold one position, which a fresh itm_mesh_index would weld.  Everything computed FROM positions is stale.
-  void vertices_moved() { attrCurrent = 0; indexedAttrCurrent = 0; components_recomputing(); }
-  void soup_rewritten() { attrCurrent = 0; index_rebuilding(); }
+  // The run table (itm_mesh_update) describes the buffer exactly as itm_mesh_scene on a hash scene or an update left it: current once one
+  // of the two has recorded it, stale from the moment anything else writes the buffer (the filter, the smoothing, a dense volume's mesh).
+  void vertices_moved() { attrCurrent = 0; indexedAttrCurrent = 0; runCurrent = false; components_recomputing(); }
+  void soup_rewritten() { attrCurrent = 0; runCurrent = false; index_rebuilding(); }
   void soup_remeshed() { soup_rewritten(); fromVolume = false; }       // itm_mesh_scene: the buffer holds a dense volume's mesh no more
   void index_rebuilding() { indexCurrent = false; indexedAttrCurrent = 0; components_recomputing(); }
   void components_recomputing() { componentsCurrent = false; }
@@ -98,6 +113,8 @@ struct itm_mesh {
   void attributes_current(bool indexed, uint32_t what) { (indexed ? indexedAttrCurrent : attrCurrent) |= what; }
   void index_current() { indexCurrent = true; }
   void components_current() { componentsCurrent = true; }
+  void run_table_recorded() { runCurrent = true; }
+  bool run_table_current() const { return runCurrent; }
   bool holds_volume_mesh() const { return fromVolume; }
   uint32_t attributes(bool indexed) const { return indexed ? indexedAttrCurrent : attrCurrent; }   // the ITM_MESH_* bits that are current
   int require_index() const { return indexCurrent ? ITM_OK : itm::set_error(ITM_ERR_INVALID, "no index for this mesh: itm_mesh_index has not built it since the last itm_mesh_scene"); }
@@ -119,11 +136,14 @@ struct itm_mesh {
   bool indexCurrent = false;         // vertices / faces / first describe the soup
   uint32_t indexedAttrCurrent = 0;   // ITM_MESH_* bits computed for the index
   bool componentsCurrent = false;    // the labelling describes the index
+  bool runCurrent = false;           // the run table describes the buffer (and, on the device, whether every generated triangle fitted)
 };
 
 namespace itm {
 
 int launch_mesh_volume_dense(const itm_scene* s, itm_mesh* m, hipStream_t st);   // mesh_dense.hip
+hipError_t alloc_update_arena(const itm_scene* s, itm_mesh* m);                    // mesh_update.hip: itm_mesh_create, hash scenes
+int record_run_table(const itm_scene* s, itm_mesh* m, hipStream_t st);             // mesh_update.hip: the tail of itm_mesh_scene on a hash scene
 
 // The clamped download: min(count, capacity) elements of `src` to the host, nothing where that is 0 or `dst` is null (the caller synchronises)
 inline hipError_t copy_out(void* dst, const void* src, size_t count, size_t capacity, size_t bytesPerElement, hipStream_t st) {

@@ -18,63 +18,18 @@
 //   2. mesh_scan_kernel: exclusive scan of the per-block totals (one workgroup; meshing is an export step, not a frame step).
 //   3. mesh_cells_kernel<WRITE>: the same staging, then every lane interpolates its cell's vertices with the reference's float
 //      operations and writes its triangles at base(block) + offset(cell), i.e. in the reference's order.
+// The kernels of 1-3 take any list of blocks and stand in mesh_cells.h: the frame step, itm_mesh_update (mesh_update.hip), runs them
+// over the blocks a frame touched.  For it, a fourth launch here records which run of the buffer belongs to which block.
 #include <new>
 
 #include "itm_internal.h"
-#include "mc_device.h"
+#include "mesh_cells.h"
 #include "mesh_types.h"
-#include "ordered_device.h"
-#include "wave_utils.h"
 
 namespace itm {
 
 __global__ void __launch_bounds__(256) mesh_flag_kernel(const uint4* __restrict__ hash, int nEntries, uint8_t* __restrict__ flags, int32_t* __restrict__ chunkCount) {
   flag_chunk(nEntries, flags, chunkCount, [&](int slot) { return (int)hash[slot].w >= 0; });
-}
-
-template <class VX, bool WRITE>
-__global__ void __launch_bounds__(512) mesh_cells_kernel(VolumeView vol, const int32_t* __restrict__ slots, const RenderCounters* __restrict__ lc,
-                                                         int32_t* __restrict__ blockTriangles, float* __restrict__ triangles, uint32_t maxTriangles,
-                                                         const uint32_t* __restrict__ totals, float factor) {
-  __shared__ float sdf[9 * 9 * 9];          // SDF_valueToFloat of the samples; NaN marks "no voxel stored there"
-  __shared__ int nbBase[8];
-  __shared__ int scan[9];
-  const int nBlocks = lc->noVisibleEntries;
-  const int t = threadIdx.x;
-  for (int b = blockIdx.x; b < nBlocks; b += gridDim.x) {
-    const HashEntry he = unpack_entry(vol.hash[slots[b]]);
-    __syncthreads();                          // previous block's LDS contents are no longer needed
-    if (t < 8) nbBase[t] = (t == 0) ? he.ptr * kBlockVoxels : block_base(vol, he.px + (t & 1), he.py + ((t >> 1) & 1), he.pz + (t >> 2));
-    __syncthreads();
-    for (int i = t; i < 729; i += 512) {
-      const int x = i % 9, y = (i / 9) % 9, z = i / 81;
-      const int base = nbBase[(x >> 3) | ((y >> 3) << 1) | ((z >> 3) << 2)];
-      float v = __builtin_nanf("");
-      if (base >= 0) v = VX::to_float(VX::load_raw_sdf(vol.vba, (size_t)(base + (x & 7) + ((y & 7) << 3) + ((z & 7) << 6))));
-      sdf[i] = v;
-    }
-    __syncthreads();
-    const int x = t & 7, y = (t >> 3) & 7, z = t >> 6;       // the reference's loop order: z outer, x inner == ascending t
-    const McCell cell = classify_cell(sdf, x, y, z);
-    int total;
-    const int offset = block_exclusive_scan<8>(cell.nTri, scan, &total);
-    if (!WRITE) {
-      if (t == 0) blockTriangles[b] = total;
-      continue;
-    }
-    if (cell.nTri == 0) continue;
-    emit_cell(cell, he.px * kBlockSide + x, he.py * kBlockSide + y, he.pz * kBlockSide + z, (uint64_t)(uint32_t)blockTriangles[b] + (uint64_t)offset, totals[0],
-              maxTriangles, factor, triangles);
-  }
-}
-
-// exclusive scan of the per-block triangle counts (in place) by one workgroup; totals[0] = sum, totals[1] = count after the cap
-__global__ void __launch_bounds__(1024) mesh_scan_kernel(int32_t* __restrict__ blockTriangles, const RenderCounters* __restrict__ lc,
-                                                         uint32_t* __restrict__ totals, uint32_t maxTriangles) {
-  // (prefixes < 2^32: at most 5 * 512 triangles per block, 2^18 blocks)
-  const unsigned long long generated = carry_scan<16, unsigned long long>(
-      lc->noVisibleEntries, [&](int i) { return blockTriangles[i]; }, [&](int i, unsigned long long before) { blockTriangles[i] = (int32_t)(uint32_t)before; });
-  if (threadIdx.x == 0) store_triangle_totals(totals, generated, maxTriangles);
 }
 
 // the soup on the host, with the attributes that are current where the writer carries them
@@ -111,6 +66,7 @@ int itm_mesh_create(const itm_scene* s, uint32_t maxTriangles, itm_mesh** out) {
   if (e == hipSuccess && hash) e = m->flags.alloc((size_t)s->numChunks * kSweepChunk);
   if (e == hipSuccess && hash) e = m->chunkCount.alloc((size_t)s->numChunks);
   if (e == hipSuccess && hash) e = m->listCounters.alloc(1);
+  if (e == hipSuccess && hash) e = alloc_update_arena(s, m);
   if (e == hipSuccess) e = hipMemset(m->triangles, 0, (size_t)m->maxTriangles * 36);   // MemoryBlock storage starts zeroed
   if (e != hipSuccess) { delete m; return hip_fail(e, "mesh buffers", __FILE__, __LINE__); }
   *out = m;
@@ -134,7 +90,7 @@ int itm_mesh_scene(const itm_scene* s, itm_mesh* m, itm_stream stream) {
                                       &m->listCounters->noVisibleEntries, st);
   if (rc) return rc;
   const VolumeView vol = make_volume(s);
-  const int grid = 256 * 4;
+  const int grid = kMeshCellsGrid;
   rc = dispatch_voxel(s->cfg.voxelType, [&](auto vx) {
     using VX = decltype(vx);
     mesh_cells_kernel<VX, false><<<grid, 512, 0, st>>>(vol, m->slots, m->listCounters, m->blockTriangles, m->triangles, m->maxTriangles, m->totals, s->prm.voxelSize);
@@ -144,7 +100,7 @@ int itm_mesh_scene(const itm_scene* s, itm_mesh* m, itm_stream stream) {
   });
   if (rc) return rc;
   ITM_LAUNCH_CHECK();
-  return ITM_OK;
+  return record_run_table(s, m, st);                           // (the buffer and the counts are not touched)
 }
 
 // The mesh of the scene's volume whatever its index: a hash scene as itm_mesh_scene, a dense scene brick by brick (mesh_dense.hip)
