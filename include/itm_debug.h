@@ -16,7 +16,7 @@ extern "C" {
 /* Test hooks (no effect on results): select alternative code paths so that they can be covered. */
 #define ITM_DEBUG_FORCE_GLOBAL_RANGE_ATOMICS 1 /* range image via global atomics even if it fits LDS */
 #define ITM_DEBUG_EXPLICIT_MARK_PREVIOUS 2     /* always run the separate mark-previous-list launch   */
-#define ITM_DEBUG_INTEGRATE_WORKGROUPS 3      /* tuning: persistent workgroups of the hash integration (0 = default) */
+#define ITM_DEBUG_INTEGRATE_WORKGROUPS 3      /* tuning: persistent workgroups of the hash integration (0 = default); the dense strip kernel's grid reads it too */
 #define ITM_DEBUG_NO_FUSED_PROJECTION 4       /* process_frame: keep integration and projection as two launches */
 #define ITM_DEBUG_NO_DIRECTORY 5              /* ray casting / free-view reads walk the hash table instead of the block directory */
 #define ITM_DEBUG_NO_FUSED_RANGE_REDUCE 6     /* process_frame: reduce the partial range images in their own launch, not in the ray cast */
@@ -24,11 +24,11 @@ extern "C" {
 #define ITM_DEBUG_SINGLE_PASS_RAYCAST 8       /* ray casting: every ray start to finish in one launch (no parked-ray pass) */
 #define ITM_DEBUG_DENSE_GROUP_CULL 9          /* dense integration: frustum test per 4-voxel group instead of the per-column row interval */
 #define ITM_DEBUG_TRACKER_LAUNCH_PER_EVALUATION 10 /* TrackCamera: one launch per cost evaluation instead of one resident kernel per call */
-#define ITM_DEBUG_TRACKER_HOST_COMMAND 11     /* TrackCamera session: commands through pinned host memory (set before the tracker's first call) */
+#define ITM_DEBUG_TRACKER_HOST_COMMAND 11     /* TrackCamera session: commands through pinned host memory even where the device has a large BAR (set before the tracker's first call) */
+#define ITM_DEBUG_NO_SDF_MIRROR 12            /* ray casting: voxels through the directory / table although the scene has an sdf mirror; set before itm_scene_create: no mirror is allocated */
 #define ITM_DEBUG_SEPARATE_SWEEP 13           /* AllocateSceneFromDepth: allocation sweep as its own launch, not inside the visible-list launch */
 #define ITM_DEBUG_NO_SIDE_PROJECTION 14       /* itm_process_frame on large images: projection of the visible blocks after the integration on the frame's stream, not beside it on the render state's own */
 #define ITM_DEBUG_DENSE_RANGE_REFILL 15       /* dense scenes: write the constant expected-depth image on every frame, as the reference does, although it already holds it */
-#define ITM_DEBUG_NO_SDF_MIRROR 12            /* ray casting: voxels through the directory / table although the scene has an sdf mirror; set before itm_scene_create: no mirror is allocated */
 #define ITM_DEBUG_DENSE_CLASSIFY 16            /* dense integration: 0 = 4-voxel groups classified against the depth tiles before the fetch (default), 1 = no classification, 2 = classified after the fetch, 3 = check mode (itm_debug_dense_classify_check) */
 #define ITM_DEBUG_DENSE_NO_STRIPS 17           /* dense integration: the launch shape of rounds 1-2 (four groups per lane, 131 072 short waves) instead of the strip kernel */
 #define ITM_DEBUG_TRACKER_SESSION_UNUSABLE 18  /* TrackCamera: the resident evaluation kernel reports itself unusable at the n-th evaluation of a handle (n = value): the call must finish through one launch per evaluation with the same pose */
@@ -42,7 +42,11 @@ extern "C" {
 #define ITM_DEBUG_POSE_QUALITY_ROWS 29            /* itm_pose_quality_evaluate: a wave covers 64 x 1 pixels of a row instead of an 8 x 8 tile (same counts and residual image; the sums are added in another order) */
 #define ITM_DEBUG_MESH_COMPONENTS_PER_LANE 30      /* itm_mesh_components: the statistics with one atomic per lane instead of one per wave segment (lanes of a wave that share a component aggregate first) */
 #define ITM_DEBUG_MESH_SMOOTH_SCATTER 31            /* itm_mesh_smooth: every pass as a scatter -- one lane per proper triangle adds its corners into per-vertex int64 accumulators with 64-bit integer atomics, a second kernel applies the step -- instead of the gather over the adjacency rows (same bits by construction) */
+#define ITM_DEBUG_KEY_COUNT 32                      /* every key is below it; 0 and 21-23 are not keys */
+/* itm_debug_set stores a key's value, itm_debug_get reads it back into *value (what FAIL_ALLOCATION still has to count down): every
+ * key starts at 0, EXCHANGE_CORRUPT_WORD at -1.  A number that is not a key is refused with ITM_ERR_INVALID.  Host only. */
 int ITM_FN(debug_set)(int key, int value);
+int ITM_FN(debug_get)(int key, int* value);
 /* The forward-only 32-bit counters behind the tagged granules (DESIGN.md "Forward-only counters"): reads one counter of one handle into
  * *get (may be NULL) and then, when set is not NULL, replaces it with *set -- so that a test can place a handle a few steps before the
  * roll-over that 2^32 frames of uptime would reach.  Only the number changes: no buffer is touched, no result depends on where a counter

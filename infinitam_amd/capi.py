@@ -558,6 +558,7 @@ _HOST_IO_SIGS = {
     "debug_accel_census": (C.c_int, [_P, C.POINTER(AccelCensus), _P, _P]),
     "debug_ordered_compact": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "debug_memory": (C.c_int, [_P]),
+    "debug_get": (C.c_int, [C.c_int, C.POINTER(C.c_int)]),
     "debug_counter": (C.c_int, [C.c_int, _P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "swap_integrate_global_into_local": (C.c_int, [_P, _P, _P]),
     "swap_save_to_global_memory": (C.c_int, [_P, _P, _P]),

@@ -189,31 +189,20 @@ __global__ void __launch_bounds__(kGHThreads) align_eval_kernel(VolumeView vol, 
 
 }  // namespace itm
 
-struct itm_aligner {
-  mutable std::mutex mu;
-  itm::GHChannel ch;
+struct itm_aligner : itm::GHHandle {
   const float4* samples = nullptr;      // the caller's device memory
   int n = 0;
 };
 
 namespace itm {
 
-int debug_counter_aligner(int which, void* handle, const uint32_t* set, uint32_t* get) {
-  if (which != ITM_COUNTER_ALIGN_SEQ) return -1;
-  itm_aligner* a = (itm_aligner*)handle;
-  if (!a) return set_error(ITM_ERR_INVALID, "null handle");
-  std::lock_guard<std::mutex> lock(a->mu);
-  if (get) *get = a->ch.seq;
-  if (set) a->ch.seq = *set;
-  return ITM_OK;
-}
+GHHandle* gh_handle(itm_aligner* a) { return static_cast<GHHandle*>(a); }
 
 // One pass over the handle's samples at the float pose M: cost, gradient, Hessian and the valid count.
 static int align_evaluate(itm_aligner* a, const itm_scene* s, const float M[16], const itm_align_config& cfg, itm_align_eval* out, hipStream_t st) {
   memset(out, 0, sizeof *out);
   if (a->n <= 0 || !a->samples) return ITM_OK;
-  if (a->ch.moved()) a->ch.release();
-  { const int rc = a->ch.reserve(kGHGroups); if (rc) return rc; }
+  { const int rc = a->ready([&] { a->ch.release(); }); if (rc) return rc; }
   AlignParams p;
   for (int r = 0; r < 3; ++r) {
     for (int c = 0; c < 3; ++c) p.R[3 * r + c] = M[4 * c + r];
@@ -225,16 +214,15 @@ static int align_evaluate(itm_aligner* a, const itm_scene* s, const float M[16],
   p.n = a->n;
   const int groups = std::min(kGHGroups, (a->n + kGHThreads - 1) / kGHThreads);
   const VolumeView vol = make_volume(s);
-  const unsigned int seq = a->ch.begin();
-  const int rc = dispatch_volume(s, [&](auto vx, auto dense) {
-    align_eval_kernel<decltype(vx), dense.value><<<groups, kGHThreads, 0, st>>>(vol, a->samples, p, a->ch.rec.device(), seq);
-    return ITM_OK;
-  });
-  if (rc) return rc;
-  ITM_LAUNCH_CHECK();
   double sums[kGHValues];
   int valid = 0;
-  { const int r = a->ch.collect((size_t)groups, seq, st, sums, &valid); if (r) return r; }
+  const int rc = a->evaluate((size_t)groups, st, [&](GHBlockRecord* rec, unsigned int seq) {
+    return dispatch_volume(s, [&](auto vx, auto dense) {
+      align_eval_kernel<decltype(vx), dense.value><<<groups, kGHThreads, 0, st>>>(vol, a->samples, p, rec, seq);
+      return ITM_OK;
+    });
+  }, sums, &valid);
+  if (rc) return rc;
   out->f = (float)sums[0];
   out->noValid = valid;
   unpack_gh(sums, 6, 6, 1.0f, out->nabla, out->hessian);

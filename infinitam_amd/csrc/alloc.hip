@@ -38,10 +38,6 @@
 
 namespace itm {
 
-int g_debug_explicit_mark = 0;   // test hook: always run the explicit mark-previous launch
-int g_debug_two_pass_visible_list = 0;   // test hook: count and compact as two launches
-int g_debug_separate_sweep = 0;          // test hook (key 13): the allocation sweep as its own launch
-int g_debug_force_list_stuck = 0;        // test hook (key 20): chunk n - 1 of the one-launch list behaves as if its bounded wait had expired
 
 // (When the last list build found more visible slots than the list holds -- the reference then writes past its list, SURVEY section 7
 // trap 6; list and count are clamped here -- every slot that was visible counts as "visible in the previous frame", listed or not:
@@ -675,8 +671,8 @@ int prepare_request_stage(itm_scene* s, const itm_view* v, itm_render_state* rs,
   if (rc) return rc;
   p.org = s->org;
   int2* reqCur = (int2*)s->chunkReq.get() + (size_t)(s->frameParity & 1u) * s->numChunks;
-  lazy = rs->listCoherent && !g_debug_explicit_mark;
-  ra = RequestArgs{v->depth, s->hash, rs->visibleType, s->allocKey, reqCur, s->counters, rs->range, rs->counters, g_debug_no_directory ? nullptr : s->dirSlot, (int32_t*)s->fatalHost.device()};
+  lazy = rs->listCoherent && !debug_value(ITM_DEBUG_EXPLICIT_MARK_PREVIOUS);
+  ra = RequestArgs{v->depth, s->hash, rs->visibleType, s->allocKey, reqCur, s->counters, rs->range, rs->counters, debug_value(ITM_DEBUG_NO_DIRECTORY) ? nullptr : s->dirSlot, (int32_t*)s->fatalHost.device()};
   return ITM_OK;
 }
 
@@ -754,8 +750,8 @@ int launch_sweep_stage(itm_scene* s, const itm_view* v, itm_render_state* rs, bo
   // process drives more hardware queues than the device runs at once (GPU_MAX_HW_QUEUES=8, 6 scenes) the queues are time-sliced and
   // the waits collapse the frame rate (492 frames/s against 19.2 k).  No frame of a multi-scene process contains a wait between
   // workgroups.
-  const bool onePass = !g_debug_two_pass_visible_list && (one_pass_list_is_safe(s) || g_debug_force_list_stuck != 0);      // (the test hook needs the launch that can get stuck)
-  const bool fusedSweep = !onlyVisible && onePass && !g_debug_separate_sweep && (s->cfg.bucketNum % kSweepChunk) == 0;
+  const bool onePass = !debug_value(ITM_DEBUG_TWO_PASS_VISIBLE_LIST) && (one_pass_list_is_safe(s) || debug_value(ITM_DEBUG_FORCE_LIST_STUCK) != 0);      // (the test hook needs the launch that can get stuck)
+  const bool fusedSweep = !onlyVisible && onePass && !debug_value(ITM_DEBUG_SEPARATE_SWEEP) && (s->cfg.bucketNum % kSweepChunk) == 0;
   if (!onlyVisible) {
     if (!fusedSweep) {
       KernelTimer ts(s, ITM_TK_ALLOC_SWEEP, st);
@@ -778,7 +774,7 @@ int launch_sweep_stage(itm_scene* s, const itm_view* v, itm_render_state* rs, bo
     }
     const uint32_t epoch = s->listEpoch;
     const SweepArgs sw{s->allocKey, reqNext, s->excessList, s->allocList, accel_writer(s), v->depth, lazy ? 1 : 0, s->chunkSweepDone, s->chunkKeptGran,
-                       (int32_t*)s->fatalHost.device(), fusedSweep ? g_debug_force_list_stuck - 1 : -1};
+                       (int32_t*)s->fatalHost.device(), fusedSweep ? debug_value(ITM_DEBUG_FORCE_LIST_STUCK) - 1 : -1};
 #define ITM_VL(CM, LZ, SW) visible_list_kernel<CM, LZ, SW><<<nChunks, 256, 0, st>>>(rs->visibleType, s->hash, s->chunkGran, epoch, reqCur, nChunks, s->counters, rs->visibleIds, rs->capIds, rs->counters, p, sw)
     if (onlyVisible) { if (lazy) ITM_VL(false, true, false); else ITM_VL(false, false, false); }
     else if (fusedSweep) { if (lazy) ITM_VL(true, true, true); else ITM_VL(true, false, true); }

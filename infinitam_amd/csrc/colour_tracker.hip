@@ -190,9 +190,7 @@ __global__ void __launch_bounds__(kGHThreads) colour_eval_kernel(const float4* _
 
 }  // namespace itm
 
-struct itm_colour_tracker {
-  mutable std::mutex mu;
-  itm::GHChannel ch;
+struct itm_colour_tracker : itm::GHHandle {
   itm::DeviceBuffer<void> pyramidMem;
   itm::ColourPyramid P = {};
   float intr[4] = {0, 0, 0, 0};    // intr_rgb of the last prepare
@@ -202,15 +200,7 @@ struct itm_colour_tracker {
 
 namespace itm {
 
-int debug_counter_colour_tracker(int which, void* handle, const uint32_t* set, uint32_t* get) {
-  if (which != ITM_COUNTER_COLOUR_SEQ) return -1;
-  itm_colour_tracker* t = (itm_colour_tracker*)handle;
-  if (!t) return set_error(ITM_ERR_INVALID, "null handle");
-  std::lock_guard<std::mutex> lock(t->mu);
-  if (get) *get = t->ch.seq;
-  if (set) t->ch.seq = *set;
-  return ITM_OK;
-}
+GHHandle* gh_handle(itm_colour_tracker* t) { return static_cast<GHHandle*>(t); }
 
 static void colour_release(itm_colour_tracker* t) {
   t->ch.release();
@@ -219,8 +209,7 @@ static void colour_release(itm_colour_tracker* t) {
 }
 
 static int colour_reserve(itm_colour_tracker* t, size_t pyramidBytes) {
-  if (t->ch.moved()) colour_release(t);
-  int rc = t->ch.reserve(kGHGroups);
+  const int rc = t->ready([&] { colour_release(t); });
   if (rc) return rc;
   if (!t->totalHost) {
     const hipError_t e = t->totalHost.alloc(1, hipHostMallocMapped | hipHostMallocCoherent);
@@ -286,19 +275,19 @@ static int colour_evaluate(itm_colour_tracker* t, int level, const float* locati
   p.countDev = countDev; p.countHost = countHost;
   const int np = colour_num_para(mode);
   const float4* loc = (const float4*)locations; const float4* col = (const float4*)colours;
-  const unsigned int seq = t->ch.begin();
   const dim3 grid(kGHGroups);
-  if (np == 3) {
-    if (gh) colour_eval_kernel<3, true><<<grid, kGHThreads, 0, st>>>(loc, col, p, t->ch.rec.device(), seq);
-    else colour_eval_kernel<3, false><<<grid, kGHThreads, 0, st>>>(loc, col, p, t->ch.rec.device(), seq);
-  } else {
-    if (gh) colour_eval_kernel<6, true><<<grid, kGHThreads, 0, st>>>(loc, col, p, t->ch.rec.device(), seq);
-    else colour_eval_kernel<6, false><<<grid, kGHThreads, 0, st>>>(loc, col, p, t->ch.rec.device(), seq);
-  }
-  ITM_LAUNCH_CHECK();
   double sums[kGHValues];
   int valid = 0;
-  const int rc = t->ch.collect(kGHGroups, seq, st, sums, &valid);
+  const int rc = t->evaluate(kGHGroups, st, [&](GHBlockRecord* rec, unsigned int seq) {
+    if (np == 3) {
+      if (gh) colour_eval_kernel<3, true><<<grid, kGHThreads, 0, st>>>(loc, col, p, rec, seq);
+      else colour_eval_kernel<3, false><<<grid, kGHThreads, 0, st>>>(loc, col, p, rec, seq);
+    } else {
+      if (gh) colour_eval_kernel<6, true><<<grid, kGHThreads, 0, st>>>(loc, col, p, rec, seq);
+      else colour_eval_kernel<6, false><<<grid, kGHThreads, 0, st>>>(loc, col, p, rec, seq);
+    }
+    return ITM_OK;
+  }, sums, &valid);
   if (rc) return rc;
   // the launch has finished (its records are in): the count it read is in place as well
   const int total = countDev ? *(volatile int*)t->totalHost.get() : countHost;

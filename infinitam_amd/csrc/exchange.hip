@@ -42,8 +42,6 @@
 
 namespace itm {
 
-int g_debug_exchange_device_copy = 0;     // debug key: a ONE-rank exchange replaces ncclAllGather by a device copy (read when the exchange is created)
-int g_debug_exchange_corrupt_word = -1;   // debug key: the self-check sees this word of the own block flipped (read when the exchange is created)
 
 constexpr int kRecordHeader = 17;   // 16 floats of pose + the count
 
@@ -275,7 +273,7 @@ int itm_exchange_create(int world, int rank, const unsigned char id[128], int ma
   if (e != hipSuccess) { free_exchange(x); return hip_fail(e, "exchange buffers", __FILE__, __LINE__); }
   // One code path for every world size: a single rank gets a communicator too (its id made here) and runs the same ncclAllGather
   // as eight do.  Debug key ITM_DEBUG_EXCHANGE_DEVICE_COPY replaces the one-rank collective by a device copy (a test pins both to the same table).
-  const bool deviceCopy = world == 1 && g_debug_exchange_device_copy != 0;
+  const bool deviceCopy = world == 1 && debug_value(ITM_DEBUG_EXCHANGE_DEVICE_COPY) != 0;
   if (!deviceCopy) {
     if (!rccl().ok) { free_exchange(x); return set_error(ITM_ERR_DEVICE, "librccl.so could not be loaded"); }
     ncclUniqueId u;
@@ -292,7 +290,7 @@ int itm_exchange_create(int world, int rank, const unsigned char id[128], int ma
     if (!(sc && sc[0] == '0')) {
       if (x->check.alloc(1, hipHostMallocMapped | hipHostMallocCoherent, true) != hipSuccess) (void)hipGetLastError();
     }
-    x->corruptWord = g_debug_exchange_corrupt_word;
+    x->corruptWord = debug_value(ITM_DEBUG_EXCHANGE_CORRUPT_WORD);
   }
   x->issuer = std::thread(issuer_main, x);
   *out = x;

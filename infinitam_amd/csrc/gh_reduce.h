@@ -8,6 +8,7 @@
 
 #include <chrono>
 #include <cstring>
+#include <mutex>
 
 #include "itm_internal.h"
 #include "wave_utils.h"
@@ -208,6 +209,43 @@ struct GHChannel {
     return collect_records(rec, blocks, tag, st, sums, n);
   }
 };
+
+// What every handle that owns a channel begins with: the mutex that serialises its callers, the channel, and the host frame of an
+// evaluation that is ONE launch.  The order of the steps is the contract of the tagged records: the tag is taken before the launch
+// that sends it, and the host waits for exactly as many records as workgroups were launched.
+struct GHHandle {
+  mutable std::mutex mu;
+  GHChannel ch;
+
+  // Records for `blocks` workgroups on the current device; `release` (the handle's own: the channel and whatever else it holds on a
+  // device) runs first when the handle's memory is that of another device.
+  template <class Release>
+  int ready(Release&& release, size_t blocks = kGHGroups) {
+    if (ch.moved()) release();
+    return ch.reserve(blocks);
+  }
+  // launch(records, tag) starts `groups` workgroups on st, each of which sends one record with that tag, and returns ITM_OK or an
+  // error of its own; sums / *valid receive the records' values and counts, added in the common order.
+  template <class Launch>
+  int evaluate(size_t groups, hipStream_t st, Launch&& launch, double sums[kGHValues], int* valid) {
+    const unsigned int seq = ch.begin();
+    { const int rc = launch(ch.rec.device(), seq); if (rc) return rc; }
+    ITM_LAUNCH_CHECK();
+    return ch.collect(groups, seq, st, sums, valid);
+  }
+  // itm_debug_counter's view of ch.seq: *get receives it, then *set replaces it
+  int seq_counter(const uint32_t* set, uint32_t* get) {
+    std::lock_guard<std::mutex> lock(mu);
+    if (get) *get = ch.seq;
+    if (set) ch.seq = *set;
+    return ITM_OK;
+  }
+};
+// the handle types as their base, each converted where the type is complete (the compiler checks the conversion); null stays null
+GHHandle* gh_handle(itm_colour_tracker* t);            // colour_tracker.hip
+GHHandle* gh_handle(itm_ren_tracker* t);               // ren_tracker.hip
+GHHandle* gh_handle(itm_pose_quality_handle* q);       // pose_quality.hip
+GHHandle* gh_handle(itm_aligner* a);                   // align.hip
 
 // The gradient nabla[0..np) and the symmetric Hessian hessian[r + c * ld] (column-major) from the sums, each times `scale`.
 // Scale 1 stores the bits of the plain (float) conversion: multiplying by 1.0f is exact.

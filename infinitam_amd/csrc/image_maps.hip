@@ -203,11 +203,10 @@ static int acquire_limits(hipStream_t st, ImageLimits** words, uint32_t* epoch) 
   return ITM_OK;
 }
 
-int debug_counter_image_maps(int which, void* handle, const uint32_t* set, uint32_t* get) {
-  if (which != ITM_COUNTER_IMAGE_MAP_EPOCH) return -1;
+int image_map_counter(itm_stream stream, const uint32_t* set, uint32_t* get) {
   std::lock_guard<std::mutex> lock(g_slotMutex);
   LimitSlot* slot = nullptr;
-  { const int rc = find_slot(as_stream((itm_stream)handle), &slot); if (rc) return rc; }
+  { const int rc = find_slot(as_stream(stream), &slot); if (rc) return rc; }
   if (get) *get = slot->epoch;
   if (set) slot->epoch = *set;
   return ITM_OK;

@@ -20,8 +20,6 @@ namespace itm {
 #ifndef ITM_MIRROR_FLOAT_TYPES
 #define ITM_MIRROR_FLOAT_TYPES 0     // (scene.hip decides whether a float scene gets a mirror; the same switch must be given to both files)
 #endif
-int g_debug_integrate_wgs = 0;      // (the dense strip kernel's grid reads it too)
-int g_debug_no_fused_projection = 0;
 
 // Work item = kSlices consecutive z-slices of one visible block, done by ONE WAVE: lane <-> (x, y), one 64-voxel run per slice.
 // The persistent waves stride over the items (item i = block i / (8 / kSlices), slice group i % (8 / kSlices)), so the waves of a
@@ -271,7 +269,7 @@ int launch_integrate(itm_scene* s, const itm_view* v, itm_render_state* rs, hipS
     // 1024: 19.5-19.8 us, 1536: 19.4-19.8, 2048: 19.0-19.5, 3072: 18.9-19.8, 8192: 18.2-19.6; 1280 x 960 colour (55.8 k blocks) 1024: 193 us,
     // 2048: 178, 3072: 174, 4096: 173-174, 6144: 172-173, 8192: 171 -- the number of visible blocks is not known on the host (nothing is read
     // back), the image size stands in for it
-    const int grid = g_debug_integrate_wgs > 0 ? g_debug_integrate_wgs : ((size_t)rs->w * rs->h > (size_t)640 * 480 ? 8192 : 2048);
+    const int grid = debug_value(ITM_DEBUG_INTEGRATE_WORKGROUPS) > 0 ? debug_value(ITM_DEBUG_INTEGRATE_WORKGROUPS) : ((size_t)rs->w * rs->h > (size_t)640 * 480 ? 8192 : 2048);
     ProjParams pp;
     const int RW = (rs->w + 7) / 8, RH = (rs->h + 7) / 8;
     if (fuseProjection) {

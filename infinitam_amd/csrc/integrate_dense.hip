@@ -13,9 +13,6 @@
 
 namespace itm {
 
-int g_debug_dense_group_cull = 0;   // debug key 9: per-group frustum test instead of the per-column row interval
-int g_debug_dense_no_strips = 0;    // debug key 17: the launch shape of rounds 1-2 (four groups per lane) instead of the strip kernel
-int g_debug_dense_classify = 0;     // debug key 16: 0 = classify groups before the fetch, 1 = no classification, 2 = after the fetch, 3 = check mode
 
 // Dense volume, generic voxel type: one voxel per lane, x fastest (coalesced).
 template <class VX>
@@ -558,28 +555,29 @@ int launch_integrate_dense(itm_scene* s, const itm_view* v, const FuseParams& p,
       return ITM_OK;
     });
   }
+  const int noStrips = debug_value(ITM_DEBUG_DENSE_NO_STRIPS), classifyMode = debug_value(ITM_DEBUG_DENSE_CLASSIFY);      // debug keys 17 and 16
   const int sx4 = sz[0] / 4;
   int lg = 0; while ((1 << lg) < sx4) ++lg;
   const bool pow2 = (1 << lg) == sx4;
   const int plane = sx4 * sz[1];
   int splits = (plane + 2 * 256 - 1) / (2 * 256);        // every lane gets ~2 groups per pass
   if (splits > 64) splits = 64;
-  if (g_debug_dense_no_strips > 1) splits = g_debug_dense_no_strips;      // measurement: debug key 17 = n > 1 sets the number of splits of a slice
+  if (noStrips > 1) splits = noStrips;      // measurement: debug key 17 = n > 1 sets the number of splits of a slice
   if (splits < 1) splits = 1;
   ColumnCull cc;
-  const bool planes = !g_debug_dense_group_cull && make_column_cull(p, sz, of, cc);
+  const bool planes = !debug_value(ITM_DEBUG_DENSE_GROUP_CULL) && make_column_cull(p, sz, of, cc);
   const bool columns = pow2 && ((splits * 256) % sx4) == 0 && planes;
   GroupClassify gc;
   memset(&gc, 0, sizeof gc);
   int classify = 0;
-  const bool wantStrips = planes && !g_debug_dense_no_strips && g_debug_dense_classify != 1 && g_debug_dense_classify != 3 && sz[1] < (1 << 24);
-  if (planes && g_debug_dense_classify != 1) {
+  const bool wantStrips = planes && !noStrips && classifyMode != 1 && classifyMode != 3 && sz[1] < (1 << 24);
+  if (planes && classifyMode != 1) {
     // min / max depth tiles of this frame (one small launch), then groups are classified against them
     const TileLevels tl = tile_levels(v->w, v->h);
     if (s->depthTiles.reserve((size_t)tl.total) != hipSuccess) (void)hipGetLastError();
     if (s->depthTiles && make_group_classify(p, sz, of, s->depthTiles, tl, gc, wantStrips ? 4 : 1)) {
       depth_tiles_kernel<<<dim3((v->w + 63) / 64, (v->h + 63) / 64), 256, 0, st>>>(v->depth, v->w, v->h, s->depthTiles, tl);
-      classify = g_debug_dense_classify == 2 ? 2 : g_debug_dense_classify == 3 ? 3 : 1;
+      classify = classifyMode == 2 ? 2 : classifyMode == 3 ? 3 : 1;
     }
   }
   KernelTimer tk(s, ITM_TK_INTEGRATE, st);
@@ -587,7 +585,7 @@ int launch_integrate_dense(itm_scene* s, const itm_view* v, const FuseParams& p,
   if (wantStrips && classify != 0) {
     // 16 384 waves for the 16 384 items of a 512^3 volume: one item each, dispatched as slots free up (measured, BASELINE configs[2]:
     // 1 024 workgroups 102-110 us, 2 048: 95-104, 3 072: 93-107, 4 096: 91-105)
-    const int wgs = g_debug_integrate_wgs > 0 ? g_debug_integrate_wgs : 4096;
+    const int wgs = debug_value(ITM_DEBUG_INTEGRATE_WORKGROUPS) > 0 ? debug_value(ITM_DEBUG_INTEGRATE_WORKGROUPS) : 4096;
     integrate_dense_strip_kernel<<<wgs, 256, 0, st>>>((uint4*)s->vba.get(), v->depth, p, sz[0], sz[1], sz[2], of[0], of[1], of[2], cc, gc);
   } else {
     dense_x4_kernel(pow2, columns, classify)<<<dim3(splits, sz[2]), 256, 0, st>>>((uint4*)s->vba.get(), v->depth, p, sz[0], sz[1], sz[2], of[0], of[1], of[2], lg, cc, gc);

@@ -11,6 +11,7 @@
 #include "itm_types.h"
 #include "accel_device.h"
 #include "device_memory.h"
+#include "debug.h"
 
 namespace itm {
 
@@ -214,7 +215,53 @@ inline int dispatch_voxel(int voxelType, F&& f) {
 inline bool voxel_is_float(int voxelType) { return voxelType == ITM_VOXEL_F || voxelType == ITM_VOXEL_F_RGB; }
 inline bool voxel_has_colour(int voxelType) { return voxelType == ITM_VOXEL_S_RGB || voxelType == ITM_VOXEL_F_RGB; }
 
-// ---- pending work of the entry points (pending.hip) --------------------------------------------------------------------------------
+// ---- scene.hip -------------------------------------------------------------------------------------------------------------------------
+int rebuild_sdf_mirror(itm_scene* s, hipStream_t st);
+// Foreign voxel bytes on their way into a HASH scene (buffer upload, checkpoint load, the checkpoint's cached blocks): ITM_ERR_INVALID, naming
+// the voxel, when one of the n voxels holds the sdf word that the sdf mirror keeps for "no block here" (MirrorCodec::kAbsent,
+// accel_device.h); `what` says where the bytes come from.  Dense scenes have no mirror and take any word.  Host memory, host only.
+int refuse_absent_sdf_words(const itm_scene* s, const void* voxels_host, size_t n, const char* what);
+int live_hash_scenes(int device);                                     // hash scenes alive on a device
+std::vector<itm_render_state*> render_states_of(const itm_scene* s);  // the render states registered with a scene, copied under the registry's lock
+int accel_unfill(itm_scene* s, hipStream_t st);                      // empties the cubes through the table that filled them
+int accel_place(itm_scene* s, const float* invM, hipStream_t st);    // (re-)places the cubes around a view
+int accel_rebuild(itm_scene* s, hipStream_t st);       // occupancy bitmap, both directories and the sdf mirror, from the table
+AccelWriter accel_writer(const itm_scene* s);          // the scene's derived structures as kernels write them (accel_device.h)
+
+// ---- alloc.hip -------------------------------------------------------------------------------------------------------------------------
+int launch_request_stage(itm_scene* s, const itm_view* v, itm_render_state* rs, bool onlyVisible, bool fuseRangeInit, hipStream_t st);
+int launch_sweep_stage(itm_scene* s, const itm_view* v, itm_render_state* rs, bool onlyVisible, hipStream_t st);
+int launch_allocate(itm_scene* s, const itm_view* v, itm_render_state* rs, bool onlyVisible, bool fuseRangeInit, hipStream_t st);
+int validate_allocate(const itm_scene* s, const itm_view* v, const itm_render_state* rs, bool onlyVisible);
+int cancel_ahead(itm_scene* s, itm_render_state* rs, hipStream_t st);
+int launch_find_visible(const itm_scene* s, const float* M, const float* intr, itm_render_state* rs, hipStream_t st);
+
+// ---- integrate.hip, integrate_dense.hip ------------------------------------------------------------------------------------------------
+int validate_integrate(const itm_scene* s, const itm_view* v);
+int launch_integrate(itm_scene* s, const itm_view* v, itm_render_state* rs, hipStream_t st, bool fuseProjection = false);
+struct FuseParams;                                     // fuse_device.h
+int launch_integrate_dense(itm_scene* s, const itm_view* v, const FuseParams& p, hipStream_t st);   // integrate_dense.hip: the dense half of launch_integrate
+
+// ---- visualise.hip, visualise_aux.hip --------------------------------------------------------------------------------------------------
+bool can_fuse_projection(const itm_scene* s, const itm_render_state* rs);
+int launch_expected_depths(const itm_scene* s, const float* M, const float* intr, itm_render_state* rs, bool rangeAlreadyInit, hipStream_t st, bool projected = false);
+int launch_raycast(const itm_scene* s, const float* invM, const float* intr, itm_render_state* rs, float4* dst, hipStream_t st, bool reduceRange = false);
+int launch_icp_maps(const itm_scene* s, const itm_view* v, itm_render_state* rs, float4* points, float4* normals, hipStream_t st, bool reduceRange = false,
+                    itm_scene* sceneForNext = nullptr, const itm_view* next = nullptr);
+int launch_render_image(const itm_scene* s, const float* M, const float* intr, itm_render_state* rs, uchar4* out, int type, hipStream_t st);
+int launch_forward_render(const itm_scene* s, const itm_view* v, itm_render_state* rs, hipStream_t st);
+int launch_point_cloud(const itm_scene* s, const itm_view* v, itm_render_state* rs, bool skip, float4* loc, float4* col, hipStream_t st);
+
+// ---- swapping.hip ----------------------------------------------------------------------------------------------------------------------
+int launch_swap_after_allocation(itm_scene* s, itm_render_state* rs, hipStream_t st);
+void free_swap_state(itm_scene* s);
+int create_swap_state(itm_scene* s);
+// the host cache of a swapping scene as the checkpoint sees it: the flags of all entries and, compactly, the stored blocks of the
+// flagged entries in entry order
+void swap_cache_export(const itm_scene* s, std::vector<uint8_t>& flags, std::vector<char>& blocks);
+void swap_cache_replace(itm_scene* s, const uint8_t* flags, const char* blocks);      // wholesale; inputs as swap_cache_export gives them
+
+// ---- pending.hip: pending work of the entry points -------------------------------------------------------------------------------------
 // Launches, unfused and in call order, what the render state has recorded (no-op when nothing is).
 int flush_deferred(itm_render_state* rs);
 // The prologue of every entry point that reads or writes a scene / render state: fails with ITM_ERR_DEVICE once the scene has raised a
@@ -224,75 +271,14 @@ int enter_scene(const itm_scene* s, const itm_render_state* rs);
 // [p, p + bytes) -- or, p == nullptr, that were recorded on `st` -- are launched first.
 int flush_overlapping(const void* p, size_t bytes, hipStream_t st);
 void forget_deferred(itm_render_state* rs);      // the render state is going away
-extern int g_debug_no_deferred_fusion;
 bool deferred_fusion_default();               // ITM_DEFERRED_FUSION=1 in the environment: new scenes record without being asked
-extern int g_debug_force_list_stuck;
-extern int g_debug_exchange_device_copy, g_debug_exchange_corrupt_word;      // exchange.hip
-extern int g_debug_mesh_attr_per_vertex;                                     // mesh_attributes.hip
-extern int g_debug_mesh_index_weak_hash;                                     // mesh_index.hip
-extern int g_debug_mesh_components_per_lane;                                 // mesh_components.hip
-extern int g_debug_mesh_smooth_scatter;                                      // mesh_smooth.hip
-extern int g_debug_pose_quality_rows;                                        // pose_quality.hip
 // true when rs holds the block requests of a frame issued ahead (itm_process_frame_ahead): `what` is refused with ITM_ERR_INVALID
 int refuse_while_ahead(const itm_scene* s, const itm_render_state* rs, const char* what);
 
-// entry points implemented per translation unit
-extern int g_debug_explicit_mark;
-extern int g_debug_two_pass_visible_list;
-extern int g_debug_integrate_wgs;
-extern int g_debug_dense_group_cull;
-extern int g_debug_dense_classify;
-extern int g_debug_dense_no_strips;
-extern int g_debug_tracker_launch_per_evaluation;
-extern int g_debug_tracker_host_command;
-extern int g_debug_tracker_session_unusable;
-extern int g_debug_no_sdf_mirror;
-extern int g_debug_separate_sweep;
-// itm_debug_counter (include/itm_debug.h), one per translation unit that owns a handle type: ITM_OK when `which` is one of its own
-// (*get receives the counter, then *set replaces it), -1 when it is not
-int debug_counter_tracker(int which, void* handle, const uint32_t* set, uint32_t* get);          // tracker.hip
-int debug_counter_colour_tracker(int which, void* handle, const uint32_t* set, uint32_t* get);   // colour_tracker.hip
-int debug_counter_ren_tracker(int which, void* handle, const uint32_t* set, uint32_t* get);      // ren_tracker.hip
-int debug_counter_pose_quality(int which, void* handle, const uint32_t* set, uint32_t* get);     // pose_quality.hip
-int debug_counter_image_maps(int which, void* handle, const uint32_t* set, uint32_t* get);       // image_maps.hip
-int debug_counter_aligner(int which, void* handle, const uint32_t* set, uint32_t* get);          // align.hip
-int rebuild_sdf_mirror(itm_scene* s, hipStream_t st);
-// Foreign voxel bytes on their way into a HASH scene (buffer upload, checkpoint load, the checkpoint's cached blocks): ITM_ERR_INVALID, naming
-// the voxel, when one of the n voxels holds the sdf word that the sdf mirror keeps for "no block here" (MirrorCodec::kAbsent,
-// accel_device.h); `what` says where the bytes come from.  Dense scenes have no mirror and take any word.  Host memory, host only.
-int refuse_absent_sdf_words(const itm_scene* s, const void* voxels_host, size_t n, const char* what);
-int launch_swap_after_allocation(itm_scene* s, itm_render_state* rs, hipStream_t st);   // swapping.hip
-void free_swap_state(itm_scene* s);
-int create_swap_state(itm_scene* s);
-// the host cache of a swapping scene as the checkpoint sees it (swapping.hip): the flags of all entries and, compactly, the stored
-// blocks of the flagged entries in entry order
-void swap_cache_export(const itm_scene* s, std::vector<uint8_t>& flags, std::vector<char>& blocks);
-void swap_cache_replace(itm_scene* s, const uint8_t* flags, const char* blocks);      // wholesale; inputs as swap_cache_export gives them
-int live_hash_scenes(int device);                                     // hash scenes alive on a device (scene.hip)
-std::vector<itm_render_state*> render_states_of(const itm_scene* s);  // the render states registered with a scene, copied under the registry's lock (scene.hip)
-int accel_unfill(itm_scene* s, hipStream_t st);                      // empties the cubes through the table that filled them
-int accel_place(itm_scene* s, const float* invM, hipStream_t st);    // (re-)places the cubes around a view
-extern int g_debug_no_fused_projection;
-int accel_rebuild(itm_scene* s, hipStream_t st);       // occupancy bitmap, both directories and the sdf mirror, from the table
-AccelWriter accel_writer(const itm_scene* s);          // the scene's derived structures as kernels write them (accel_device.h)
-extern int g_debug_no_directory;
-int launch_request_stage(itm_scene* s, const itm_view* v, itm_render_state* rs, bool onlyVisible, bool fuseRangeInit, hipStream_t st);
-int launch_sweep_stage(itm_scene* s, const itm_view* v, itm_render_state* rs, bool onlyVisible, hipStream_t st);
-int launch_allocate(itm_scene* s, const itm_view* v, itm_render_state* rs, bool onlyVisible, bool fuseRangeInit, hipStream_t st);
-int validate_allocate(const itm_scene* s, const itm_view* v, const itm_render_state* rs, bool onlyVisible);
-int validate_integrate(const itm_scene* s, const itm_view* v);
-int cancel_ahead(itm_scene* s, itm_render_state* rs, hipStream_t st);
-int launch_integrate(itm_scene* s, const itm_view* v, itm_render_state* rs, hipStream_t st, bool fuseProjection = false);
-struct FuseParams;                                     // fuse_device.h
-int launch_integrate_dense(itm_scene* s, const itm_view* v, const FuseParams& p, hipStream_t st);   // integrate_dense.hip: the dense half of launch_integrate
-bool can_fuse_projection(const itm_scene* s, const itm_render_state* rs);
-int launch_find_visible(const itm_scene* s, const float* M, const float* intr, itm_render_state* rs, hipStream_t st);
-int launch_expected_depths(const itm_scene* s, const float* M, const float* intr, itm_render_state* rs, bool rangeAlreadyInit, hipStream_t st, bool projected = false);
-int launch_raycast(const itm_scene* s, const float* invM, const float* intr, itm_render_state* rs, float4* dst, hipStream_t st, bool reduceRange = false);
-int launch_icp_maps(const itm_scene* s, const itm_view* v, itm_render_state* rs, float4* points, float4* normals, hipStream_t st, bool reduceRange = false,
-                    itm_scene* sceneForNext = nullptr, const itm_view* next = nullptr);
-int launch_render_image(const itm_scene* s, const float* M, const float* intr, itm_render_state* rs, uchar4* out, int type, hipStream_t st);
-int launch_forward_render(const itm_scene* s, const itm_view* v, itm_render_state* rs, hipStream_t st);
-int launch_point_cloud(const itm_scene* s, const itm_view* v, itm_render_state* rs, bool skip, float4* loc, float4* col, hipStream_t st);
+// ---- debug.hip -------------------------------------------------------------------------------------------------------------------------
+// The switches are read through debug_value(key) (debug.h).  itm_debug_counter hands the counters that are more than a handle's
+// sequence number (gh_reduce.h: GHHandle) to their owners: *get receives the counter, then *set replaces it.
+int tracker_counter(int which, itm_tracker* t, const uint32_t* set, uint32_t* get);      // tracker.hip: the TRACKER_* counters; t == nullptr: the calling thread's tracker
+int image_map_counter(itm_stream stream, const uint32_t* set, uint32_t* get);            // image_maps.hip: IMAGE_MAP_EPOCH
 
 }  // namespace itm

@@ -237,7 +237,7 @@ inline int select_slots(const int32_t* srcSlots_dev, int n, int srcEntries, uint
 // itm_scene_coarsen pass src's table, itm_scene_resample its candidate list (resample.hip).  chunkCnt: one int2 per chunk of dst's table.
 template <int SHIFT>
 inline int place_positions(itm_scene* dst, const uint4* posHash, int posEntries, const uint8_t* sel, int2* chunkCnt, hipStream_t st, MergePlacement& p) {
-  const MergeTable table{dst->hash, g_debug_no_directory ? nullptr : dst->dirSlot, dst->org, (uint32_t)(dst->cfg.bucketNum - 1), dst->cfg.bucketNum, dst->noTotalEntries};
+  const MergeTable table{dst->hash, debug_value(ITM_DEBUG_NO_DIRECTORY) ? nullptr : dst->dirSlot, dst->org, (uint32_t)(dst->cfg.bucketNum - 1), dst->cfg.bucketNum, dst->noTotalEntries};
   const int reqGrid = (posEntries + 255) / 256;
   for (int round = 1;; ++round) {
     ITM_HIP(hipMemsetAsync(chunkCnt, 0, (size_t)dst->numChunks * 8, st));

@@ -28,7 +28,6 @@
 
 namespace itm {
 
-int g_debug_mesh_attr_per_vertex = 0;
 
 constexpr int kHaloLow = 2;                       // planes below the block
 constexpr int kHaloSide = kBlockSide + 5;         // -2 .. +10
@@ -177,7 +176,7 @@ int itm_mesh_attributes(const itm_scene* s, itm_mesh* m, int what, itm_stream st
   const int grid = 256 * 8;
   const int rc = dispatch_volume(s, [&](auto vx, auto isDense) {
     using VX = decltype(vx);
-    if (isDense.value || g_debug_mesh_attr_per_vertex)      // the mesh of itm_mesh_volume: every vertex through the voxel array
+    if (isDense.value || debug_value(ITM_DEBUG_MESH_ATTR_PER_VERTEX))      // the mesh of itm_mesh_volume: every vertex through the voxel array
       mesh_attr_vertex_kernel<VX, isDense.value><<<grid, 256, 0, st>>>(vol, m->triangles, m->totals, 0u, s->prm.voxelSize, (uint32_t)what, m->normals, m->colours);
     else
       mesh_attr_block_kernel<VX, false><<<grid, 256, 0, st>>>(vol, m->slots, m->listCounters, m->blockTriangles, m->triangles, m->totals, m->capBlocks, s->prm.voxelSize,

@@ -42,7 +42,6 @@
 
 namespace itm {
 
-int g_debug_mesh_components_per_lane = 0;
 
 constexpr uint32_t kComponentMaxRounds = 8;       // union rounds before the call gives up (one is what a correct union takes)
 constexpr int kComponentWords = 10;               // an itm_mesh_component as uint32 words: root, vertices, triangles, 0, min[3], max[3]
@@ -364,7 +363,7 @@ static int label_components(ComponentBuffers& b, const uint32_t* faces, uint32_t
   components_spread_kernel<<<grid_for(nV), 256, 0, st>>>(b.parent, nV, b.vertexComponent);
   // a wave per span of consecutive elements, eight waves' worth of them at least: the fewer waves, the fewer flushes onto the hot records
   const int statsGrid = (int)std::min<size_t>(std::max<size_t>(((size_t)std::max(nT, nV) + 2047) / 2048, 1), 256);
-  if (g_debug_mesh_components_per_lane)
+  if (debug_value(ITM_DEBUG_MESH_COMPONENTS_PER_LANE))
     components_stats_kernel<true><<<statsGrid, 256, 0, st>>>(b.vertexComponent, positions, nV, faces, nT, b.triangleComponent, b.components);
   else
     components_stats_kernel<false><<<statsGrid, 256, 0, st>>>(b.vertexComponent, positions, nV, faces, nT, b.triangleComponent, b.components);

@@ -34,7 +34,6 @@
 
 namespace itm {
 
-int g_debug_mesh_index_weak_hash = 0;
 
 constexpr uint32_t kIndexEmpty = 0xffffffffu;
 constexpr int kIndexChunk = 1024;                 // soup vertices per workgroup of the counting and compacting passes
@@ -195,7 +194,7 @@ int itm_mesh_index(itm_mesh* m, itm_stream stream) {
   if ((e = m->indexChunks.reserve((size_t)nChunks + 1)) != hipSuccess) return fail(e, "mesh index chunk counts");
   const uint32_t* soup = (const uint32_t*)m->triangles.get();
   const uint32_t mask = (uint32_t)(tableSize - 1);
-  const int weak = g_debug_mesh_index_weak_hash;
+  const int weak = debug_value(ITM_DEBUG_MESH_INDEX_WEAK_HASH);
   const int grid = 256 * 8;
   ITM_HIP(hipMemsetAsync(m->indexTable, 0xff, tableSize * 4, st));
   mesh_index_insert_kernel<<<grid, 256, 0, st>>>(soup, (uint32_t)nSoup, m->indexTable, mask, weak);

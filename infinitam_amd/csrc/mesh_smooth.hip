@@ -41,7 +41,6 @@
 
 namespace itm {
 
-int g_debug_mesh_smooth_scatter = 0;
 
 constexpr uint32_t kHeavyRow = 128;               // rows with more entries go to one wave per row
 constexpr int kRegisterRow = 16;                  // rows up to this many entries are judged in registers (the median is 12)
@@ -377,7 +376,7 @@ static int run_smooth(SmoothBuffers& b, float* vertices, const uint32_t* faces, 
                       itm_mesh_smooth_stats* stats, bool* written, hipStream_t st) {
   *written = false;
   if ((size_t)nT * 6 >= 0x7fffffffull || nV >= 0x7fffffffu) return set_error(ITM_ERR_INVALID, "mesh too large to smooth");
-  const bool scatter = g_debug_mesh_smooth_scatter != 0 && cfg.steps > 0;
+  const bool scatter = debug_value(ITM_DEBUG_MESH_SMOOTH_SCATTER) != 0 && cfg.steps > 0;
   const int nChunks = (int)((nV + kSmoothChunk - 1) / kSmoothChunk);
   const uint32_t capHeavy = (uint32_t)std::min<size_t>(nV, (size_t)nT * 6 / kHeavyRow + 1);
   hipError_t e;

@@ -287,7 +287,7 @@ hipError_t alloc_update_arena(const itm_scene* s, itm_mesh* m) {
 }
 
 static UpdateTable update_table(const itm_scene* s) {
-  return UpdateTable{s->hash, g_debug_no_directory ? nullptr : s->dirSlot.get(), s->org, (uint32_t)(s->cfg.bucketNum - 1), s->cfg.bucketNum, s->noTotalEntries};
+  return UpdateTable{s->hash, debug_value(ITM_DEBUG_NO_DIRECTORY) ? nullptr : s->dirSlot.get(), s->org, (uint32_t)(s->cfg.bucketNum - 1), s->cfg.bucketNum, s->noTotalEntries};
 }
 
 int record_run_table(const itm_scene* s, itm_mesh* m, hipStream_t st) {

@@ -34,7 +34,6 @@
 
 namespace itm {
 
-int g_debug_no_deferred_fusion = 0;
 
 // One lock for the recorded calls of the whole process: a record is a few stores, a flush happens at most once per frame and render
 // state, and a flush triggered from another thread (a copy into an image someone else's recorded view reads) must not race with the
@@ -121,7 +120,7 @@ static bool deferral_enabled(const itm_scene* s) {
   static const bool off = [] { const char* e = getenv("ITM_NO_DEFERRED_FUSION"); return e && atoi(e) != 0; }();
   // dense scenes launch the same kernels either way; with swapping the mapper calls the swapping engine between the integration and
   // the ray cast (Engine/ITMDenseMapper.cpp:59-64), which would flush every frame
-  return s->deferredFusion && !off && !g_debug_no_deferred_fusion && s->cfg.indexType == ITM_INDEX_HASH && !s->cfg.useSwapping;
+  return s->deferredFusion && !off && !debug_value(ITM_DEBUG_NO_DEFERRED_FUSION) && s->cfg.indexType == ITM_INDEX_HASH && !s->cfg.useSwapping;
 }
 
 bool deferred_fusion_default() {

@@ -28,8 +28,6 @@
 
 namespace itm {
 
-int g_debug_pose_quality_rows = 0;
-
 constexpr float kQualityPointLimit = 262136.0f;      // itm_scene_query_points' limit on |p| in voxels (query.hip: kPointLimit)
 
 struct PoseQualityParams {
@@ -118,21 +116,10 @@ static const char* quality_config_fault(const itm_pose_quality_config* c) {
 
 using namespace itm;
 
-struct itm_pose_quality_handle {
-  std::mutex mu;
-  itm::GHChannel ch;      // the pinned records of this handle's launches
-};
+struct itm_pose_quality_handle : itm::GHHandle {};      // the pinned records of this handle's launches
 
 namespace itm {
-int debug_counter_pose_quality(int which, void* handle, const uint32_t* set, uint32_t* get) {
-  if (which != ITM_COUNTER_POSE_QUALITY_SEQ) return -1;
-  itm_pose_quality_handle* t = (itm_pose_quality_handle*)handle;
-  if (!t) return set_error(ITM_ERR_INVALID, "null handle");
-  std::lock_guard<std::mutex> lock(t->mu);
-  if (get) *get = t->ch.seq;
-  if (set) t->ch.seq = *set;
-  return ITM_OK;
-}
+GHHandle* gh_handle(itm_pose_quality_handle* q) { return static_cast<GHHandle*>(q); }
 }  // namespace itm
 
 extern "C" {
@@ -188,29 +175,26 @@ int itm_pose_quality_evaluate(itm_pose_quality_handle* q, const itm_scene* s, co
   // the residual image may be read by a recorded (not yet launched) call of another scene
   if (residuals_dev) { const int rc = flush_overlapping(residuals_dev, (size_t)pixels * 4, st); if (rc) return rc; }
   std::lock_guard<std::mutex> lock(q->mu);
-  if (q->ch.moved()) q->ch.release();
-  { const int rc = q->ch.reserve(kGHGroups); if (rc) return rc; }
+  { const int rc = q->ready([&] { q->ch.release(); }); if (rc) return rc; }
   p.fx = view->intr_d[0]; p.fy = view->intr_d[1]; p.cx = view->intr_d[2]; p.cy = view->intr_d[3];
   p.voxelSize = s->prm.voxelSize; p.mu = s->prm.mu; p.inlierDistance = cfg->inlierDistance; p.minWeight = cfg->minWeight;
   p.w = view->w; p.h = view->h;
-  const bool tiles = g_debug_pose_quality_rows == 0;
+  const bool tiles = debug_value(ITM_DEBUG_POSE_QUALITY_ROWS) == 0;
   const long long units = tiles ? (long long)((view->w + 7) >> 3) * ((view->h + 7) >> 3) : ((long long)pixels + 63) >> 6;
   const long long groups = (units + kGHWaves - 1) / kGHWaves;
   const int grid = (int)(groups < kGHGroups ? groups : kGHGroups);
   const VolumeView vol = make_volume(s);
-  const unsigned int seq = q->ch.begin();
-  GHBlockRecord* rec = q->ch.rec.device();
-  const int rc = dispatch_volume(s, [&](auto vx, auto dense) {
-    using VX = decltype(vx);
-    if (tiles) pose_quality_kernel<VX, dense.value, true><<<grid, kGHThreads, 0, st>>>(vol, view->depth, p, residuals_dev, rec, seq);
-    else pose_quality_kernel<VX, dense.value, false><<<grid, kGHThreads, 0, st>>>(vol, view->depth, p, residuals_dev, rec, seq);
-    return ITM_OK;
-  });
-  if (rc) return rc;
-  ITM_LAUNCH_CHECK();
   double sums[kGHValues];
   int valid = 0;
-  { const int r = q->ch.collect((size_t)grid, seq, st, sums, &valid); if (r) return r; }
+  const int rc = q->evaluate((size_t)grid, st, [&](GHBlockRecord* rec, unsigned int seq) {
+    return dispatch_volume(s, [&](auto vx, auto dense) {
+      using VX = decltype(vx);
+      if (tiles) pose_quality_kernel<VX, dense.value, true><<<grid, kGHThreads, 0, st>>>(vol, view->depth, p, residuals_dev, rec, seq);
+      else pose_quality_kernel<VX, dense.value, false><<<grid, kGHThreads, 0, st>>>(vol, view->depth, p, residuals_dev, rec, seq);
+      return ITM_OK;
+    });
+  }, sums, &valid);
+  if (rc) return rc;
   out->noPixels = pixels; out->noValid = valid;
   out->noKnown = (int32_t)sums[0]; out->noInliers = (int32_t)sums[1];
   out->sumSqKnown = sums[2]; out->sumSqInliers = sums[3];

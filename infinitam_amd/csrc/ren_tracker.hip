@@ -109,24 +109,14 @@ __global__ void __launch_bounds__(kGHThreads) ren_eval_kernel(VolumeView vol, co
 
 }  // namespace itm
 
-struct itm_ren_tracker {
-  mutable std::mutex mu;
-  itm::GHChannel ch;
+struct itm_ren_tracker : itm::GHHandle {
   itm::DeviceBuffer<float4> points;
   int w = 0, h = 0;                // size of the last prepared depth image (0: nothing prepared)
 };
 
 namespace itm {
 
-int debug_counter_ren_tracker(int which, void* handle, const uint32_t* set, uint32_t* get) {
-  if (which != ITM_COUNTER_REN_SEQ) return -1;
-  itm_ren_tracker* t = (itm_ren_tracker*)handle;
-  if (!t) return set_error(ITM_ERR_INVALID, "null handle");
-  std::lock_guard<std::mutex> lock(t->mu);
-  if (get) *get = t->ch.seq;
-  if (set) t->ch.seq = *set;
-  return ITM_OK;
-}
+GHHandle* gh_handle(itm_ren_tracker* t) { return static_cast<GHHandle*>(t); }
 
 static void ren_release(itm_ren_tracker* t) {
   t->ch.release();
@@ -137,8 +127,7 @@ static void ren_release(itm_ren_tracker* t) {
 static int ren_prepare(itm_ren_tracker* t, const itm_view* view, hipStream_t st) {
   if (!view || !view->depth) return set_error(ITM_ERR_INVALID, "Ren tracker: null view or depth image");
   if (view->w <= 0 || view->h <= 0) return set_error(ITM_ERR_INVALID, "Ren tracker: empty depth image");
-  if (t->ch.moved()) ren_release(t);
-  int rc = t->ch.reserve(kGHGroups);
+  int rc = t->ready([&] { ren_release(t); });
   if (rc) return rc;
   const hipError_t e = t->points.reserve((size_t)view->w * view->h);
   if (e != hipSuccess) { ren_release(t); return hip_fail(e, "Ren tracker points", __FILE__, __LINE__); }
@@ -164,19 +153,17 @@ static int ren_evaluate(itm_ren_tracker* t, const itm_scene* s, const float invM
   p.oneOverVoxel = 1.0f / s->prm.voxelSize;
   p.n = t->w * t->h;
   const VolumeView vol = make_volume(s);
-  const unsigned int seq = t->ch.begin();
-  const int rc = dispatch_volume(s, [&](auto vx, auto dense) {
-    using VX = decltype(vx);
-    if (gh) ren_eval_kernel<VX, dense.value, true><<<kGHGroups, kGHThreads, 0, st>>>(vol, t->points, p, t->ch.rec.device(), seq);
-    else ren_eval_kernel<VX, dense.value, false><<<kGHGroups, kGHThreads, 0, st>>>(vol, t->points, p, t->ch.rec.device(), seq);
-    return ITM_OK;
-  });
-  if (rc) return rc;
-  ITM_LAUNCH_CHECK();
   double sums[kGHValues];
   int valid = 0;
-  const int r = t->ch.collect(kGHGroups, seq, st, sums, &valid);
-  if (r) return r;
+  const int rc = t->evaluate(kGHGroups, st, [&](GHBlockRecord* rec, unsigned int seq) {
+    return dispatch_volume(s, [&](auto vx, auto dense) {
+      using VX = decltype(vx);
+      if (gh) ren_eval_kernel<VX, dense.value, true><<<kGHGroups, kGHThreads, 0, st>>>(vol, t->points, p, rec, seq);
+      else ren_eval_kernel<VX, dense.value, false><<<kGHGroups, kGHThreads, 0, st>>>(vol, t->points, p, rec, seq);
+      return ITM_OK;
+    });
+  }, sums, &valid);
+  if (rc) return rc;
   out->f = -(float)sums[0];
   if (gh) {
     out->noValidPoints = valid;

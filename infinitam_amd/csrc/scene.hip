@@ -584,7 +584,7 @@ int itm_scene_create(const itm_scene_config* cfg_in, const itm_scene_params* prm
   // ITM_MIRROR_PAGES sizes the pool).  Silently left out when not even the pool fits -- and only for the short voxel types: for the
   // float types it was measured on BASELINE configs[4], the ray cast gains less than the integration pays for the extra 4-byte stores
   // (ITM_MIRROR_FLOAT_TYPES=1 builds it in).
-  if (cfg.indexType == ITM_INDEX_HASH && s->dirPtr && !g_debug_no_sdf_mirror && (ITM_MIRROR_FLOAT_TYPES || !mirror_is_float(s))) {
+  if (cfg.indexType == ITM_INDEX_HASH && s->dirPtr && !debug_value(ITM_DEBUG_NO_SDF_MIRROR) && (ITM_MIRROR_FLOAT_TYPES || !mirror_is_float(s))) {
     const char* mode = getenv("ITM_MIRROR");
     const size_t voxBytes = mirror_is_float(s) ? 4 : 2;
     // the dense cube's side: the smallest power of two of blocks that is at least 1.25 x the view's reach (viewFrustum_max in blocks + 2:

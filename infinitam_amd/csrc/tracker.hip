@@ -460,9 +460,7 @@ __global__ void __launch_bounds__(kGHThreads) gh_session_kernel(const unsigned l
 // threads) never share records or sequence numbers.
 }  // namespace itm
 
-struct itm_tracker {
-  std::mutex mu;
-  itm::GHChannel ch;                      // pinned host records of every evaluation (a session's coarse levels included)
+struct itm_tracker : itm::GHHandle {      // ch: pinned host records of every evaluation (a session's coarse levels included)
   std::vector<itm::DeviceBuffer<float>> pyramid;
   std::vector<itm::DeviceBuffer<float>> weightPyramid;   // weighted ICP: the sigmaZ pyramid (allocated on first use)
   int sessionUsable = -1;                 // -1 not probed yet, 0 launch per evaluation, 1 resident evaluation kernel
@@ -505,8 +503,7 @@ static void tracker_release(itm_tracker* t) {
 
 // records for `blocks` workgroups on the current device
 static int tracker_reserve(itm_tracker* t, size_t blocks) {
-  if (t->ch.moved()) tracker_release(t);           // buffers of another device (incl. the pyramid and the session's) are of no use here
-  const int rc = t->ch.reserve(blocks);
+  const int rc = t->ready([&] { tracker_release(t); }, blocks);      // buffers of another device (incl. the pyramid and the session's) are of no use here
   if (rc) tracker_release(t);                      // a handle that could not get its memory keeps none of it
   return rc;
 }
@@ -536,9 +533,8 @@ static itm_tracker* thread_tracker() {
   return mine;
 }
 
-int debug_counter_tracker(int which, void* handle, const uint32_t* set, uint32_t* get) {
-  if (which < ITM_COUNTER_TRACKER_SEQ || which > ITM_COUNTER_TRACKER_RELAUNCHES) return -1;
-  itm_tracker* t = handle ? (itm_tracker*)handle : thread_tracker();
+int tracker_counter(int which, itm_tracker* t, const uint32_t* set, uint32_t* get) {
+  if (!t) t = thread_tracker();
   if (!t) return set_error(ITM_ERR_DEVICE, "out of host memory");
   std::lock_guard<std::mutex> lock(t->mu);
   if (which == ITM_COUNTER_TRACKER_SEQ) { if (get) *get = t->ch.seq; if (set) t->ch.seq = *set; return ITM_OK; }
@@ -571,29 +567,25 @@ static int compute_g_and_h(itm_tracker* trk, const float* depth, int w, int h, c
   p.weight = weight;
   const float4* pm = (const float4*)pointsMap; const float4* nm = (const float4*)normalsMap;
   const int np = (iterationType == ITM_TRACKER_ITERATION_BOTH) ? 6 : 3;
-  const unsigned int seq = trk->ch.begin();
-  if (weight) {          // weighted ICP (ITMWeightedICPTracker_CPU::ComputeGandH): the same tiles, grid and order of the additions
-    if (iterationType == 1) gh_partial_kernel<1, true><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, trk->ch.rec.device(), seq);
-    else if (iterationType == 2) gh_partial_kernel<2, true><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, trk->ch.rec.device(), seq);
-    else gh_partial_kernel<3, true><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, trk->ch.rec.device(), seq);
-  } else if (iterationType == 1) gh_partial_kernel<1><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, trk->ch.rec.device(), seq);
-  else if (iterationType == 2) gh_partial_kernel<2><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, trk->ch.rec.device(), seq);
-  else gh_partial_kernel<3><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, trk->ch.rec.device(), seq);
-  ITM_LAUNCH_CHECK();
-  // Wait for every workgroup's tagged record and add them in block order (fixed order => deterministic, in double; bounded wait)
+  // Launch, wait for every workgroup's tagged record and add them in block order (fixed order => deterministic, in double; bounded wait)
   double sums[kGHValues];
   int n = 0;
-  rc = trk->ch.collect(blocks, seq, st, sums, &n);
+  rc = trk->evaluate(blocks, st, [&](GHBlockRecord* rec, unsigned int seq) {
+    if (weight) {          // weighted ICP (ITMWeightedICPTracker_CPU::ComputeGandH): the same tiles, grid and order of the additions
+      if (iterationType == 1) gh_partial_kernel<1, true><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, rec, seq);
+      else if (iterationType == 2) gh_partial_kernel<2, true><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, rec, seq);
+      else gh_partial_kernel<3, true><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, rec, seq);
+    } else if (iterationType == 1) gh_partial_kernel<1><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, rec, seq);
+    else if (iterationType == 2) gh_partial_kernel<2><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, rec, seq);
+    else gh_partial_kernel<3><<<grid, kGHThreads, 0, st>>>(depth, pm, nm, p, rec, seq);
+    return ITM_OK;
+  }, sums, &n);
   if (rc) return rc;
   icp_result(sums, n, np, out);
   return ITM_OK;
 }
 
 // ---- evaluation session, host side -------------------------------------------------------------------------
-int g_debug_tracker_launch_per_evaluation = 0;   // debug key 10: TrackCamera with one launch per evaluation (the path before the session kernel)
-int g_debug_tracker_session_unusable = 0;        // debug key 18: the resident kernel reports itself unusable at the n-th evaluation of a call (tests the fall-back)
-int g_debug_tracker_host_command = 0;            // debug key 11: session commands through pinned host memory even where the device has a large BAR
-
 constexpr int kSessionUnusable = -1000;     // internal: the resident kernel cannot serve this evaluation, use a launch instead
 constexpr double kSessionTimeoutSeconds = 0.5;   // an evaluation through the resident kernel answers in microseconds; after this long it goes through a launch
 
@@ -607,7 +599,7 @@ static int session_reserve(itm_tracker* t) {
   hipError_t e = hipSuccess;
   int dev = 0, largeBar = 0;
   (void)hipGetDevice(&dev);
-  if (!g_debug_tracker_host_command && hipDeviceGetAttribute(&largeBar, hipDeviceAttributeIsLargeBar, dev) == hipSuccess && largeBar &&
+  if (!debug_value(ITM_DEBUG_TRACKER_HOST_COMMAND) && hipDeviceGetAttribute(&largeBar, hipDeviceAttributeIsLargeBar, dev) == hipSuccess && largeBar &&
       t->cmdBar.alloc(64, 16, hipDeviceMallocFinegrained) == hipSuccess) {
     t->cmdDirect = true;
     t->cmd = t->cmdDev = t->cmdBar;
@@ -775,7 +767,7 @@ static int subsample_pyramid(const float* src, int w, int h, int levels, std::ve
     ITM_HIP(bufs[i].reserve((size_t)lw[i] * lh[i]));
     lv[i] = bufs[i];
   }
-  if (levels >= 2 && levels <= 5 && !g_debug_tracker_launch_per_evaluation) {
+  if (levels >= 2 && levels <= 5 && !debug_value(ITM_DEBUG_TRACKER_LAUNCH_PER_EVALUATION)) {
     PyramidLevels P;
     memset(&P, 0, sizeof P);
     P.levels = levels - 1;
@@ -821,7 +813,7 @@ static int track_camera(itm_tracker* trk, const itm_tracker_config* cfg, const i
     return compute_g_and_h(trk, pyr[level].depth, pyr[level].w, pyr[level].h, pyr[level].intr, pointsMap, normalsMap, view->w, view->h,
                            pyr[0].intr, invPose, scenePose, distThresh, mode, e, st);
   };
-  if (g_debug_tracker_launch_per_evaluation) return icp_track(cfg, view->M_d, M_d_out, per_launch);
+  if (debug_value(ITM_DEBUG_TRACKER_LAUNCH_PER_EVALUATION)) return icp_track(cfg, view->M_d, M_d_out, per_launch);
   // One resident kernel for all evaluations of this call -- and one such kernel per DEVICE at a time: its workgroups take a compute
   // unit's whole register budget for one wave per SIMD (256 VGPRs), so two sessions cannot share a compute unit, and two sessions
   // that have each got hold of SOME compute units wait for the rest until their idle limits fire (measured with four closed loops
@@ -843,7 +835,7 @@ static int track_camera(itm_tracker* trk, const itm_tracker_config* cfg, const i
   std::lock_guard<std::mutex> oneSession(session_gate(trk->ch.device));
   rc = icp_track(cfg, view->M_d, M_d_out, [&](int level, int mode, const float invPose[16], float distThresh, itm_tracker_gh* e) {
     if (trk->sessionUsable) {
-      const int r = (g_debug_tracker_session_unusable > 0 && ++trk->debugEvaluations == g_debug_tracker_session_unusable) ? kSessionUnusable : session_g_and_h(trk, pyr[level].depth, pyr[level].w, pyr[level].h, pyr[level].intr, pointsMap, normalsMap, view->w, view->h,
+      const int r = (debug_value(ITM_DEBUG_TRACKER_SESSION_UNUSABLE) > 0 && ++trk->debugEvaluations == debug_value(ITM_DEBUG_TRACKER_SESSION_UNUSABLE)) ? kSessionUnusable : session_g_and_h(trk, pyr[level].depth, pyr[level].w, pyr[level].h, pyr[level].intr, pointsMap, normalsMap, view->w, view->h,
                                     pyr[0].intr, invPose, scenePose, distThresh, mode, e, st);
       if (r != kSessionUnusable) return r;
       session_close(trk);

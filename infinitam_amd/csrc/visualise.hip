@@ -34,13 +34,6 @@ namespace itm {
 #define ITM_MIRROR_FLOAT_TYPES 0     // (scene.hip decides whether a float scene gets a mirror; the same switch must be given to every file)
 #endif
 
-int g_debug_force_global_range = 0;
-int g_debug_no_directory = 0;
-int g_debug_no_sdf_mirror = 0;      // debug key 12: ray casting reads voxels through the directory / table although the scene has an sdf mirror
-int g_debug_no_fused_range_reduce = 0;
-int g_debug_single_pass_raycast = 0;
-int g_debug_no_side_projection = 0;
-int g_debug_dense_range_refill = 0;
 
 // ---------------------------------------------------------------------------------------------
 // expected depth range
@@ -151,7 +144,7 @@ __global__ void __launch_bounds__(256) range_reduce_kernel(RenderCounters* __res
 // their LDS copy of the sub-sampled range image
 bool can_fuse_projection(const itm_scene* s, const itm_render_state* rs) {
   const size_t ldsBytes = (size_t)((rs->w + 7) / 8) * ((rs->h + 7) / 8) * sizeof(uint2);
-  return !g_debug_no_fused_projection && s->cfg.indexType == ITM_INDEX_HASH && ldsBytes <= 39 * 1024 && rs->rangePartials && !g_debug_force_global_range;
+  return !debug_value(ITM_DEBUG_NO_FUSED_PROJECTION) && s->cfg.indexType == ITM_INDEX_HASH && ldsBytes <= 39 * 1024 && rs->rangePartials && !debug_value(ITM_DEBUG_FORCE_GLOBAL_RANGE_ATOMICS);
 }
 
 static int ensure_range_lds(const itm_scene* s) {
@@ -182,7 +175,7 @@ static ProjParams make_proj_params(const itm_scene* s, const float* M, const flo
 // 28 us of config 5's frame that used to sit between the integration and the ray cast.  Returns 1 when it was launched (the caller
 // then passes projected = true to launch_expected_depths), 0 when this path does not apply, < 0 on error.
 int launch_projection_beside(const itm_scene* s, const float* M, const float* intr, itm_render_state* rs, hipStream_t st) {
-  if (s->cfg.indexType != ITM_INDEX_HASH || g_debug_force_global_range || g_debug_no_side_projection || !rs->rangePartials) return 0;
+  if (s->cfg.indexType != ITM_INDEX_HASH || debug_value(ITM_DEBUG_FORCE_GLOBAL_RANGE_ATOMICS) || debug_value(ITM_DEBUG_NO_SIDE_PROJECTION) || !rs->rangePartials) return 0;
   const int RW = (rs->w + 7) / 8, RH = (rs->h + 7) / 8;
   const size_t ldsBytes = (size_t)RW * RH * sizeof(uint2);
   if (ldsBytes > 150 * 1024) return 0;
@@ -217,7 +210,7 @@ int launch_expected_depths(const itm_scene* s, const float* M, const float* intr
   const int P = rs->w * rs->h;
   KernelTimer tk(s, ITM_TK_RANGE, st);
   if (s->cfg.indexType == ITM_INDEX_DENSE) {
-    if (rs->denseRangeReady && !g_debug_dense_range_refill) return ITM_OK;        // the image already holds the constant (5 us per frame of config 3)
+    if (rs->denseRangeReady && !debug_value(ITM_DEBUG_DENSE_RANGE_REFILL)) return ITM_OK;        // the image already holds the constant (5 us per frame of config 3)
     range_init_kernel<<<512, 256, 0, st>>>(rs->range, P, 0.2f, 3.0f, rs->counters);
     ITM_LAUNCH_CHECK();
     rs->denseRangeReady = true;
@@ -227,7 +220,7 @@ int launch_expected_depths(const itm_scene* s, const float* M, const float* intr
   if (!rangeAlreadyInit) range_init_kernel<<<512, 256, 0, st>>>(rs->range, P, 999999.9f, 0.05f, rs->counters);
   const int RW = (rs->w + 7) / 8, RH = (rs->h + 7) / 8;
   const size_t ldsBytes = (size_t)RW * RH * sizeof(uint2);
-  const bool forceGlobal = g_debug_force_global_range != 0;  // test hook for the fallback path
+  const bool forceGlobal = debug_value(ITM_DEBUG_FORCE_GLOBAL_RANGE_ATOMICS) != 0;  // test hook for the fallback path
   if (ldsBytes <= 150 * 1024 && !forceGlobal && rs->rangePartials) {
     int rc = ensure_range_lds(s);
     if (rc) return rc;
@@ -437,7 +430,7 @@ int launch_raycast(const itm_scene* s, const float* invM, const float* intr, itm
   const bool dense = s->cfg.indexType == ITM_INDEX_DENSE;
   RangeFuse fuse{rs->rangePartials, rs->counters, rs->projBuf, rs->range, (rs->w + 7) / 8, (rs->h + 7) / 8, s->cfg.maxRenderingBlocks};
   // two phases whenever the block directory is in use
-  const bool park = !dense && vol.dirPtr != nullptr && !g_debug_single_pass_raycast;
+  const bool park = !dense && vol.dirPtr != nullptr && !debug_value(ITM_DEBUG_SINGLE_PASS_RAYCAST);
   AheadRequest ahead;
   memset(&ahead, 0, sizeof ahead);
   int reqTiles = 0;
@@ -635,66 +628,6 @@ using namespace itm;
 
 extern "C" {
 
-int itm_debug_set(int key, int value) {
-  if (key == ITM_DEBUG_FORCE_GLOBAL_RANGE_ATOMICS) { g_debug_force_global_range = value; return ITM_OK; }
-  if (key == ITM_DEBUG_EXPLICIT_MARK_PREVIOUS) { g_debug_explicit_mark = value; return ITM_OK; }
-  if (key == ITM_DEBUG_INTEGRATE_WORKGROUPS) { g_debug_integrate_wgs = value; return ITM_OK; }
-  if (key == ITM_DEBUG_NO_FUSED_PROJECTION) { g_debug_no_fused_projection = value; return ITM_OK; }
-  if (key == ITM_DEBUG_NO_DIRECTORY) { g_debug_no_directory = value; return ITM_OK; }
-  if (key == ITM_DEBUG_NO_FUSED_RANGE_REDUCE) { g_debug_no_fused_range_reduce = value; return ITM_OK; }
-  if (key == ITM_DEBUG_TWO_PASS_VISIBLE_LIST) { g_debug_two_pass_visible_list = value; return ITM_OK; }
-  if (key == ITM_DEBUG_SINGLE_PASS_RAYCAST) { g_debug_single_pass_raycast = value; return ITM_OK; }
-  if (key == ITM_DEBUG_DENSE_GROUP_CULL) { g_debug_dense_group_cull = value; return ITM_OK; }
-  if (key == ITM_DEBUG_TRACKER_LAUNCH_PER_EVALUATION) { g_debug_tracker_launch_per_evaluation = value; return ITM_OK; }
-  if (key == ITM_DEBUG_TRACKER_HOST_COMMAND) { g_debug_tracker_host_command = value; return ITM_OK; }
-  if (key == ITM_DEBUG_NO_SDF_MIRROR) { g_debug_no_sdf_mirror = value; return ITM_OK; }
-  if (key == ITM_DEBUG_SEPARATE_SWEEP) { g_debug_separate_sweep = value; return ITM_OK; }
-  if (key == ITM_DEBUG_NO_SIDE_PROJECTION) { g_debug_no_side_projection = value; return ITM_OK; }
-  if (key == ITM_DEBUG_DENSE_RANGE_REFILL) { g_debug_dense_range_refill = value; return ITM_OK; }
-  if (key == ITM_DEBUG_DENSE_CLASSIFY) { g_debug_dense_classify = value; return ITM_OK; }
-  if (key == ITM_DEBUG_TRACKER_SESSION_UNUSABLE) { g_debug_tracker_session_unusable = value; return ITM_OK; }
-  if (key == ITM_DEBUG_DENSE_NO_STRIPS) { g_debug_dense_no_strips = value; return ITM_OK; }
-  if (key == ITM_DEBUG_NO_DEFERRED_FUSION) { g_debug_no_deferred_fusion = value; return ITM_OK; }
-  if (key == ITM_DEBUG_FORCE_LIST_STUCK) { g_debug_force_list_stuck = value; return ITM_OK; }
-  if (key == ITM_DEBUG_EXCHANGE_DEVICE_COPY) { g_debug_exchange_device_copy = value; return ITM_OK; }
-  if (key == ITM_DEBUG_EXCHANGE_CORRUPT_WORD) { g_debug_exchange_corrupt_word = value; return ITM_OK; }
-  if (key == ITM_DEBUG_MESH_ATTR_PER_VERTEX) { g_debug_mesh_attr_per_vertex = value; return ITM_OK; }
-  if (key == ITM_DEBUG_MESH_INDEX_WEAK_HASH) { g_debug_mesh_index_weak_hash = value; return ITM_OK; }
-  if (key == ITM_DEBUG_MESH_COMPONENTS_PER_LANE) { g_debug_mesh_components_per_lane = value; return ITM_OK; }
-  if (key == ITM_DEBUG_MESH_SMOOTH_SCATTER) { g_debug_mesh_smooth_scatter = value; return ITM_OK; }
-  if (key == ITM_DEBUG_POSE_QUALITY_ROWS) { g_debug_pose_quality_rows = value; return ITM_OK; }
-  if (key == ITM_DEBUG_FAIL_ALLOCATION) { memory_stats().failAt.store(value > 0 ? value : 0); return ITM_OK; }
-  return set_error(ITM_ERR_INVALID, "unknown debug key");
-}
-
-int itm_debug_counter(int which, void* handle, const uint32_t* set, uint32_t* get) {
-  if (which >= ITM_COUNTER_LIST_EPOCH && which <= ITM_COUNTER_TABLE_EPOCH) {
-    itm_scene* s = (itm_scene*)handle;
-    if (!s) return set_error(ITM_ERR_INVALID, "null scene");
-    if (which == ITM_COUNTER_LIST_EPOCH) { if (get) *get = s->listEpoch; if (set) s->listEpoch = *set; }
-    else if (which == ITM_COUNTER_FRAME_PARITY) {
-      if (set && ((*set ^ s->frameParity) & 1u)) return set_error(ITM_ERR_INVALID, "the frame count keeps its parity");
-      if (get) *get = s->frameParity;
-      if (set) s->frameParity = *set;
-    } else { if (get) *get = s->tableEpoch; if (set) s->tableEpoch = *set; }
-    return ITM_OK;
-  }
-  int rc = debug_counter_tracker(which, handle, set, get);
-  if (rc == -1) rc = debug_counter_colour_tracker(which, handle, set, get);
-  if (rc == -1) rc = debug_counter_ren_tracker(which, handle, set, get);
-  if (rc == -1) rc = debug_counter_pose_quality(which, handle, set, get);
-  if (rc == -1) rc = debug_counter_image_maps(which, handle, set, get);
-  if (rc == -1) rc = debug_counter_aligner(which, handle, set, get);
-  return rc == -1 ? set_error(ITM_ERR_INVALID, "unknown counter") : rc;
-}
-
-int itm_debug_memory(int64_t out[3]) {
-  if (!out) return set_error(ITM_ERR_INVALID, "null argument");
-  const MemoryStats& m = memory_stats();
-  out[0] = m.live.load(); out[1] = m.liveBytes.load(); out[2] = m.attempted.load();
-  return ITM_OK;
-}
-
 int itm_find_surface(const itm_scene* s, const float M[16], const float intr[4], itm_render_state* rs, itm_stream stream) {
   if (!s || !M || !intr || !rs) return set_error(ITM_ERR_INVALID, "null argument");
   if (rs->scene != s) return set_error(ITM_ERR_INVALID, "render state belongs to another scene");
@@ -738,7 +671,7 @@ int itm_process_frame_ahead(itm_scene* s, const itm_view* v, const itm_view* nex
   if (beside) ITM_HIP(hipStreamWaitEvent(st, rs->projectionDone, 0));
   // with the projection done inside the integration launch, the ray-cast workgroups reduce the partial range images of their
   // own cells (raycast_kernel<.., REDUCE>); otherwise CreateExpectedDepths runs as its own launches
-  const bool reduceInRaycast = (fuse || beside) && !g_debug_no_fused_range_reduce;
+  const bool reduceInRaycast = (fuse || beside) && !debug_value(ITM_DEBUG_NO_FUSED_RANGE_REDUCE);
   if (!reduceInRaycast && (rc = launch_expected_depths(s, v->M_d, v->intr_d, rs, hashScene, st, fuse || beside))) return rc;
   const bool ahead = next && hashScene && !s->cfg.useSwapping;
   return launch_icp_maps(s, v, rs, (float4*)points, (float4*)normals, st, reduceInRaycast, ahead ? s : nullptr, ahead ? next : nullptr);

@@ -443,8 +443,8 @@ __device__ inline long long fine_block_base(const VolumeView& vol, int noTotalEn
 static inline VolumeView make_volume(const itm_scene* s) {
   VolumeView v;
   v.hash = s->hash; v.vba = s->vba; v.headBits = s->headBits;
-  v.dirPtr = g_debug_no_directory ? nullptr : s->dirPtr;
-  v.sdfMirror = (g_debug_no_directory || g_debug_no_sdf_mirror) ? nullptr : s->sdfMirror;
+  v.dirPtr = debug_value(ITM_DEBUG_NO_DIRECTORY) ? nullptr : s->dirPtr;
+  v.sdfMirror = (debug_value(ITM_DEBUG_NO_DIRECTORY) || debug_value(ITM_DEBUG_NO_SDF_MIRROR)) ? nullptr : s->sdfMirror;
   v.pageTable = s->org.mTable;
   v.org = s->org;
   v.mask = (uint32_t)s->cfg.bucketNum - 1u; v.bucketNum = s->cfg.bucketNum;
